@@ -36,11 +36,19 @@ unnecessary and does not take them: the figure passes 1 and is not a bound); roo
 bound by -- vector-instruction issue -- with the counters behind it; roofline.write_floor_ms is the stored bytes at the 6.1 TB/s
 plain stores reach on this part.
 
-Besides the headline the JSON line carries (rank 0, N = 1, outside the timed region):
+A plain run sets up, warms up, times the --steps steps and prints the headline line (value, ms_per_step); roofline,
+cpu_baseline and extra_configs are null in it.  --full adds, outside the timed region (rank 0):
+  roofline                       the three byte counts above (counting renders of every frame of a launch), hit_fraction
   roofline.single_frame_launch   the same kernel with ONE frame per launch (the reference's call pattern, engine.cpp:81-92)
   extra_configs                  BASELINE configs[2] (shadow ray + 1 and 2 denoiser passes) and the reference's default
                                  workload (AO 4 x 64, shadow, <= 5 bounces, 2 passes; voxel_render_settings.hpp:21-35):
                                  per-kernel ms, rays, DDA steps and the same algorithmic-byte accounting
+  cpu_baseline                   the scalar C oracle on a sample of the same workload, compared with frame 0 (N = 1)
+  config.assembled_frames_match_single_gpu   (N > 1) finished frames against single-GPU renders of the same poses
+(--no-cpu-baseline / --no-extra-configs drop legs of a --full run.)
+
+--dump-outputs DIR writes what the timed path handed its caller after the last timed step as float32 .npy files: a fixed,
+seeded sample of pixels over all frames of the step (dump_outputs()), the same pixels on every run with the same arguments.
 """
 import argparse
 import hashlib
@@ -87,8 +95,12 @@ def parse_args():
     ap.add_argument("--frames-per-gpu", type=int, default=None,
                     help="frames of the batch per GPU and step; default 128 on one GPU, 32 on several (a rank holds the planes of "
                          "ALL N x F frames of a step: 77 MB each at 1080p)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra-configs", action="store_true", help="skip single_frame_launch and extra_configs (profiling runs)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure the roofline, extra_configs and the CPU baseline, and check the N > 1 assembly")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write a seeded sample of the last timed step's outputs to DIR/<name>.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-extra-configs", action="store_true", help="--full without single_frame_launch and extra_configs (profiling runs)")
     return ap.parse_args()
 
 
@@ -387,6 +399,39 @@ def primary_4k(vrt, torch, engine, scene, NV, pos0, yaw, pitch, W=3840, H=2160, 
             "write_floor_ms": round(px / (STORE_GBS * 1e9) * 1e3, 5)}
 
 
+DUMP_SAMPLES = 1 << 19          # pixels sampled over all frames of a step: 16 floats each at N = 1, 32 MiB in all
+DUMP_SEED = 20261016
+
+
+def dump_outputs(dirname, torch, sb, world, rank):
+    """What the timed path handed its caller after the last timed step, as float32 .npy files.  N = 1: every G-buffer plane
+    of the step's F frames (<plane>.npy, [samples] or [samples, channels]); N > 1: the colour of the finished frames this rank
+    holds (color8_rank<r>.npy).  The pixels are a fixed sample (DUMP_SEED) of frame x row x column, the same on every run with
+    the same arguments; N > 1 ranks share DUMP_SAMPLES between them."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    if world == 1:
+        planes = {n: [g.planes[n] for g in sb.gbs] for n in sb.gbs[0].planes}
+        names = {n: n for n in planes}
+    else:
+        planes = {"color8": [sb.finals[j] for j in range(len(sb.owned_frames()))]}
+        names = {"color8": f"color8_rank{rank}"}
+    nf = len(next(iter(planes.values())))
+    if nf == 0:
+        return
+    H, W = sb.H, sb.W
+    rng = np.random.default_rng(DUMP_SEED + rank)
+    idx = np.sort(rng.integers(0, nf * H * W, min(nf * H * W, DUMP_SAMPLES // world)))
+    frame, pix = idx // (H * W), idx % (H * W)
+    bounds = np.searchsorted(frame, np.arange(nf + 1))
+    dev = next(iter(planes.values()))[0].device
+    sel = [torch.from_numpy(pix[bounds[f]:bounds[f + 1]]).to(dev) for f in range(nf)]
+    for n, frames in planes.items():
+        parts = [frames[f].reshape(H * W, -1)[sel[f]] for f in range(nf) if len(sel[f])]
+        a = torch.cat(parts).to(torch.float32).cpu().numpy()
+        np.save(os.path.join(dirname, names[n] + ".npy"), a[:, 0] if a.shape[1] == 1 else a)
+
+
 def main():
     args = parse_args()
     if args.gpus > 1 and "RANK" not in os.environ:
@@ -483,11 +528,13 @@ def main():
     rays_per_step = F * W * H
     value = rays_per_step * args.steps / dt / 1e6
     kern_ms = float(marks[0].elapsed_time(marks[-1])) / (args.steps * launches_per_step)   # per K1 launch
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, torch, sb, world, rank)
 
     # N > 1: the frames assembled from everybody's strips must be the frames one GPU renders alone (checked on every rank
     # that holds finished frames, outside the timed region)
     assembled_ok = None
-    if world > 1:
+    if world > 1 and args.full:
         mine = list(sb.owned_frames())
         good = 1
         if mine:
@@ -500,8 +547,8 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MIN)
         assembled_ok = bool(t.item())
 
-    out = None
-    if rank == 0:
+    roofline = cpu = extra = hit_fraction = None
+    if rank == 0 and args.full:
         # ---- algorithmic bytes of one K1 launch (1 B per DDA iteration + W*H*B_out) ----
         # S_frames: the iterations of the REFERENCE's loop (every ray walks to a hit, the wall or the end of its budget);
         # M_frames: the iterations the product march really takes (rays end at open cells, untagged blocks are not traced) --
@@ -673,6 +720,10 @@ def main():
             oracle.render_band(osn, pushes[0], oracle.params_from(st.to_c()), r0, r1, planes=["hit_id"], nthreads=1)
             cpu["single_thread"] = {"value": round(W * (r1 - r0) / (time.perf_counter() - c1) / 1e6, 3), "unit": "Mrays/s",
                                     "sample": f"rows {r0}..{r1 - 1} of the same frame, one thread"}
+        hit_fraction = round(hit_frac[0], 4)
+        log(f"timings of last call: {tm}")
+    out = None
+    if rank == 0:
         out = {"metric": "Mrays/sec at 1080p treehouse.vox; achieved HBM GB/s vs MI355X peak",
                "value": round(value, 2), "unit": "Mrays/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
                "ms_per_step": round(dt / args.steps * 1e3, 5), "higher_is_better": True, "scaling": "weak",
@@ -682,10 +733,9 @@ def main():
                                       f"{sb.strip_rows}-row strips over {world} GPU(s)"
                                       + ((", one RCCL all-to-all/step (frame block b assembled on rank b), strip assignment rotated per block"
                                           if sb.owners else ", one RCCL gather/step to rank 0") if world > 1 else ""),
-                          "traversal": args.traversal, "frames_per_step": F, "assembled_frames_match_single_gpu": assembled_ok, "hit_fraction": round(hit_frac[0], 4), "bytes_out_per_px": B_OUT,
+                          "traversal": args.traversal, "frames_per_step": F, "assembled_frames_match_single_gpu": assembled_ok, "hit_fraction": hit_fraction, "bytes_out_per_px": B_OUT,
                           "device": engine.device_info()[0]},
-               "roofline": roofline, "cpu_baseline": cpu, "extra_configs": extra}
-        log(f"timings of last call: {tm}")
+               "roofline": roofline, "cpu_baseline": cpu, "extra_configs": extra, "full": bool(args.full)}
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()

@@ -5,7 +5,8 @@
   default palette, IMAP, legacy MATT, version 200, errors).
 * The expected flattened volume / palette of every file comes from the reference's ogt_vox_read_scene plus
   the restated voxel_scene.cpp flatten (oracle/ref_vox/ref_vox.cpp).
-Outputs: tests/golden/vox_<name>.vox (input bytes) and vox_<name>.npz (rc, voxels, palette, instances, dropped).
+Outputs: tests/golden/vox_<name>.vox (input bytes) and vox_<name>.npz (rc, voxels, palette, instances, dropped);
+refvox_live_cases.npz: the generated scenes of test_reader_matches_reference_parser_live with the reference's results.
 """
 import os
 import struct
@@ -104,7 +105,48 @@ def build():
     return fx
 
 
+LIVE_SEED, LIVE_CASES = 99, 25
+
+
+def live_case_inputs():
+    """The randomly generated scenes of tests/test_vox_reader.py::test_reader_matches_reference_parser_live, in order:
+    (models, groups, instances, palette, metal) as oracle.refvox_write takes them."""
+    rng = np.random.default_rng(LIVE_SEED)
+    perms = [((1, 0, 0), (0, 1, 0), (0, 0, 1)), ((0, 1, 0), (1, 0, 0), (0, 0, 1)), ((0, 0, 1), (0, 1, 0), (1, 0, 0)),
+             ((1, 0, 0), (0, 0, 1), (0, 1, 0)), ((0, 1, 0), (0, 0, 1), (1, 0, 0)), ((0, 0, 1), (1, 0, 0), (0, 1, 0))]
+    for case in range(LIVE_CASES):
+        nm = int(rng.integers(1, 4))
+        models = [rnd_model(rng, *rng.integers(1, 9, 3), fill=float(rng.uniform(0.2, 0.9))) for _ in range(nm)]
+        models = [m if m.any() else np.ones_like(m) for m in models]
+
+        def rx():
+            rows = np.array(perms[int(rng.integers(0, 6))]) * rng.choice([-1, 1], (3, 1))
+            return xform(rows.tolist(), rng.integers(-12, 13, 3).tolist())
+
+        ng = int(rng.integers(1, 4))
+        groups = [(xform(), 0xFFFFFFFF)] + [(rx(), int(rng.integers(0, g))) for g in range(1, ng)]
+        insts = [(int(rng.integers(0, nm)), int(rng.integers(0, ng)), rx(), bool(rng.integers(0, 2))) for _ in range(int(rng.integers(1, 6)))]
+        pal = rng.integers(0, 256, (256, 4)).astype(np.uint8)
+        met = np.where(rng.random(256) < 0.1, rng.random(256), -1).astype(np.float32)
+        yield models, groups, insts, pal, met
+
+
+def record_live_cases():
+    """refvox_live_cases.npz: every live case's file bytes (written by the reference's ogt_vox_write_scene) and what the
+    reference parser + flatten make of it, so that the test runs where oracle/_ref cannot be built."""
+    out = {"n": np.int64(LIVE_CASES)}
+    for case, inputs in enumerate(live_case_inputs()):
+        data = oracle.refvox_write(*inputs)
+        rc, vox, palette, ninst, dropped = oracle.refvox_flatten(data)
+        assert rc == 0, case
+        out.update({f"data{case}": np.frombuffer(data, np.uint8), f"voxels{case}": vox, f"palette{case}": palette,
+                    f"ninst{case}": np.int64(ninst), f"dropped{case}": np.int64(dropped)})
+    np.savez_compressed(os.path.join(HERE, "refvox_live_cases.npz"), **out)
+    print("refvox_live_cases:", LIVE_CASES, "cases")
+
+
 def main():
+    record_live_cases()
     for name, data in build().items():
         rc, vox, palette, ninst, dropped = oracle.refvox_flatten(data)
         open(os.path.join(HERE, f"vox_{name}.vox"), "wb").write(data)

@@ -1,6 +1,6 @@
 """The product's own .vox reader (csrc/vox_reader.cpp, via the host-only C-ABI entry vrt_vox_flatten_host)
-against (a) the committed golden fixtures produced by the reference's ogt_vox.h and (b), when
-oracle/_ref is present, the reference parser itself on freshly generated scenes."""
+against (a) the committed golden fixtures produced by the reference's ogt_vox.h and (b) the reference parser's results on
+generated scenes (recorded; re-derived from the reference parser itself when oracle/_ref is present)."""
 import glob
 import os
 
@@ -36,31 +36,25 @@ def test_reader_matches_golden(vrt, name):
 
 
 def test_reader_matches_reference_parser_live(vrt, oracle):
-    if oracle.refvox() is None:
-        pytest.skip("oracle/_ref not built (needs /root/reference; the GPU box has only the prebuilt .so)")
+    """25 generated scenes (make_vox_fixtures.live_case_inputs) written by the reference's ogt_vox_write_scene: the product's
+    reader against what the reference parser made of them, recorded in refvox_live_cases.npz; where oracle/_ref is present the
+    scenes are also written and parsed again by the reference itself and must match the record."""
     import sys
     sys.path.insert(0, GOLD)
-    from make_vox_fixtures import xform, rnd_model
-    rng = np.random.default_rng(99)
-    perms = [((1, 0, 0), (0, 1, 0), (0, 0, 1)), ((0, 1, 0), (1, 0, 0), (0, 0, 1)), ((0, 0, 1), (0, 1, 0), (1, 0, 0)),
-             ((1, 0, 0), (0, 0, 1), (0, 1, 0)), ((0, 1, 0), (0, 0, 1), (1, 0, 0)), ((0, 0, 1), (1, 0, 0), (0, 1, 0))]
-    for case in range(25):
-        nm = int(rng.integers(1, 4))
-        models = [rnd_model(rng, *rng.integers(1, 9, 3), fill=float(rng.uniform(0.2, 0.9))) for _ in range(nm)]
-        models = [m if m.any() else np.ones_like(m) for m in models]
-
-        def rx():
-            rows = np.array(perms[int(rng.integers(0, 6))]) * rng.choice([-1, 1], (3, 1))
-            return xform(rows.tolist(), rng.integers(-12, 13, 3).tolist())
-
-        ng = int(rng.integers(1, 4))
-        groups = [(xform(), 0xFFFFFFFF)] + [(rx(), int(rng.integers(0, g))) for g in range(1, ng)]
-        insts = [(int(rng.integers(0, nm)), int(rng.integers(0, ng)), rx(), bool(rng.integers(0, 2))) for _ in range(int(rng.integers(1, 6)))]
-        pal = rng.integers(0, 256, (256, 4)).astype(np.uint8)
-        met = np.where(rng.random(256) < 0.1, rng.random(256), -1).astype(np.float32)
-        data = oracle.refvox_write(models, groups, insts, pal, met)
-        rc, evox, epal, eninst, edrop = oracle.refvox_flatten(data)
-        assert rc == 0
+    from make_vox_fixtures import LIVE_CASES, live_case_inputs
+    rec = np.load(os.path.join(GOLD, "refvox_live_cases.npz"))
+    assert int(rec["n"]) == LIVE_CASES
+    live = oracle.refvox() is not None
+    for case, inputs in enumerate(live_case_inputs()):
+        data = rec[f"data{case}"].tobytes()
+        evox, epal = rec[f"voxels{case}"], rec[f"palette{case}"]
+        eninst, edrop = int(rec[f"ninst{case}"]), int(rec[f"dropped{case}"])
+        if live:
+            assert oracle.refvox_write(*inputs) == data, f"case {case}"
+            rc, lvox, lpal, lninst, ldrop = oracle.refvox_flatten(data)
+            assert rc == 0
+            assert lvox.shape == evox.shape and (lvox == evox).all() and (lpal == epal).all(), f"case {case}"
+            assert lninst == eninst and ldrop == edrop
         vox, gpal, ninst, dropped = vrt.vox_flatten_host(data)
         assert vox.shape == evox.shape and (vox == evox).all(), f"case {case}"
         assert ninst == eninst and dropped == edrop

@@ -3,7 +3,7 @@
 for name in "$@"; do
   lib=voxel-raytracing_amd/csrc/libvrt_hip${name}.so
   for tags in 1 0; do
-    VRT_TILE_TAGS=$tags VRT_LIB=$PWD/$lib timeout -k 10 300 python bench.py 2>/dev/null | python -c "
+    VRT_TILE_TAGS=$tags VRT_LIB=$PWD/$lib timeout -k 10 300 python bench.py --full 2>/dev/null | python -c "
 import sys,json
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 e=d['extra_configs']

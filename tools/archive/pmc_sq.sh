@@ -7,7 +7,7 @@ rm -rf $D
 for kv in "$@"; do export "$kv"; done
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 300 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_ACTIVE_INST_VALU SQ_INSTS_VALU SQ_INSTS_SALU SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY \
-    -d $D --output-format csv -- python3 $R/bench.py --no-cpu-baseline --no-extra-configs --steps 20 --warmup 5 > /dev/null 2> $D.err
+    -d $D --output-format csv -- python3 $R/bench.py --full --no-cpu-baseline --no-extra-configs --steps 20 --warmup 5 > /dev/null 2> $D.err
 python3 - <<PY
 import csv, glob, collections
 f = sorted(glob.glob("$D/*/*_counter_collection.csv"))[-1]

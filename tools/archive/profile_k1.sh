@@ -7,7 +7,7 @@ set -e
 R=${GRAFT_REPO_ROOT:-/root/repo}
 rm -rf $R/gpurun_out/prof $R/gpurun_out/pmc_fetch $R/gpurun_out/pmc_write $R/gpurun_out/pmc_sq $R/gpurun_out/pmc_misc
 cd /tmp && export TMPDIR=/tmp
-B="python3 $R/bench.py --no-cpu-baseline"
+B="python3 $R/bench.py --full --no-cpu-baseline"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $R/gpurun_out/prof --output-format csv -- $B --steps 200 --warmup 20 \
     > $R/gpurun_out/prof_bench.json 2> $R/gpurun_out/prof.err
 timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE TCC_EA0_RDREQ_sum -d $R/gpurun_out/pmc_fetch --output-format csv -- $B --steps 20 --warmup 5 \

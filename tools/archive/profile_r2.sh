@@ -9,9 +9,9 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 O=$R/gpurun_out/r2prof
 rm -rf $O; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-B="python3 $R/bench.py --no-cpu-baseline"
+B="python3 $R/bench.py --full --no-cpu-baseline"
 timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $O/trace --output-format csv -- $B --steps 100 --warmup 10 > $O/bench_under_rocprof.json 2> $O/trace.err
-BK="python3 $R/bench.py --no-cpu-baseline --no-extra-configs --steps 20 --warmup 5"
+BK="python3 $R/bench.py --full --no-cpu-baseline --no-extra-configs --steps 20 --warmup 5"
 timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE TCC_EA0_RDREQ_sum -d $O/k1_fetch --output-format csv -- $BK > /dev/null 2> $O/k1_fetch.err
 timeout -k 10 300 rocprofv3 --pmc WRITE_SIZE TCC_EA0_WRREQ_sum -d $O/k1_write --output-format csv -- $BK > /dev/null 2> $O/k1_write.err
 timeout -k 10 300 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_ACTIVE_INST_VALU SQ_INSTS_VALU SQ_INSTS_SALU SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY \

@@ -7,7 +7,7 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 O=$R/gpurun_out/r4prof
 rm -rf $O; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-B="python3 $R/bench.py --no-cpu-baseline --no-extra-configs"
+B="python3 $R/bench.py --full --no-cpu-baseline --no-extra-configs"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/trace --output-format csv -- $B --steps 100 --warmup 10 > $O/bench_under_rocprof.json 2> $O/trace.err
 BK="$B --steps 20 --warmup 5"
 C="python3 $R/tools/run_configs_r4.py"

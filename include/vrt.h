@@ -10,7 +10,7 @@
  * Threading: one vrt_ctx per host thread / per GPU; calls on one context are serialised on its HIP
  * stream (the reference is strictly single-threaded, engine.cpp:28-46).  Frames in flight
  * (MAX_FRAMES_IN_FLIGHT, engine.hpp:19): one context per frame slot; contexts of one device run
- * concurrently and may share a vrt_scene, which is read-only while rendering.  All image pointers in
+ * concurrently and may share a vrt_scene, which is read-only while rendering (vrt_scene_edit_box changes it between launches).  All image pointers in
  * vrt_frame are DEVICE pointers owned by the caller (or allocated with vrt_device_alloc).
  * There is no CPU fallback: without a HIP device every compute call fails with VRT_ERR_NO_DEVICE.
  */
@@ -199,6 +199,34 @@ int  vrt_scene_from_bricks(vrt_ctx* ctx, const uint32_t* grid, uint32_t nbx, uin
  * with a count plane (steps_primary / steps_total) builds -- as large as the first, 9 x the padded voxel bytes.  A later launch
  * with count planes builds it again.  Callers that never attach count planes never hold it.  Waits for the context's stream. */
 int  vrt_scene_trim(vrt_ctx* ctx, vrt_scene* scene);
+/* Scene edits (no reference analogue: the reference uploads its Texture3D once, voxel_scene.cpp:122).  Rewrite the voxels of the
+ * box [lo, lo+size) of a dense scene and bring every structure the march reads up to date -- volume, clearance fields with
+ * their open cells, occupancy pyramid, the list of occupied cells -- byte for byte as vrt_scene_from_dense of the edited volume
+ * would build them, recomputing only what the box can have changed (csrc/vrt_edit.h; an edit whose recomputed cells, summed over
+ * the eight octants, reach half of a full build's, or with a side above 512, rebuilds the fields in full instead).
+ * ids: HOST pointer, size[0]*size[1]*size[2] voxel ids, x fastest (x + y*size[0] + z*size[0]*size[1]); id 0 = empty.
+ * After the call returns, every later launch on any context renders exactly as it would on a scene newly built from the edited
+ * volume.  The edit works on the context's stream and, like vrt_scene_set_sky, waits for it: launches enqueued on this context
+ * before the call see the old volume, later ones the new.  The caller makes sure no OTHER context is still rendering the scene.
+ * A box that is empty (a zero size) or leaves the volume, or a NULL argument: VRT_ERR_INVALID.  A brick scene:
+ * VRT_ERR_UNSUPPORTED.  Writing an id whose material has metallic > 0 makes the scene one whose rays can bounce, and it stays
+ * one when the last such voxel is carved away again (that selects a kernel, never a result).  The count planes' second set of
+ * fields is dropped (the next launch with a count plane builds it again).  The passes keep their scratch memory from edit to
+ * edit; vrt_scene_memory counts it and vrt_scene_trim drops it. */
+int  vrt_scene_edit_box(vrt_ctx* ctx, vrt_scene* scene, const int32_t lo[3], const uint32_t size[3], const uint8_t* ids);
+/* The same with one id for the whole box (0 carves, non-zero fills). */
+int  vrt_scene_fill_box(vrt_ctx* ctx, vrt_scene* scene, const int32_t lo[3], const uint32_t size[3], uint8_t id);
+/* Diagnostics (tests): copy one of a dense scene's device structures to the host, as it lies in memory.  host == NULL only
+ * reports *bytes; a capacity below that is VRT_ERR_INVALID.  VRT_STATE_DF is the whole allocation of the clearance fields: eight
+ * zero-bordered fields, and where the layout has them the ninth with the voxel ids and the 0xFF byte behind it.  Waits for
+ * the context's stream. */
+#define VRT_STATE_VOX   0
+#define VRT_STATE_DF    1
+#define VRT_STATE_OCC1  2
+#define VRT_STATE_OCC2  3
+#define VRT_STATE_OCC3  4
+#define VRT_STATE_CELLS 5   /* the occupied 4^3 cells, x | y << 10 | z << 20, in no particular order */
+int  vrt_debug_scene_state(vrt_ctx* ctx, const vrt_scene* scene, int what, void* host, size_t capacity, size_t* bytes);
 /* Device bytes a scene holds (volume, clearance, pyramid / brick structures, palette, sky, noise). */
 int  vrt_scene_memory(const vrt_scene* sc, uint64_t* bytes);
 /* Host-only half of the loader (no device needed): parse + flatten into malloc'd host memory.

@@ -40,6 +40,14 @@ BUDGET = {
     "k_denoise_pairILb1ELi5EE": ("K3 verified weighted pass, every weight once, tap offset 5 (the reference's pass 2)", 96, 96, 0),
     "k_denoise_pairILb0ELi3EE": ("K3 VRT_DENOISE_FAST weighted pass, every weight once, tap offset 3", 96, 96, 0),
     "k_denoise_p0ILb1EE": ("K3 verified pass 0, a wave to itself (no LDS ring, no barrier)", 64, 96, 0),
+    # scene edits (vrt_scene_edit_box): no register cliff to guard, but none of them may spill
+    "k_edit_writeEPhS0_": ("scene edit: the box's ids into the volume and field 8", 64, 96, 0),
+    "k_edit_occ1EPKh": ("scene edit: occ1 words under the box", 64, 96, 0),
+    "k_edit_occ_upEPKm": ("scene edit: occ2 / occ3 words under the box", 64, 96, 0),
+    "k_edit_pass_xENS_9EditPassXE": ("scene edit: clearance pass x, ballot and carry", 64, 96, 0),
+    "k_edit_pass_ldsENS_9EditPassLE": ("scene edit: clearance passes y and z on LDS", 64, 96, 0),
+    "k_edit_open_scanENS_8EditOpenEi": ("scene edit: open-cell scans along y and z within Q_o", 64, 96, 0),
+    "k_edit_open_xENS_8EditOpenE": ("scene edit: open-cell scan along x and the bytes of Q_o", 64, 96, 0),
 }
 
 

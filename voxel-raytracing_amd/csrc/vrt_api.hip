@@ -154,6 +154,11 @@ struct vrt_scene {
     uint64_t* bentry = nullptr;        // bgrid + bcoarse folded into one word per brick (what the march reads; the two are freed after the build)
     bool bricks = false;
     uint64_t bytes = 0;                // device memory held (volume structures + textures)
+    // scene edits (vrt_scene_edit_box): which materials are metallic, and the passes' scratch memory (kept from edit to edit, counted
+    // in `bytes`, dropped by vrt_scene_trim)
+    bool metal[256] = {};
+    uint8_t* edit_scratch = nullptr;
+    size_t edit_scratch_bytes = 0;
     uint64_t shade_gen = 0;            // changes whenever something a hit's colour depends on does (creation, vrt_scene_set_sky)
 };
 static std::atomic<uint64_t> g_shade_gen{0};
@@ -324,6 +329,7 @@ void vrt_scene_free(vrt_ctx* c, vrt_scene* s)
     if (s->df) hipFree(s->df - s->df_guard);
     if (s->df_counts) hipFree(s->df_counts - s->df_guard);
     if (s->cells) hipFree(s->cells);
+    if (s->edit_scratch) hipFree(s->edit_scratch);
     if (s->palette) hipFree(s->palette);
     if (s->sky) hipFree(s->sky);
     if (s->noise) hipFree(s->noise);
@@ -412,6 +418,38 @@ static hipError_t build_fields(vrt_ctx* c, const vrt_scene* s, uint8_t* dst, boo
     return e != hipSuccess ? e : sync;
 }
 
+// The occupied 4^3 cells of a dense scene as a list (from the 16^3 summaries: one bit per cell), for the tile tags of a launch.
+// Replaces the list the scene holds; above 4 << 20 cells the scene goes without (the tags then cost more than they save).
+static hipError_t build_cell_list(vrt_ctx* c, vrt_scene* s)
+{
+    const VolumeView& d = s->d.vol;
+    if (s->cells) { hipFree(s->cells); s->bytes -= (uint64_t)s->n_cells * 4; }
+    s->cells = nullptr; s->n_cells = 0; s->cells_ok = false;
+    if (d.n1x > 1024 || d.n1y > 1024 || d.n1z > 1024) return hipSuccess;
+    const size_t n2 = (size_t)d.n2x * d.n2y * d.n2z;
+    std::vector<uint64_t> h2(n2);
+    hipError_t e = hipMemcpyAsync(h2.data(), s->occ2, n2 * 8, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) return e;
+    std::vector<uint32_t> cells;
+    for (size_t w = 0; w < n2; w++) {
+        uint64_t bits = h2[w];
+        if (!bits) continue;
+        const uint32_t wx = (uint32_t)(w % (size_t)d.n2x), wy = (uint32_t)((w / (size_t)d.n2x) % (size_t)d.n2y), wz = (uint32_t)(w / ((size_t)d.n2x * d.n2y));
+        for (uint32_t b = 0; b < 64; b++)
+            if ((bits >> b) & 1ull) cells.push_back((wx * 4u + (b & 3u)) | ((wy * 4u + ((b >> 2) & 3u)) << 10) | ((wz * 4u + (b >> 4)) << 20));
+    }
+    if (cells.size() > (4u << 20)) return hipSuccess;
+    if (!cells.empty()) {
+        if ((e = hipMalloc((void**)&s->cells, cells.size() * 4)) != hipSuccess) { s->cells = nullptr; return e; }
+        if ((e = hipMemcpy(s->cells, cells.data(), cells.size() * 4, hipMemcpyHostToDevice)) != hipSuccess) return e;
+        s->bytes += cells.size() * 4;
+    }
+    s->n_cells = (uint32_t)cells.size();
+    s->cells_ok = true;
+    return hipSuccess;
+}
+
 // The fields a launch that writes count planes marches through (no open cells: the iterations of the reference's loop, to the
 // wall), built on first use.
 static int fields_for_counts(vrt_ctx* c, const vrt_scene* cs, const uint8_t** out)
@@ -472,6 +510,7 @@ int vrt_scene_from_dense(vrt_ctx* c, const uint8_t* voxels, uint32_t W, uint32_t
     }
 #define SCHK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { rc = fail(VRT_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); goto bad; } } while (0)
     s->metallic_voxels = any_metallic(voxels, nvox, palette);
+    for (int i = 1; i < 256; i++) s->metal[i] = palette[i].metallic > 0.0f;
     SCHK(hipMalloc((void**)&s->vox, nvox));
     SCHK(hipMalloc((void**)&s->occ1, n1 * 8));
     SCHK(hipMalloc((void**)&s->occ2, n2pad * 8));
@@ -498,29 +537,8 @@ int vrt_scene_from_dense(vrt_ctx* c, const uint8_t* voxels, uint32_t W, uint32_t
     SCHK(hipMemcpyAsync(s->vox, voxels, nvox, hipMemcpyHostToDevice, c->stream));
     SCHK(hipMemcpyAsync(s->palette, palette, 256 * sizeof(vrt_material), hipMemcpyHostToDevice, c->stream));
     SCHK(launch_build_pyramid(s->vox, d.W, d.H, d.D, s->occ1, s->occ2, s->occ3, c->stream));
-    // the occupied 4^3 cells as a list (from the 16^3 summaries: one bit per cell), for the tile tags of a launch
-    if (d.n1x <= 1024 && d.n1y <= 1024 && d.n1z <= 1024) {
-        std::vector<uint64_t> h2(n2);
-        SCHK(hipMemcpyAsync(h2.data(), s->occ2, n2 * 8, hipMemcpyDeviceToHost, c->stream));
-        SCHK(hipStreamSynchronize(c->stream));
-        std::vector<uint32_t> cells;
-        for (size_t w = 0; w < n2; w++) {
-            uint64_t bits = h2[w];
-            if (!bits) continue;
-            const uint32_t wx = (uint32_t)(w % (size_t)d.n2x), wy = (uint32_t)((w / (size_t)d.n2x) % (size_t)d.n2y), wz = (uint32_t)(w / ((size_t)d.n2x * d.n2y));
-            for (uint32_t b = 0; b < 64; b++)
-                if ((bits >> b) & 1ull) cells.push_back((wx * 4u + (b & 3u)) | ((wy * 4u + ((b >> 2) & 3u)) << 10) | ((wz * 4u + (b >> 4)) << 20));
-        }
-        if (cells.size() <= (4u << 20)) {                                   // (beyond that the tags cost more than they save)
-            if (!cells.empty()) {
-                SCHK(hipMalloc((void**)&s->cells, cells.size() * 4));
-                SCHK(hipMemcpy(s->cells, cells.data(), cells.size() * 4, hipMemcpyHostToDevice));
-                s->bytes += cells.size() * 4;
-            }
-            s->n_cells = (uint32_t)cells.size();
-            s->cells_ok = true;
-        }
-    }
+    // the occupied 4^3 cells as a list, for the tile tags of a launch
+    SCHK(build_cell_list(c, s));
     {
         s->open_cells = c->opt.open_cells != 0;                           // development switch: 0 = fields without open cells
         SCHK(build_fields(c, s, s->df, s->open_cells));
@@ -669,6 +687,94 @@ int vrt_scene_trim(vrt_ctx* c, vrt_scene* s)
         s->df_counts = nullptr;
         s->bytes -= s->df_bytes;
     }
+    if (s->edit_scratch) {                                       // (an edit takes it again)
+        hipFree(s->edit_scratch);
+        s->edit_scratch = nullptr;
+        s->bytes -= s->edit_scratch_bytes;
+        s->edit_scratch_bytes = 0;
+    }
+    return VRT_OK;
+}
+
+// vrt_scene_edit_box / vrt_scene_fill_box: ids == NULL fills the box with `id`
+static int scene_edit(vrt_ctx* c, vrt_scene* s, const int32_t lo[3], const uint32_t size[3], const uint8_t* ids, uint8_t id, const char* who)
+{
+    const std::string name(who);
+    if (s->bricks) return fail(VRT_ERR_UNSUPPORTED, name + ": brick scenes cannot be edited");
+    const VolumeView& d = s->d.vol;
+    const int dim[3] = {d.W, d.H, d.D};
+    EditBox b;
+    b.W = d.W; b.H = d.H; b.D = d.D;
+    for (int a = 0; a < 3; a++) {
+        if (size[a] == 0) return fail(VRT_ERR_INVALID, name + ": the box is empty");
+        if (lo[a] < 0 || lo[a] >= dim[a] || (uint64_t)size[a] > (uint64_t)(dim[a] - lo[a])) return fail(VRT_ERR_INVALID, name + ": the box leaves the volume");
+        b.lo[a] = lo[a]; b.hi[a] = lo[a] + (int)size[a];
+    }
+    const size_t nbox = (size_t)size[0] * size[1] * size[2];
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    std::lock_guard<std::mutex> lock(s->lazy);
+    if (!s->metallic_voxels) {
+        if (ids) { for (size_t i = 0; i < nbox && !s->metallic_voxels; i++) s->metallic_voxels = ids[i] != 0 && s->metal[ids[i]]; }
+        else s->metallic_voxels = id != 0 && s->metal[id];
+    }
+    // the count planes' fields are built again by the next launch that asks for them
+    if (s->df_counts) { hipFree(s->df_counts - s->df_guard); s->df_counts = nullptr; s->bytes -= s->df_bytes; }
+    const bool in_place = edit_in_place(d.W, d.H, d.D, b.lo, b.hi, VRT_EDIT_CAP);
+    size_t need = ids ? ((nbox + 255u) & ~(size_t)255u) : 0;
+    const size_t ids_room = need;
+    if (in_place) need += edit_scratch_bytes(b, s->open_cells);
+    if (need > s->edit_scratch_bytes) {
+        if (s->edit_scratch) { hipFree(s->edit_scratch); s->bytes -= s->edit_scratch_bytes; }
+        s->edit_scratch = nullptr; s->edit_scratch_bytes = 0;
+        HIPCHK(hipMalloc((void**)&s->edit_scratch, need));
+        s->edit_scratch_bytes = need; s->bytes += need;
+    }
+    if (ids) HIPCHK(hipMemcpyAsync(s->edit_scratch, ids, nbox, hipMemcpyHostToDevice, c->stream));
+    const size_t ndf = (size_t)d.df_stride;
+    HIPCHK(launch_edit_write(s->vox, d.df_fast ? s->df + 8 * ndf : nullptr, b, ids ? s->edit_scratch : nullptr, id, c->stream));
+    HIPCHK(launch_edit_pyramid(s->vox, b, s->occ1, s->occ2, s->occ3, c->stream));
+    if (in_place) HIPCHK(launch_edit_fields(s->vox, b, s->df, ndf, s->edit_scratch + ids_room, s->open_cells, c->stream));
+    else HIPCHK(build_fields(c, s, s->df, s->open_cells));
+    HIPCHK(build_cell_list(c, s));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return VRT_OK;
+}
+
+int vrt_scene_edit_box(vrt_ctx* c, vrt_scene* s, const int32_t lo[3], const uint32_t size[3], const uint8_t* ids)
+{
+    if (!c || !s || !lo || !size || !ids) return fail(VRT_ERR_INVALID, "vrt_scene_edit_box: NULL argument");
+    return scene_edit(c, s, lo, size, ids, 0, "vrt_scene_edit_box");
+}
+
+int vrt_scene_fill_box(vrt_ctx* c, vrt_scene* s, const int32_t lo[3], const uint32_t size[3], uint8_t id)
+{
+    if (!c || !s || !lo || !size) return fail(VRT_ERR_INVALID, "vrt_scene_fill_box: NULL argument");
+    return scene_edit(c, s, lo, size, nullptr, id, "vrt_scene_fill_box");
+}
+
+int vrt_debug_scene_state(vrt_ctx* c, const vrt_scene* s, int what, void* host, size_t capacity, size_t* bytes)
+{
+    if (!c || !s || !bytes) return fail(VRT_ERR_INVALID, "vrt_debug_scene_state: NULL argument");
+    if (s->bricks) return fail(VRT_ERR_UNSUPPORTED, "vrt_debug_scene_state: dense scenes only");
+    const VolumeView& d = s->d.vol;
+    const void* src = nullptr;
+    size_t n = 0;
+    switch (what) {
+    case VRT_STATE_VOX:   src = s->vox;  n = (size_t)d.W * d.H * d.D; break;
+    case VRT_STATE_DF:    src = s->df;   n = s->df_bytes; break;
+    case VRT_STATE_OCC1:  src = s->occ1; n = (size_t)d.n1x * d.n1y * d.n1z * 8; break;
+    case VRT_STATE_OCC2:  src = s->occ2; n = (size_t)d.n2x * d.n2y * d.n2z * 8; break;
+    case VRT_STATE_OCC3:  src = s->occ3; n = (size_t)d.n3x * d.n3y * d.n3z * 8; break;
+    case VRT_STATE_CELLS: src = s->cells; n = (size_t)s->n_cells * 4; break;
+    default: return fail(VRT_ERR_INVALID, "vrt_debug_scene_state: unknown structure");
+    }
+    *bytes = n;
+    if (!host) return VRT_OK;
+    if (capacity < n) return fail(VRT_ERR_INVALID, "vrt_debug_scene_state: the host buffer is too small");
+    HIPCHK(hipSetDevice(c->device));
+    if (n) HIPCHK(hipMemcpyAsync(host, src, n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
     return VRT_OK;
 }
 

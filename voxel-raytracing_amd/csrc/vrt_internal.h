@@ -9,6 +9,7 @@
 #include "vrt_traverse.h"
 #include "vrt_sky.h"
 #include "vrt_tags.h"
+#include "vrt_edit.h"
 
 namespace vrt {
 
@@ -268,6 +269,12 @@ hipError_t launch_open_cells(const uint8_t* vox, int W, int H, int D, uint8_t* d
 hipError_t launch_tile_tags(const GeomParams& p, hipStream_t s);
 hipError_t launch_hit_colors(const GeomParams& p, uint32_t* table, hipStream_t s);
 hipError_t launch_pad_vox(const uint8_t* vox, int W, int H, int D, uint8_t* dst, hipStream_t s);
+// scene edits: the volume and the box [lo, hi) of it that is rewritten
+struct EditBox { int W, H, D; int lo[3], hi[3]; };
+hipError_t launch_edit_write(uint8_t* vox, uint8_t* field8, const EditBox& b, const uint8_t* ids_dev, int id, hipStream_t s);
+hipError_t launch_edit_pyramid(const uint8_t* vox, const EditBox& b, uint64_t* occ1, uint64_t* occ2, uint64_t* occ3, hipStream_t s);
+size_t     edit_scratch_bytes(const EditBox& b, bool open);
+hipError_t launch_edit_fields(const uint8_t* vox, const EditBox& b, uint8_t* df, size_t stride, uint8_t* scratch, bool open, hipStream_t s);
 hipError_t launch_primary(const GeomParams& p, hipStream_t s);
 hipError_t launch_shade(const GeomParams& p, hipStream_t s);
 hipError_t launch_denoise_pass(const DenoiseParams& p, hipStream_t s);

@@ -379,6 +379,34 @@ class VoxelScene:
         """Drop the diagnostic copy of the clearance fields a launch with count planes built (vrt_scene_trim)."""
         check(lib().vrt_scene_trim(self.engine.ctx, self._h))
 
+    def edit(self, lo, ids: np.ndarray) -> None:
+        """Rewrite a box of a dense scene (vrt_scene_edit_box).  lo: (x, y, z) of its low corner; ids: uint8 array indexed [z, y, x]
+        like from_dense's voxels (anything else is converted the same way), whose shape is the box.  Every later launch renders as
+        on a scene newly built from the edited volume."""
+        v = np.ascontiguousarray(ids, dtype=np.uint8)
+        if v.ndim != 3:
+            raise ValueError("VoxelScene.edit: ids must be indexed [z, y, x]")
+        d, h, w = v.shape
+        self._raise(lib().vrt_scene_edit_box(self.engine.ctx, self.handle, (C.c_int32 * 3)(*[int(t) for t in lo]), (C.c_uint32 * 3)(w, h, d),
+                                             v.ctypes.data_as(C.c_void_p)))
+
+    def fill(self, lo, size, id: int) -> None:
+        """One id for the whole box lo .. lo + size, both (x, y, z) (vrt_scene_fill_box): 0 carves, non-zero fills."""
+        if any(int(t) < 0 for t in size) or not 0 <= int(id) <= 255:
+            raise ValueError("VoxelScene.fill: negative size or id outside 0..255")
+        self._raise(lib().vrt_scene_fill_box(self.engine.ctx, self.handle, (C.c_int32 * 3)(*[int(t) for t in lo]),
+                                             (C.c_uint32 * 3)(*[int(t) for t in size]), int(id)))
+
+    def debug_state(self, what: int) -> np.ndarray:
+        """One of a dense scene's device structures as it lies in memory (vrt_debug_scene_state; _capi.STATE_*): uint8 for the
+        voxels and the clearance fields, uint64 for the pyramid levels, uint32 for the occupied cells."""
+        n = C.c_size_t()
+        self._raise(lib().vrt_debug_scene_state(self.engine.ctx, self.handle, int(what), None, 0, C.byref(n)))
+        dt = {_capi.STATE_OCC1: np.uint64, _capi.STATE_OCC2: np.uint64, _capi.STATE_OCC3: np.uint64, _capi.STATE_CELLS: np.uint32}.get(int(what), np.uint8)
+        out = np.empty(n.value // np.dtype(dt).itemsize, dtype=dt)
+        self._raise(lib().vrt_debug_scene_state(self.engine.ctx, self.handle, int(what), out.ctypes.data_as(C.c_void_p), out.nbytes, C.byref(n)))
+        return out
+
     def memory_bytes(self) -> int:
         n = C.c_uint64()
         check(lib().vrt_scene_memory(self._h, C.byref(n)))

@@ -1,6 +1,6 @@
 """K3 decodes UNORM8 / SNORM8 guides with q0 = c*r, q = fma(fma(-D, q0, c), r, q0), r = RN(1/D), instead of the
 IEEE division c/D the spec (and the oracle) use.  The two agree for every one of the 256 codes; this is the
-exhaustive check, in exact rational arithmetic (csrc/vrt_device.hip: decode_unorm8 / decode_snorm8)."""
+exhaustive check, in exact rational arithmetic (csrc/vrt_device_common.h: decode_unorm8 / decode_snorm8)."""
 import math
 from fractions import Fraction as F
 

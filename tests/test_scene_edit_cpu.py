@@ -37,7 +37,7 @@ def test_updated_fields_equal_the_rebuilt_ones(seed):
 
 
 def test_cap_matches_the_fields():
-    dev = open(os.path.join(ROOT, "voxel-raytracing_amd", "csrc", "vrt_device.hip")).read()
+    dev = open(os.path.join(ROOT, "voxel-raytracing_amd", "csrc", "vrt_device_common.h")).read()
     hdr = open(HDR).read()
     assert re.search(r"#define VRT_DF_CAP (\d+)", dev).group(1) == re.search(r"#define VRT_EDIT_CAP (\d+)", hdr).group(1)
 

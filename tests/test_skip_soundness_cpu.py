@@ -1,5 +1,5 @@
 """CPU checks (oracle only, no GPU) of the two claims the march-skipping structures of the HIP path rest on:
-  * open cells (vrt_device.hip launch_open_cells): a ray standing on an empty voxel with no solid voxel in the box between the
+  * open cells (vrt_scene_build.hip launch_open_cells): a ray standing on an empty voxel with no solid voxel in the box between the
     voxel and the volume's corner in the octant of its direction hits nothing, whatever its direction within the octant;
   * tile tags (k_tile_tags): the pixel of a primary ray that hits a voxel lies inside the screen rectangle of that voxel's
     4^3 cell grown by one voxel (+ 2 pixels) under the projection [U V C] (a, b, lambda)^T = p - cam."""

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Lint of the hand-written gfx950 assembly blocks (csrc/vrt_traverse.h and whatever else vrt_device.hip includes), on the
-PREPROCESSED device source, so that every macro-built variant of a block (the counting twins, the prefetching form ...) is seen
+"""Lint of the hand-written gfx950 assembly blocks (csrc/vrt_traverse.h and whatever else the device objects include), on the
+PREPROCESSED source of every device object (each distinct statement once), so that every macro-built variant of a block (the counting twins, the prefetching form ...) is seen
 as the compiler sees it.  The compiler keeps its own values out of the registers a block declares clobbered and out of its
 output operands; what nobody checked until round 4 is the other direction -- that a block only WRITES what it declared:
 
@@ -25,18 +25,26 @@ NO_DEST = ("s_cbranch", "s_branch", "s_waitcnt", "s_nop", "s_cmp", "s_bitcmp", "
 # v_cmp_* writes vcc (e32) or its first operand (e64: an SGPR pair)
 
 
+# the device objects as the Makefile builds them: (source, extra flags)
+OBJECTS = [("vrt_device.hip", ["-DVRT_K1_PART=%d" % n]) for n in range(4)] + [(n, []) for n in ("vrt_denoise.hip", "vrt_scene_edit.hip", "vrt_scene_build.hip", "vrt_post.hip")]
+
+
 def preprocessed():
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    p = subprocess.run([hipcc, "--offload-arch=gfx950", "--cuda-device-only", "-std=c++17", "-E", "-P", "vrt_device.hip"],
-                       cwd=CSRC, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
-    if p.returncode != 0:
-        raise RuntimeError("hipcc -E failed:\n" + p.stderr[-3000:])
-    return p.stdout
+    out = []
+    for src, extra in OBJECTS:
+        p = subprocess.run([hipcc, "--offload-arch=gfx950", "--cuda-device-only", "-std=c++17", "-E", "-P"] + extra + [src],
+                           cwd=CSRC, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
+        if p.returncode != 0:
+            raise RuntimeError("hipcc -E failed:\n" + p.stderr[-3000:])
+        out.append(p.stdout)
+    return "\n".join(out)
 
 
 def asm_statements(src):
-    """(template text, outputs, inputs, clobbers) of every asm statement with operands"""
-    out = []
+    """(template text, outputs, inputs, clobbers) of every distinct asm statement with operands (a header's statement reaches the
+    lint once per object that includes it)"""
+    out, seen = [], set()
     for m in re.finditer(r"\basm\s+(?:volatile\s*)?\(", src):
         i = m.end()
         depth, j, in_str = 1, i, False
@@ -50,6 +58,9 @@ def asm_statements(src):
             elif ch == ")": depth -= 1
             j += 1
         body = src[i:j - 1]
+        if body in seen:
+            continue
+        seen.add(body)
         # split at top-level ':' (outside strings and parentheses)
         parts, cur, depth, in_str, k = [], [], 0, False, 0
         while k < len(body):

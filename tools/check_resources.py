@@ -1,16 +1,18 @@
 #!/usr/bin/env python3
-"""Register budget of the hand-scheduled kernels (csrc/vrt_device.hip), checked at build time.
+"""Register budget of the hand-scheduled kernels (csrc: the parts of vrt_device.hip, vrt_denoise.hip, vrt_scene_edit.hip), checked
+at build time.
 
 K1's look-up loop pins physical registers and the kernel sits at two occupancy cliffs that the compiler's own remark does
 not show: past 80 scalar registers a SIMD holds seven of these waves, not eight (measured: DESIGN.md 5, "Tile tags"), and
 past 64 vector registers likewise.  `make -C voxel-raytracing_amd/csrc resources` (and tests/test_kernel_resources.py)
-compile the device code with -Rpass-analysis=kernel-resource-usage and fail when a product kernel leaves its budget: one more
+compile these objects (side by side, four at a time) with -Rpass-analysis=kernel-resource-usage and fail when a product kernel leaves its budget: one more
 live scalar then breaks the build instead of silently costing 7 %.
 """
 import os
 import re
 import subprocess
 import sys
+from concurrent.futures import ThreadPoolExecutor
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "voxel-raytracing_amd", "csrc")
@@ -51,16 +53,26 @@ BUDGET = {
 }
 
 
-def report():
+# the objects that hold budgeted kernels, as the Makefile builds them: (source, extra flags); slowest first
+OBJECTS = [("vrt_device.hip", ["-DVRT_K1_PART=%d" % n]) for n in (3, 0, 1, 2)] + [("vrt_denoise.hip", []), ("vrt_scene_edit.hip", [])]
+
+
+def remarks(obj):
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     flags = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math",
              "-fhip-fp32-correctly-rounded-divide-sqrt", "-Wno-unused-function", "-Wno-unused-result", "-Wno-unused-value", "-Wno-pass-failed",
-             "-Rpass-analysis=kernel-resource-usage", "-c", "-o", "/dev/null", "vrt_device.hip"]
-    p = subprocess.run([hipcc] + flags, cwd=CSRC, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+             "-Rpass-analysis=kernel-resource-usage", "-c", "-o", "/dev/null"]
+    p = subprocess.run([hipcc] + flags + obj[1] + [obj[0]], cwd=CSRC, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     if p.returncode != 0:
         raise RuntimeError("hipcc failed:\n" + p.stdout[-4000:])
+    return p.stdout
+
+
+def report():
+    with ThreadPoolExecutor(max_workers=4) as pool:                  # four compiler processes at a time
+        out = "\n".join(pool.map(remarks, OBJECTS))
     kernels, cur = {}, None
-    for line in p.stdout.splitlines():
+    for line in out.splitlines():
         m = re.search(r"Function Name: (\S+)", line)
         if m:
             cur = kernels.setdefault(m.group(1), {})

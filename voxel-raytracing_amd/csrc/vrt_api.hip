@@ -1,5 +1,5 @@
 // vrt_api.hip -- the C-ABI of libvrt_hip.so (include/vrt.h): contexts, scenes, the geometry and
-// denoiser stages, strip packing.  Host code only; kernels live in vrt_device.hip.
+// denoiser stages, strip packing.  Host code only; kernels live in the other .hip files.
 //
 // Call surface mirrored from the reference (paths relative to its root):
 //   VoxelScene ctor            source/voxels/resource/voxel_scene.cpp:33-133

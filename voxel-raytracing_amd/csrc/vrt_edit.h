@@ -1,5 +1,5 @@
 // vrt_edit.h -- which bytes of a dense scene's clearance fields an edit of a box of voxels can change (vrt_scene_edit_box).
-// Plain integer arithmetic, compiled for the device (vrt_device.hip), the host (vrt_api.hip) and the tests
+// Plain integer arithmetic, compiled for the device (vrt_scene_edit.hip), the host (vrt_api.hip) and the tests
 // (tests/native/edit_host.cpp, which checks every statement below against a brute-force rebuild).
 //
 // Octant o has the signs s = (bit 0: +x, bit 1: +y, bit 2: +z; a clear bit: -).  c_o(p) = min(cap, distance in the octant's
@@ -23,7 +23,7 @@
 #define VRT_EDIT_HD inline
 #endif
 
-#define VRT_EDIT_CAP 127          // == VRT_DF_CAP (vrt_device.hip asserts it)
+#define VRT_EDIT_CAP 127          // == VRT_DF_CAP (vrt_device_common.h; vrt_scene_edit.hip asserts it)
 #define VRT_EDIT_MAX_SIDE 512     // a longer box side is rebuilt in full: the scan kernels hold a line of side + 2 (cap - 1) in LDS
 
 namespace vrt {

@@ -1,5 +1,5 @@
-// vrt_internal.h -- structures shared between the C-ABI layer (vrt_api.cpp) and the HIP kernels
-// (vrt_device.hip).  Not part of the public interface.
+// vrt_internal.h -- structures shared between the C-ABI layer (vrt_api.hip) and the HIP kernels
+// (one .hip file per stage).  Not part of the public interface.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -253,7 +253,8 @@ struct BlitParams {
     int32_t sw, sh, tw, th;
 };
 
-// launchers (vrt_device.hip)
+// launchers: scene build (vrt_scene_build.hip), scene edits (vrt_scene_edit.hip), render (vrt_device.hip: sky, tile tags, hit
+// colours, K1, K2), K3 (vrt_denoise.hip), rows / blit / accumulate / resolve (vrt_post.hip)
 hipError_t launch_build_pyramid(const uint8_t* vox, int W, int H, int D, uint64_t* occ1, uint64_t* occ2,
                                 uint64_t* occ3, hipStream_t s);
 hipError_t launch_build_df(const uint8_t* vox, int W, int H, int D, uint8_t* df, size_t stride, uint8_t* tmp0, uint8_t* tmp1, hipStream_t s, int cap = 0 /* 0: the dense scene's cap */);

@@ -1907,7 +1907,12 @@ VRT_HD uint64_t brick_entry_pack(uint32_t ptr, const uint8_t coarse[8])
 // brick; only a lane inside an OCCUPIED brick goes on to its per-voxel byte.  The arithmetic for the empty-brick answer runs
 // for every lane (a dozen instructions, no branch); 32-bit offsets while the padded grid is below 2^29 bricks.
 #if defined(VRT_TRACE_COUNTERS) && defined(__HIPCC__)
-// development build only: look-ups of the brick march by kind, summed over the lanes of all rays (vrt_debug_counters)
+// development build only: look-ups of the brick march by kind, summed over the lanes of all rays (vrt_debug_counters).
+// Defined in one object: part 0 of vrt_device.hip, which holds the brick march's kernels and debug_brick_counts.  Every other
+// object that includes this header counts into a copy of its own that nobody reads (the brick march's counting twins of part 2).
+#if !(defined(VRT_K1_PART) && VRT_K1_PART == 0)
+static
+#endif
 __device__ unsigned long long g_vrt_brick_counts[4];   // lanes looking up, ... in an occupied brick, ... that found a solid voxel, ... in the border / an open brick
 #endif
 VRT_HD uint32_t brick_clear(const VolumeView& v, int mx, int my, int mz, uint32_t oct, int sx, int sy, int sz, uint32_t& material, uint32_t* bytes = nullptr)

@@ -8,7 +8,7 @@ block to the rank that owns the block, issued together as a single all-to-all (S
 a ring-neighbour exchange of `halo` guide rows (strip s needs rows of strips s-1 and s+1, which live on
 ranks r-1 and r+1).
 
-The row maps here are the host mirror of vrt_pack_rows / vrt_pack_halo (csrc/vrt_device.hip: k_rows); the
+The row maps here are the host mirror of vrt_pack_rows / vrt_pack_halo (csrc/vrt_post.hip: k_rows); the
 CPU tests check both against each other.
 """
 import ctypes as C

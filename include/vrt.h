@@ -208,24 +208,41 @@ int  vrt_scene_trim(vrt_ctx* ctx, vrt_scene* scene);
  * After the call returns, every later launch on any context renders exactly as it would on a scene newly built from the edited
  * volume.  The edit works on the context's stream and, like vrt_scene_set_sky, waits for it: launches enqueued on this context
  * before the call see the old volume, later ones the new.  The caller makes sure no OTHER context is still rendering the scene.
- * A box that is empty (a zero size) or leaves the volume, or a NULL argument: VRT_ERR_INVALID.  A brick scene:
- * VRT_ERR_UNSUPPORTED.  Writing an id whose material has metallic > 0 makes the scene one whose rays can bounce, and it stays
+ * A box that is empty (a zero size) or leaves the volume, or a NULL argument: VRT_ERR_INVALID.  A brick scene that
+ * vrt_scene_reserve_bricks has not made editable: VRT_ERR_UNSUPPORTED.  Writing an id whose material has metallic > 0 makes the scene one whose rays can bounce, and it stays
  * one when the last such voxel is carved away again (that selects a kernel, never a result).  The count planes' second set of
  * fields is dropped (the next launch with a count plane builds it again).  The passes keep their scratch memory from edit to
  * edit; vrt_scene_memory counts it and vrt_scene_trim drops it. */
 int  vrt_scene_edit_box(vrt_ctx* ctx, vrt_scene* scene, const int32_t lo[3], const uint32_t size[3], const uint8_t* ids);
 /* The same with one id for the whole box (0 carves, non-zero fills). */
 int  vrt_scene_fill_box(vrt_ctx* ctx, vrt_scene* scene, const int32_t lo[3], const uint32_t size[3], uint8_t id);
-/* Diagnostics (tests): copy one of a dense scene's device structures to the host, as it lies in memory.  host == NULL only
+/* Makes a brick scene editable: room for capacity_bricks bricks in its pool, and the structures an edit updates kept on the
+ * device (padded pointer grid, brick occupancy, the eight coarse fields before they are folded into the entries: 5 bytes per
+ * brick of the padded grid more, and 4.5 KiB per reserved brick).  capacity_bricks below the number of occupied bricks, or above
+ * 2^24 - 3: VRT_ERR_INVALID; a dense scene: VRT_ERR_UNSUPPORTED.  Calling it again with a larger capacity grows the
+ * reservation; one that is not larger changes nothing.  What the scene renders is unchanged, bit for bit.  Waits for the
+ * context's stream, like an edit.  vrt_scene_memory counts the reservation and vrt_scene_trim keeps it.
+ * vrt_scene_edit_box / vrt_scene_fill_box then work on the scene under the dense scene's contract, and leave every structure
+ * the march reads as vrt_scene_from_bricks of the edited volume would build it (up to which pool slot a brick lies in): a brick
+ * whose 512 voxels all become 0 becomes an empty brick and its slot is free again, an empty brick that receives a non-zero id
+ * takes a free slot.  Only the bricks the box meets and their neighbours are recomputed, and the brick-level fields only if
+ * some brick's occupancy changed (csrc/vrt_brick_edit.h).  An edit that needs more slots than are free changes nothing and
+ * returns VRT_ERR_UNSUPPORTED; reserve more and repeat it. */
+int  vrt_scene_reserve_bricks(vrt_ctx* ctx, vrt_scene* scene, uint32_t capacity_bricks);
+/* Diagnostics (tests): copy one of a scene's device structures to the host, as it lies in memory.  host == NULL only
  * reports *bytes; a capacity below that is VRT_ERR_INVALID.  VRT_STATE_DF is the whole allocation of the clearance fields: eight
- * zero-bordered fields, and where the layout has them the ninth with the voxel ids and the 0xFF byte behind it.  Waits for
- * the context's stream. */
+ * zero-bordered fields, and where the layout has them the ninth with the voxel ids and the 0xFF byte behind it.  Selectors 0 - 4
+ * are a dense scene's, 6 - 8 a brick scene's (the other kind: VRT_ERR_UNSUPPORTED), the cell list either's.  Waits for the
+ * context's stream. */
 #define VRT_STATE_VOX   0
 #define VRT_STATE_DF    1
 #define VRT_STATE_OCC1  2
 #define VRT_STATE_OCC2  3
 #define VRT_STATE_OCC3  4
-#define VRT_STATE_CELLS 5   /* the occupied 4^3 cells, x | y << 10 | z << 20, in no particular order */
+#define VRT_STATE_CELLS 5   /* the occupied 4^3 cells (brick scenes: the occupied bricks), x | y << 10 | z << 20, in no particular order */
+#define VRT_STATE_BENTRY 6  /* one packed 8-byte word per brick of the padded grid ((nbx+2)(nby+2)(nbz+2); VolumeView::bentry) */
+#define VRT_STATE_BPOOL  7  /* the voxel ids, 512 bytes per pool slot, for every slot the pool has room for; a slot no entry points to holds anything */
+#define VRT_STATE_BFINE  8  /* the per-voxel clearances, 8 x 512 bytes per pool slot, likewise */
 int  vrt_debug_scene_state(vrt_ctx* ctx, const vrt_scene* scene, int what, void* host, size_t capacity, size_t* bytes);
 /* Device bytes a scene holds (volume, clearance, pyramid / brick structures, palette, sky, noise). */
 int  vrt_scene_memory(const vrt_scene* sc, uint64_t* bytes);

@@ -50,6 +50,10 @@ BUDGET = {
     "k_edit_pass_ldsENS_9EditPassLE": ("scene edit: clearance passes y and z on LDS", 64, 96, 0),
     "k_edit_open_scanENS_8EditOpenEi": ("scene edit: open-cell scans along y and z within Q_o", 64, 96, 0),
     "k_edit_open_xENS_8EditOpenE": ("scene edit: open-cell scan along x and the bytes of Q_o", 64, 96, 0),
+    "k_bedit_classifyENS_9BrickEditE": ("brick-scene edit: which bricks of T are occupied after the edit", 64, 96, 0),
+    "k_bedit_writeENS_9BrickEditE": ("brick-scene edit: the box's ids into the pool bricks of T", 64, 96, 0),
+    "k_bedit_extractENS_11BrickCoarseE": ("brick-scene edit: the occupancy of E as a lattice of its own", 64, 96, 0),
+    "k_bedit_copyENS_11BrickCoarseE": ("brick-scene edit: R_o into the coarse fields", 64, 96, 0),
 }
 
 

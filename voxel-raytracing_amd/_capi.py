@@ -13,6 +13,7 @@ ERR_NAMES = {1: "VRT_ERR_INVALID", 2: "VRT_ERR_IO", 3: "VRT_ERR_PARSE", 4: "VRT_
              5: "VRT_ERR_NO_DEVICE", 6: "VRT_ERR_HIP", 7: "VRT_ERR_UNSUPPORTED"}
 
 STATE_VOX, STATE_DF, STATE_OCC1, STATE_OCC2, STATE_OCC3, STATE_CELLS = 0, 1, 2, 3, 4, 5     # vrt_debug_scene_state
+STATE_BENTRY, STATE_BPOOL, STATE_BFINE = 6, 7, 8                                            # ... of a brick scene
 TRAVERSAL_AUTO, TRAVERSAL_DENSE, TRAVERSAL_BITMASK, TRAVERSAL_JUMP, TRAVERSAL_DF, TRAVERSAL_DFJ = 0, 1, 2, 3, 4, 5
 DENOISE_CANONICAL, DENOISE_AS_SHIPPED, DENOISE_FAST = 0, 1, 2       # FAST is a flag OR-ed into either
 MAX_BOUNCES = 8
@@ -82,6 +83,7 @@ SYMBOLS = {
     "vrt_scene_trim": (C.c_int, [_P, _P]),
     "vrt_scene_edit_box": (C.c_int, [_P, _P, C.POINTER(C.c_int32), C.POINTER(C.c_uint32), _P]),
     "vrt_scene_fill_box": (C.c_int, [_P, _P, C.POINTER(C.c_int32), C.POINTER(C.c_uint32), C.c_uint8]),
+    "vrt_scene_reserve_bricks": (C.c_int, [_P, _P, C.c_uint32]),
     "vrt_debug_scene_state": (C.c_int, [_P, _P, C.c_int, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
     "vrt_comm_unique_id": (C.c_int, [_P]),
     "vrt_comm_init_rank": (C.c_int, [_P, C.c_int32, C.c_int32, _P, C.POINTER(_P)]),

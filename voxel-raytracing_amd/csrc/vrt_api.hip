@@ -153,6 +153,17 @@ struct vrt_scene {
     uint32_t* bgrid = nullptr; uint8_t* bcoarse = nullptr; uint8_t* bpool = nullptr; uint8_t* bfine = nullptr;
     uint64_t* bentry = nullptr;        // bgrid + bcoarse folded into one word per brick (what the march reads; the two are freed after the build)
     bool bricks = false;
+    uint32_t bcap = 0;                 // bricks bpool / bfine have room for
+    // editable brick scenes (vrt_scene_reserve_bricks): bgrid, bcoarse (unfolded: cap 16, bit 7 = open) and the occupancy bytes stay
+    // on the device; the host keeps the padded grid once more, the brick of every pool slot and the slots that are free
+    bool reserved = false;
+    uint8_t* bocc = nullptr;           // one byte per brick of the (unpadded) lattice
+    uint32_t n_occ = 0;                // occupied bricks
+    size_t cells_room = 0;             // entries `cells` has room for (reserved scenes)
+    std::vector<uint32_t> hgrid;       // bgrid
+    std::vector<uint32_t> slot_pc;     // pool slot -> index in the padded grid, 0xFFFFFFFF = free
+    std::vector<uint32_t> free_slots;  // a stack: the lowest slot on top
+    std::vector<uint32_t> hcells, cell_slot, cell_pos;   // the cell list, the slot behind each entry, and each slot's entry
     uint64_t bytes = 0;                // device memory held (volume structures + textures)
     // scene edits (vrt_scene_edit_box): which materials are metallic, and the passes' scratch memory (kept from edit to edit, counted
     // in `bytes`, dropped by vrt_scene_trim)
@@ -340,6 +351,7 @@ void vrt_scene_free(vrt_ctx* c, vrt_scene* s)
     if (s->bpool) hipFree(s->bpool);
     if (s->bfine) hipFree(s->bfine);
     if (s->bentry) hipFree(s->bentry);
+    if (s->bocc) hipFree(s->bocc);
     delete s;
 }
 
@@ -474,6 +486,276 @@ static int fields_for_counts(vrt_ctx* c, const vrt_scene* cs, const uint8_t** ou
     return VRT_OK;
 }
 
+// ---- editable brick scenes (vrt_scene_reserve_bricks; csrc/vrt_brick_edit.h) ------------------------------------------------
+
+namespace {
+
+const uint32_t kNoBrick = 0xFFFFFFFFu;
+const size_t kMaxCells = (size_t)4u << 20;      // above it a scene goes without a cell list (as vrt_scene_from_bricks)
+
+inline size_t round256(size_t n) { return (n + 255u) & ~(size_t)255u; }
+
+struct BrickDims { int nb[3]; size_t n, npad, cstride; };
+BrickDims brick_dims(const vrt_scene* s)
+{
+    const VolumeView& d = s->d.vol;
+    BrickDims b;
+    b.nb[0] = d.W / 8; b.nb[1] = d.H / 8; b.nb[2] = d.D / 8;
+    b.n = (size_t)b.nb[0] * b.nb[1] * b.nb[2];
+    b.npad = ((size_t)b.nb[0] + 2u) * ((size_t)b.nb[1] + 2u) * ((size_t)b.nb[2] + 2u);
+    b.cstride = (size_t)d.bcoarse_stride;
+    return b;
+}
+
+// device bytes of a reserved brick scene
+uint64_t brick_scene_bytes(const vrt_scene* s)
+{
+    const BrickDims b = brick_dims(s);
+    return b.npad * 8ull + (uint64_t)s->bcap * 512ull * 9ull + 256 * sizeof(vrt_material) + (uint64_t)s->cells_room * 4ull +
+           b.npad * 4ull + b.n + 8ull * b.cstride + s->edit_scratch_bytes;
+}
+
+hipError_t brick_scratch(vrt_scene* s, size_t need)
+{
+    if (need <= s->edit_scratch_bytes) return hipSuccess;
+    if (s->edit_scratch) { hipFree(s->edit_scratch); s->bytes -= s->edit_scratch_bytes; }
+    s->edit_scratch = nullptr; s->edit_scratch_bytes = 0;
+    const hipError_t e = hipMalloc((void**)&s->edit_scratch, need);
+    if (e != hipSuccess) { s->edit_scratch = nullptr; return e; }
+    s->edit_scratch_bytes = need; s->bytes += need;
+    return hipSuccess;
+}
+
+uint32_t brick_cell_code(uint32_t pc, int pbx, int pby)
+{
+    return (uint32_t)(pc % (uint32_t)pbx - 1u) | ((uint32_t)((pc / (uint32_t)pbx) % (uint32_t)pby - 1u) << 10) | ((uint32_t)(pc / ((uint32_t)pbx * (uint32_t)pby) - 1u) << 20);
+}
+
+void brick_cell_add(vrt_scene* s, uint32_t slot, uint32_t pc)
+{
+    s->cell_pos[slot] = (uint32_t)s->hcells.size();
+    s->hcells.push_back(brick_cell_code(pc, s->d.vol.pbx, s->d.vol.pby));
+    s->cell_slot.push_back(slot);
+}
+
+void brick_cell_remove(vrt_scene* s, uint32_t slot)
+{
+    const uint32_t pos = s->cell_pos[slot], last = (uint32_t)s->hcells.size() - 1u;
+    s->hcells[pos] = s->hcells[last]; s->cell_slot[pos] = s->cell_slot[last];
+    s->cell_pos[s->cell_slot[pos]] = pos;
+    s->hcells.pop_back(); s->cell_slot.pop_back();
+    s->cell_pos[slot] = kNoBrick;
+}
+
+// the host's cell list to the device; a scene with more than kMaxCells occupied bricks goes without until it has fewer again
+hipError_t brick_upload_cells(vrt_scene* s)
+{
+    const size_t n = s->hcells.size();
+    s->n_cells = 0; s->cells_ok = false;
+    if (n > kMaxCells || n > s->cells_room) return hipSuccess;
+    if (n) { const hipError_t e = hipMemcpy(s->cells, s->hcells.data(), n * 4, hipMemcpyHostToDevice); if (e != hipSuccess) return e; }
+    s->n_cells = (uint32_t)n; s->cells_ok = true;
+    return hipSuccess;
+}
+
+// the full build of the coarse fields, as vrt_scene_from_bricks does it, from the occupancy bytes; tmp0 / tmp1: one byte per brick
+hipError_t brick_build_coarse(vrt_ctx* c, vrt_scene* s, uint8_t* tmp0, uint8_t* tmp1, bool pack)
+{
+    const BrickDims b = brick_dims(s);
+    hipError_t e = launch_build_df(s->bocc, b.nb[0], b.nb[1], b.nb[2], s->bcoarse, b.cstride, tmp0, tmp1, c->stream, VRT_BRICK_EDIT_CAP);
+    if (e == hipSuccess && s->open_cells) e = launch_open_cells(s->bocc, b.nb[0], b.nb[1], b.nb[2], s->bcoarse, b.cstride, tmp0, tmp1, c->stream, 0x80);
+    if (e == hipSuccess && pack) e = launch_brick_pack(s->bgrid, s->bcoarse, b.cstride, b.npad, s->bentry, c->stream);
+    return e;
+}
+
+// vrt_scene_edit_box / vrt_scene_fill_box on a reserved brick scene; the caller checked the box, waited for the stream and holds the lock
+int brick_scene_edit(vrt_ctx* c, vrt_scene* s, const EditBox& box, const uint8_t* ids, uint8_t id, const std::string& name)
+{
+    const VolumeView& d = s->d.vol;
+    const BrickDims bd = brick_dims(s);
+    BrickEdit e;
+    e.nbx = bd.nb[0]; e.nby = bd.nb[1]; e.nbz = bd.nb[2]; e.pbx = d.pbx; e.pby = d.pby;
+    EditSpan f[3];
+    size_t nT = 1, nF = 1, nbox = 1;
+    for (int a = 0; a < 3; a++) {
+        e.lo[a] = box.lo[a]; e.hi[a] = box.hi[a];
+        const EditSpan t = brick_span_t(box.lo[a], box.hi[a]);
+        e.t_lo[a] = t.lo; e.t_n[a] = t.hi - t.lo;
+        f[a] = brick_span_f(t, bd.nb[a]);
+        nT *= (size_t)e.t_n[a]; nF *= (size_t)(f[a].hi - f[a].lo); nbox *= (size_t)(box.hi[a] - box.lo[a]);
+    }
+    const bool rule = brick_edit_in_place(e.nbx, e.nby, e.nbz, box.lo, box.hi);
+    // scratch: the ids | a word per brick of T from the classification | one to the write | the fine list | the coarse passes'
+    const size_t ids_room = ids ? round256(nbox) : 0, t_room = round256(nT * 4);
+    const size_t list_max = rule ? nF : ((size_t)s->n_occ + nT < (size_t)s->bcap ? (size_t)s->n_occ + nT : (size_t)s->bcap);
+    const size_t list_room = round256(list_max * 8);
+    const size_t coarse_room = rule ? bedit_coarse_scratch_bytes(e, bd.cstride, s->open_cells) : 2 * round256(bd.n);
+    HIPCHK(brick_scratch(s, ids_room + 2 * t_room + list_room + coarse_room));
+    uint8_t* ids_dev = s->edit_scratch;
+    uint32_t* after_dev = (uint32_t*)(s->edit_scratch + ids_room);
+    uint32_t* ptr_dev = (uint32_t*)(s->edit_scratch + ids_room + t_room);
+    uint2* list_dev = (uint2*)(s->edit_scratch + ids_room + 2 * t_room);
+    uint8_t* coarse_scr = s->edit_scratch + ids_room + 2 * t_room + list_room;
+    if (ids) HIPCHK(hipMemcpyAsync(ids_dev, ids, nbox, hipMemcpyHostToDevice, c->stream));
+    e.ids = ids ? ids_dev : nullptr; e.id = id;
+    // 1. classify, before anything is written: a refused edit leaves the scene as it was
+    std::vector<uint32_t> after(nT), new_ptr(nT);
+    HIPCHK(launch_bedit_classify(e, s->bgrid, s->bpool, after_dev, c->stream));
+    HIPCHK(hipMemcpyAsync(after.data(), after_dev, nT * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    auto pc_of = [&](size_t t) {
+        const int bx = e.t_lo[0] + (int)(t % (size_t)e.t_n[0]), by = e.t_lo[1] + (int)((t / (size_t)e.t_n[0]) % (size_t)e.t_n[1]);
+        const int bz = e.t_lo[2] + (int)(t / ((size_t)e.t_n[0] * e.t_n[1]));
+        return (uint32_t)((size_t)(bx + 1) + ((size_t)(by + 1) + (size_t)(bz + 1) * (size_t)e.pby) * (size_t)e.pbx);
+    };
+    size_t appear = 0, vanish = 0;
+    for (size_t t = 0; t < nT; t++) {
+        const uint32_t old = s->hgrid[pc_of(t)];
+        if (!old && after[t]) appear++;
+        if (old && !after[t]) vanish++;
+    }
+    if (appear > s->free_slots.size() + vanish)
+        return fail(VRT_ERR_UNSUPPORTED, name + ": the edit makes " + std::to_string(appear) + " empty bricks occupied and the pool has " +
+                    std::to_string(s->free_slots.size() + vanish) + " free slots; reserve more with vrt_scene_reserve_bricks");
+    if (!s->metallic_voxels) {
+        if (ids) { for (size_t i = 0; i < nbox && !s->metallic_voxels; i++) s->metallic_voxels = ids[i] != 0 && s->metal[ids[i]]; }
+        else s->metallic_voxels = id != 0 && s->metal[id];
+    }
+    // slots: the bricks that vanish give theirs back first, so an edit may move as many bricks as it likes within the reservation
+    for (size_t t = 0; t < nT; t++) {
+        const uint32_t pc = pc_of(t), old = s->hgrid[pc];
+        new_ptr[t] = old;
+        if (!old || after[t]) continue;
+        s->free_slots.push_back(old - 1u); s->slot_pc[old - 1u] = kNoBrick;
+        brick_cell_remove(s, old - 1u);
+        s->hgrid[pc] = 0u; new_ptr[t] = 0u;
+    }
+    for (size_t t = 0; t < nT && appear; t++) {
+        const uint32_t pc = pc_of(t);
+        if (s->hgrid[pc] || !after[t]) continue;
+        const uint32_t slot = s->free_slots.back();
+        s->free_slots.pop_back(); s->slot_pc[slot] = pc;
+        brick_cell_add(s, slot, pc);
+        s->hgrid[pc] = slot + 1u; new_ptr[t] = slot + 1u;
+    }
+    s->n_occ = (uint32_t)((size_t)s->n_occ + appear - vanish);
+    // 2. write
+    HIPCHK(hipMemcpy(ptr_dev, new_ptr.data(), nT * 4, hipMemcpyHostToDevice));
+    HIPCHK(launch_bedit_write(e, s->bgrid, s->bocc, s->bpool, ptr_dev, c->stream));
+    // 3. fine bytes: the occupied bricks of F -- or every occupied brick, on the full build path
+    const bool changed = appear != 0 || vanish != 0, full = changed && !rule;
+    std::vector<uint2> list;
+    if (full) {
+        for (uint32_t slot = 0; slot < s->bcap; slot++)
+            if (s->slot_pc[slot] != kNoBrick) list.push_back(make_uint2(slot, s->slot_pc[slot]));
+    } else {
+        for (int z = f[2].lo; z < f[2].hi; z++) for (int y = f[1].lo; y < f[1].hi; y++) for (int x = f[0].lo; x < f[0].hi; x++) {
+            const uint32_t pc = (uint32_t)((size_t)(x + 1) + ((size_t)(y + 1) + (size_t)(z + 1) * (size_t)e.pby) * (size_t)e.pbx);
+            if (s->hgrid[pc]) list.push_back(make_uint2(s->hgrid[pc] - 1u, pc));
+        }
+    }
+    if (list.size() > list_max) return fail(VRT_ERR_HIP, name + ": internal error (fine list)");
+    if (!list.empty()) HIPCHK(hipMemcpy(list_dev, list.data(), list.size() * 8, hipMemcpyHostToDevice));
+    HIPCHK(launch_brick_fine_list(s->bgrid, e.pbx, e.pby, list_dev, (uint32_t)list.size(), s->bpool, s->bfine, c->stream));
+    // 4. coarse fields, open bits, entries, 5. cell list: functions of the occupancy and the slots alone
+    if (changed) {
+        if (full) HIPCHK(brick_build_coarse(c, s, coarse_scr, coarse_scr + round256(bd.n), true));
+        else {
+            HIPCHK(launch_bedit_coarse(e, s->bocc, s->bcoarse, bd.cstride, coarse_scr, s->open_cells, c->stream));
+            HIPCHK(launch_brick_pack(s->bgrid, s->bcoarse, bd.cstride, bd.npad, s->bentry, c->stream));
+        }
+        HIPCHK(brick_upload_cells(s));
+    }
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return VRT_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int vrt_scene_reserve_bricks(vrt_ctx* c, vrt_scene* s, uint32_t capacity)
+{
+    if (!c || !s) return fail(VRT_ERR_INVALID, "vrt_scene_reserve_bricks: NULL argument");
+    if (!s->bricks) return fail(VRT_ERR_UNSUPPORTED, "vrt_scene_reserve_bricks: a dense scene has no brick pool (it is editable as it is)");
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    std::lock_guard<std::mutex> lock(s->lazy);
+    const uint32_t n_occ = s->reserved ? s->n_occ : s->bcap;
+    if (capacity < n_occ) return fail(VRT_ERR_INVALID, "vrt_scene_reserve_bricks: the scene has " + std::to_string(n_occ) + " occupied bricks");
+    if (capacity >= 0xFFFFFEu) return fail(VRT_ERR_INVALID, "vrt_scene_reserve_bricks: at most 2^24 - 3 bricks (the march's 24-bit brick pointer)");
+    VolumeView& d = s->d.vol;
+    const BrickDims bd = brick_dims(s);
+    if (!s->reserved) {
+        // the grid and the occupancy back out of the entries; the coarse fields built again (an entry holds them saturated at 15)
+        uint32_t* grid = nullptr; uint8_t *occ = nullptr, *coarse = nullptr, *tmp = nullptr;
+        hipError_t e = hipMalloc((void**)&grid, bd.npad * 4);
+        if (e == hipSuccess) e = hipMalloc((void**)&occ, bd.n);
+        if (e == hipSuccess) e = hipMalloc((void**)&coarse, 8 * bd.cstride);
+        if (e == hipSuccess) e = hipMalloc((void**)&tmp, 2 * round256(bd.n));
+        if (e == hipSuccess) e = hipMemsetAsync(coarse, 0, 8 * bd.cstride, c->stream);
+        if (e == hipSuccess) e = launch_brick_unpack(s->bentry, bd.nb[0], bd.nb[1], bd.nb[2], grid, occ, c->stream);
+        s->bgrid = grid; s->bocc = occ; s->bcoarse = coarse;
+        if (e == hipSuccess) e = brick_build_coarse(c, s, tmp, tmp + round256(bd.n), false);
+        std::vector<uint32_t> hgrid(bd.npad);
+        if (e == hipSuccess) e = hipMemcpyAsync(hgrid.data(), grid, bd.npad * 4, hipMemcpyDeviceToHost, c->stream);
+        const hipError_t sync = hipStreamSynchronize(c->stream);
+        if (tmp) hipFree(tmp);
+        if (e == hipSuccess) e = sync;
+        if (e != hipSuccess) {
+            if (grid) hipFree(grid);
+            if (occ) hipFree(occ);
+            if (coarse) hipFree(coarse);
+            s->bgrid = nullptr; s->bocc = nullptr; s->bcoarse = nullptr;
+            return fail(VRT_ERR_HIP, std::string("vrt_scene_reserve_bricks: ") + hipGetErrorString(e));
+        }
+        s->hgrid.swap(hgrid);
+        s->slot_pc.assign(s->bcap, kNoBrick);
+        for (size_t i = 0; i < bd.npad; i++) {
+            const uint32_t g = s->hgrid[i];
+            if (g != 0u && g != 0xFFFFFFFFu) s->slot_pc[g - 1u] = (uint32_t)i;
+        }
+        s->cell_pos.assign(s->bcap, kNoBrick);
+        s->hcells.clear(); s->cell_slot.clear(); s->free_slots.clear();
+        for (uint32_t slot = 0; slot < s->bcap; slot++) brick_cell_add(s, slot, s->slot_pc[slot]);     // the build's own order
+        s->n_occ = s->bcap;
+        s->cells_room = s->cells ? s->bcap : 0;
+        s->reserved = true;
+        s->bytes = brick_scene_bytes(s);
+    }
+    if (capacity > s->bcap) {
+        uint8_t *pool = nullptr, *fine = nullptr;
+        hipError_t e = hipMalloc((void**)&pool, (size_t)capacity * 512u);
+        if (e == hipSuccess) e = hipMalloc((void**)&fine, (size_t)capacity * 4096u);
+        if (e == hipSuccess && s->bcap) e = hipMemcpy(pool, s->bpool, (size_t)s->bcap * 512u, hipMemcpyDeviceToDevice);
+        if (e == hipSuccess && s->bcap) e = hipMemcpy(fine, s->bfine, (size_t)s->bcap * 4096u, hipMemcpyDeviceToDevice);
+        if (e != hipSuccess) {
+            if (pool) hipFree(pool);
+            if (fine) hipFree(fine);
+            return fail(VRT_ERR_HIP, std::string("vrt_scene_reserve_bricks: ") + hipGetErrorString(e));
+        }
+        hipFree(s->bpool); hipFree(s->bfine);
+        s->bpool = pool; s->bfine = fine; d.bpool = pool; d.bfine = fine;
+        std::vector<uint32_t> fresh;
+        for (uint32_t slot = capacity; slot-- > s->bcap;) fresh.push_back(slot);
+        s->free_slots.insert(s->free_slots.begin(), fresh.begin(), fresh.end());    // under the slots already free
+        s->slot_pc.resize(capacity, kNoBrick); s->cell_pos.resize(capacity, kNoBrick);
+        s->bcap = capacity;
+    }
+    const size_t room = (size_t)s->bcap < kMaxCells ? (size_t)s->bcap : kMaxCells;
+    if (room > s->cells_room) {
+        uint32_t* cells = nullptr;
+        HIPCHK(hipMalloc((void**)&cells, room * 4));
+        if (s->cells) hipFree(s->cells);
+        s->cells = cells; s->cells_room = room;
+        HIPCHK(brick_upload_cells(s));
+    }
+    s->bytes = brick_scene_bytes(s);
+    return VRT_OK;
+}
+
+} // extern "C"
+
 extern "C" {
 
 int vrt_scene_from_dense(vrt_ctx* c, const uint8_t* voxels, uint32_t W, uint32_t H, uint32_t D,
@@ -599,6 +881,7 @@ int vrt_scene_from_bricks(vrt_ctx* c, const uint32_t* grid, uint32_t nbx, uint32
     int rc = VRT_OK;
 #define SCHK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { rc = fail(VRT_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); goto bad; } } while (0)
     s->metallic_voxels = any_metallic(pool, pool_bytes, palette);
+    for (int i = 1; i < 256; i++) s->metal[i] = palette[i].metallic > 0.0f;
     SCHK(hipMalloc((void**)&s->bgrid, npad * 4));
     SCHK(hipMalloc((void**)&s->bcoarse, 8 * cstride));
     SCHK(hipMalloc((void**)&s->bpool, pool_bytes ? pool_bytes : 1));
@@ -650,6 +933,7 @@ int vrt_scene_from_bricks(vrt_ctx* c, const uint32_t* grid, uint32_t nbx, uint32
     SCHK(hipStreamSynchronize(c->stream));
     hipFree(s->bgrid); hipFree(s->bcoarse); s->bgrid = nullptr; s->bcoarse = nullptr;
     s->bytes = npad * 8ull + pool_bytes + fine_bytes + 256 * sizeof(vrt_material) + (uint64_t)n_bricks * 4;
+    s->bcap = n_bricks;
 #undef SCHK
     hipFree(grid_dev); hipFree(coord_dev); hipFree(occ); hipFree(tmp0); hipFree(tmp1);
     grid_dev = coord_dev = nullptr; occ = tmp0 = tmp1 = nullptr;
@@ -700,7 +984,7 @@ int vrt_scene_trim(vrt_ctx* c, vrt_scene* s)
 static int scene_edit(vrt_ctx* c, vrt_scene* s, const int32_t lo[3], const uint32_t size[3], const uint8_t* ids, uint8_t id, const char* who)
 {
     const std::string name(who);
-    if (s->bricks) return fail(VRT_ERR_UNSUPPORTED, name + ": brick scenes cannot be edited");
+    if (s->bricks && !s->reserved) return fail(VRT_ERR_UNSUPPORTED, name + ": a brick scene cannot be edited before vrt_scene_reserve_bricks");
     const VolumeView& d = s->d.vol;
     const int dim[3] = {d.W, d.H, d.D};
     EditBox b;
@@ -714,6 +998,7 @@ static int scene_edit(vrt_ctx* c, vrt_scene* s, const int32_t lo[3], const uint3
     HIPCHK(hipSetDevice(c->device));
     HIPCHK(hipStreamSynchronize(c->stream));
     std::lock_guard<std::mutex> lock(s->lazy);
+    if (s->bricks) return brick_scene_edit(c, s, b, ids, id, name);
     if (!s->metallic_voxels) {
         if (ids) { for (size_t i = 0; i < nbox && !s->metallic_voxels; i++) s->metallic_voxels = ids[i] != 0 && s->metal[ids[i]]; }
         else s->metallic_voxels = id != 0 && s->metal[id];
@@ -756,11 +1041,17 @@ int vrt_scene_fill_box(vrt_ctx* c, vrt_scene* s, const int32_t lo[3], const uint
 int vrt_debug_scene_state(vrt_ctx* c, const vrt_scene* s, int what, void* host, size_t capacity, size_t* bytes)
 {
     if (!c || !s || !bytes) return fail(VRT_ERR_INVALID, "vrt_debug_scene_state: NULL argument");
-    if (s->bricks) return fail(VRT_ERR_UNSUPPORTED, "vrt_debug_scene_state: dense scenes only");
     const VolumeView& d = s->d.vol;
+    const bool brick_state = what == VRT_STATE_BENTRY || what == VRT_STATE_BPOOL || what == VRT_STATE_BFINE;
+    if (s->bricks ? !(brick_state || what == VRT_STATE_CELLS) : brick_state)
+        return fail(VRT_ERR_UNSUPPORTED, s->bricks ? "vrt_debug_scene_state: a brick scene has the structures VRT_STATE_CELLS, _BENTRY, _BPOOL and _BFINE only"
+                                                   : "vrt_debug_scene_state: VRT_STATE_BENTRY, _BPOOL and _BFINE are a brick scene's");
     const void* src = nullptr;
     size_t n = 0;
     switch (what) {
+    case VRT_STATE_BENTRY: src = s->bentry; n = ((size_t)d.W / 8 + 2u) * ((size_t)d.H / 8 + 2u) * ((size_t)d.D / 8 + 2u) * 8u; break;
+    case VRT_STATE_BPOOL:  src = s->bpool;  n = (size_t)s->bcap * 512u; break;
+    case VRT_STATE_BFINE:  src = s->bfine;  n = (size_t)s->bcap * 4096u; break;
     case VRT_STATE_VOX:   src = s->vox;  n = (size_t)d.W * d.H * d.D; break;
     case VRT_STATE_DF:    src = s->df;   n = s->df_bytes; break;
     case VRT_STATE_OCC1:  src = s->occ1; n = (size_t)d.n1x * d.n1y * d.n1z * 8; break;

@@ -10,6 +10,7 @@
 #include "vrt_sky.h"
 #include "vrt_tags.h"
 #include "vrt_edit.h"
+#include "vrt_brick_edit.h"
 
 namespace vrt {
 
@@ -276,6 +277,21 @@ hipError_t launch_edit_write(uint8_t* vox, uint8_t* field8, const EditBox& b, co
 hipError_t launch_edit_pyramid(const uint8_t* vox, const EditBox& b, uint64_t* occ1, uint64_t* occ2, uint64_t* occ3, hipStream_t s);
 size_t     edit_scratch_bytes(const EditBox& b, bool open);
 hipError_t launch_edit_fields(const uint8_t* vox, const EditBox& b, uint8_t* df, size_t stride, uint8_t* scratch, bool open, hipStream_t s);
+// edits of brick scenes: the lattice, the voxel box [lo, hi) that is rewritten and the bricks T it meets
+struct BrickEdit {
+    int nbx, nby, nbz, pbx, pby;
+    int lo[3], hi[3];
+    int t_lo[3], t_n[3];
+    const uint8_t* ids;               // device; nullptr: every voxel gets `id`
+    int id;
+};
+hipError_t launch_brick_unpack(const uint64_t* entry, int nbx, int nby, int nbz, uint32_t* padded, uint8_t* occ, hipStream_t s);
+hipError_t launch_brick_fine_list(const uint32_t* padded, int pbx, int pby, const uint2* list, uint32_t n_list, const uint8_t* pool,
+                                  uint8_t* fine, hipStream_t s);
+hipError_t launch_bedit_classify(const BrickEdit& p, const uint32_t* padded, const uint8_t* pool, uint32_t* after, hipStream_t s);
+hipError_t launch_bedit_write(const BrickEdit& p, uint32_t* padded, uint8_t* occ, uint8_t* pool, const uint32_t* new_ptr, hipStream_t s);
+size_t     bedit_coarse_scratch_bytes(const BrickEdit& b, size_t cstride, bool open);
+hipError_t launch_bedit_coarse(const BrickEdit& b, const uint8_t* occ, uint8_t* coarse, size_t cstride, uint8_t* scratch, bool open, hipStream_t s);
 hipError_t launch_primary(const GeomParams& p, hipStream_t s);
 hipError_t launch_shade(const GeomParams& p, hipStream_t s);
 hipError_t launch_denoise_pass(const DenoiseParams& p, hipStream_t s);

@@ -198,12 +198,11 @@ __global__ __launch_bounds__(256) void k_brick_grid(const uint32_t* __restrict__
 // (24^3 voxels in LDS; beyond them -- and outside the volume -- counts as solid, so values reach 9..16).  Per octant the
 // three one-sided min-max passes of k_df_pass, restricted to the cells the centre brick's results depend on.
 #define VRT_FINE_CAP 16
-__global__ __launch_bounds__(256) void k_brick_fine(const uint32_t* __restrict__ padded, int pbx, int pby, const uint32_t* __restrict__ coord,
-                                                    const uint8_t* __restrict__ pool, uint8_t* __restrict__ fine)
+// b: the brick's pool index; pc: its index in the padded grid
+__device__ __forceinline__ void brick_fine_body(const uint32_t* __restrict__ padded, int pbx, int pby, const uint32_t b, const uint32_t pc,
+                                                const uint8_t* __restrict__ pool, uint8_t* __restrict__ fine)
 {
     __shared__ uint8_t A[24 * 24 * 24], B[24 * 24 * 24];
-    const uint32_t b = blockIdx.x;                             // pool index
-    const uint32_t pc = coord[b];                              // index of the brick in the padded grid
     const int cbx = (int)(pc % (uint32_t)pbx), cby = (int)((pc / (uint32_t)pbx) % (uint32_t)pby), cbz = (int)(pc / ((uint32_t)pbx * (uint32_t)pby));
     __shared__ uint32_t nb[27];                               // the 3 x 3 x 3 bricks around it: 0 empty, 0xFFFFFFFF outside the volume
     if (threadIdx.x < 27) {
@@ -270,6 +269,35 @@ __global__ __launch_bounds__(256) void k_brick_fine(const uint32_t* __restrict__
     }
 }
 
+// the build: every pool brick, its padded index from coord[]
+__global__ __launch_bounds__(256) void k_brick_fine(const uint32_t* __restrict__ padded, int pbx, int pby, const uint32_t* __restrict__ coord,
+                                                    const uint8_t* __restrict__ pool, uint8_t* __restrict__ fine)
+{
+    brick_fine_body(padded, pbx, pby, blockIdx.x, coord[blockIdx.x], pool, fine);
+}
+
+// scene edits: the listed bricks, list[i] = (pool index, padded index)
+__global__ __launch_bounds__(256) void k_brick_fine_list(const uint32_t* __restrict__ padded, int pbx, int pby, const uint2* __restrict__ list,
+                                                         const uint8_t* __restrict__ pool, uint8_t* __restrict__ fine)
+{
+    const uint2 e = list[blockIdx.x];
+    brick_fine_body(padded, pbx, pby, e.x, e.y, pool, fine);
+}
+
+// vrt_scene_reserve_bricks: the padded pointer grid and the occupancy bytes back out of the packed entries
+__global__ __launch_bounds__(256) void k_brick_unpack(const uint64_t* __restrict__ entry, int nbx, int nby, int nbz,
+                                                      uint32_t* __restrict__ padded, uint8_t* __restrict__ occ)
+{
+    const size_t pbx = (size_t)nbx + 2u, pby = (size_t)nby + 2u, npad = pbx * pby * ((size_t)nbz + 2u);
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= npad) return;
+    const int x = (int)(i % pbx) - 1, y = (int)((i / pbx) % pby) - 1, z = (int)(i / (pbx * pby)) - 1;
+    const uint32_t ptr = (uint32_t)entry[i] & 0xFFFFFFu;
+    if (x < 0 || y < 0 || z < 0 || x >= nbx || y >= nby || z >= nbz) { padded[i] = 0xFFFFFFFFu; return; }
+    padded[i] = ptr;
+    occ[(size_t)x + ((size_t)y + (size_t)z * (size_t)nby) * (size_t)nbx] = ptr != 0u ? 1 : 0;
+}
+
 // the padded pointer grid and the eight coarse fields folded into the one word per brick the march reads (brick_entry_pack)
 __global__ __launch_bounds__(256) void k_brick_pack(const uint32_t* __restrict__ padded, const uint8_t* __restrict__ coarse, size_t cstride,
                                                     size_t npad, uint64_t* __restrict__ entry)
@@ -300,6 +328,21 @@ hipError_t launch_brick_fine(const uint32_t* padded, int pbx, int pby, const uin
 {
     if (n_bricks == 0) return hipSuccess;
     hipLaunchKernelGGL(k_brick_fine, dim3(n_bricks), dim3(256), 0, s, padded, pbx, pby, coord, pool, fine);
+    return hipGetLastError();
+}
+
+hipError_t launch_brick_fine_list(const uint32_t* padded, int pbx, int pby, const uint2* list, uint32_t n_list, const uint8_t* pool,
+                                  uint8_t* fine, hipStream_t s)
+{
+    if (n_list == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_brick_fine_list, dim3(n_list), dim3(256), 0, s, padded, pbx, pby, list, pool, fine);
+    return hipGetLastError();
+}
+
+hipError_t launch_brick_unpack(const uint64_t* entry, int nbx, int nby, int nbz, uint32_t* padded, uint8_t* occ, hipStream_t s)
+{
+    const size_t npad = ((size_t)nbx + 2u) * ((size_t)nby + 2u) * ((size_t)nbz + 2u);
+    hipLaunchKernelGGL(k_brick_unpack, dim3((unsigned)((npad + 255) / 256)), dim3(256), 0, s, entry, nbx, nby, nbz, padded, occ);
     return hipGetLastError();
 }
 

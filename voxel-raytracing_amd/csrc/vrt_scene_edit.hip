@@ -199,11 +199,13 @@ struct EditOpen {
     int r_lo[3], r_hi[3];             // R_o
     int sgn[3];
     int cap;
+    int mark;                         // 0: open = the code 0 (dense scenes); else the bit beside the clearance that says open (brick lattice: 0x80)
 };
 
 __device__ __forceinline__ bool edit_open_before(const EditOpen& P, int x, int y, int z)
 {
     if (x < 0 || y < 0 || z < 0 || x >= P.W || y >= P.H || z >= P.D) return true;
+    if (P.mark) return (P.field[edit_pidx(x, y, z, P.W, P.H)] & (uint8_t)P.mark) != 0;
     return P.field[edit_pidx(x, y, z, P.W, P.H)] == 0 && P.vox[(size_t)x + ((size_t)y + (size_t)z * (size_t)P.H) * (size_t)P.W] == 0;
 }
 
@@ -249,6 +251,7 @@ __global__ __launch_bounds__(256) void k_edit_open_x(const EditOpen P)
         if (qx >= nx) continue;
         const int x = P.q_lo[0] + qx;
         uint8_t* cell = P.field + edit_pidx(x, y, z, P.W, P.H);
+        if (P.mark) { *cell = open ? (uint8_t)(*cell | (uint8_t)P.mark) : (uint8_t)(*cell & (uint8_t)~P.mark); continue; }
         if (open) { *cell = 0; continue; }
         if (yz_in_r && x >= P.r_lo[0] && x < P.r_hi[0]) continue;
         if (*cell == 0 && P.vox[(size_t)x + ((size_t)y + (size_t)z * (size_t)P.H) * (size_t)P.W] == 0)
@@ -349,11 +352,200 @@ hipError_t launch_edit_fields(const uint8_t* vox, const EditBox& b, uint8_t* df,
         for (int o = 0; o < 8; o++) {
             EditOpen P;
             P.vox = vox; P.field = df + (size_t)o * stride; P.tmp0 = scratch; P.tmp1 = scratch + p.open_bytes;
-            P.W = b.W; P.H = b.H; P.D = b.D; P.cap = cap;
+            P.W = b.W; P.H = b.H; P.D = b.D; P.cap = cap; P.mark = 0;
             for (int a = 0; a < 3; a++) {
                 const int si = (o >> a) & 1;
                 const EditSpan q = edit_span_q(b.lo[a], b.hi[a], dim[a], si ? 1 : -1);
                 P.q_lo[a] = q.lo; P.q_n[a] = q.hi - q.lo; P.r_lo[a] = p.r[a][si].lo; P.r_hi[a] = p.r[a][si].hi; P.sgn[a] = si ? 1 : -1;
+            }
+            const unsigned bx = (unsigned)((P.q_n[0] + 255) / 256);
+            hipLaunchKernelGGL(k_edit_open_scan, dim3(bx, (unsigned)P.q_n[2]), dim3(256), 0, s, P, 1);
+            hipLaunchKernelGGL(k_edit_open_scan, dim3(bx, (unsigned)P.q_n[1]), dim3(256), 0, s, P, 2);
+            const size_t lines = (size_t)P.q_n[1] * (size_t)P.q_n[2];
+            hipLaunchKernelGGL(k_edit_open_x, dim3((unsigned)((lines + 3) / 4)), dim3(256), 0, s, P);
+        }
+    }
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------
+// edits of brick scenes (vrt_scene_reserve_bricks, then vrt_scene_edit_box).  vrt_brick_edit.h has the regions (T, F, R_o, E, Q_o).
+//   k_bedit_classify  per brick of T: is it occupied once the box's part is laid over its old content?  (the host assigns slots)
+//   k_bedit_write     the box's ids into the pool bricks of T (a brick that appears starts from zeros), the padded grid and the
+//                     occupancy bytes
+//   k_brick_fine_list (vrt_scene_build.hip) the fine bytes of the occupied bricks of F
+//   only when a brick's occupancy changed:
+//   k_bedit_extract   the occupancy of E as a lattice of its own, through the build's own transform (launch_build_df, cap 16)
+//   k_bedit_copy      R_o of each octant from there into the scene's coarse fields
+//   k_edit_open_scan/_x   with mark = 0x80: the open bits of Q_o; then the entries are packed again (launch_brick_pack)
+// ---------------------------------------------------------------------------------------------
+
+static_assert(VRT_BRICK_EDIT_CAP == 16, "vrt_scene_from_bricks builds the coarse fields with cap 16");
+
+// the voxel of the box at (x, y, z), which the caller knows to be inside it
+__device__ __forceinline__ uint8_t bedit_box_id(const BrickEdit& P, int x, int y, int z)
+{
+    if (!P.ids) return (uint8_t)P.id;
+    const size_t nx = (size_t)(P.hi[0] - P.lo[0]), ny = (size_t)(P.hi[1] - P.lo[1]);
+    return P.ids[(size_t)(x - P.lo[0]) + ((size_t)(y - P.lo[1]) + (size_t)(z - P.lo[2]) * ny) * nx];
+}
+
+// one wave per brick of T; lane = (x, y) within the brick, z in a loop
+__global__ __launch_bounds__(64) void k_bedit_classify(const BrickEdit P, const uint32_t* __restrict__ padded, const uint8_t* __restrict__ pool,
+                                                       uint32_t* __restrict__ after)
+{
+    const uint32_t t = blockIdx.x;
+    const int bx = P.t_lo[0] + (int)(t % (uint32_t)P.t_n[0]), by = P.t_lo[1] + (int)((t / (uint32_t)P.t_n[0]) % (uint32_t)P.t_n[1]);
+    const int bz = P.t_lo[2] + (int)(t / ((uint32_t)P.t_n[0] * (uint32_t)P.t_n[1]));
+    const uint32_t ptr = padded[(size_t)(bx + 1) + ((size_t)(by + 1) + (size_t)(bz + 1) * (size_t)P.pby) * (size_t)P.pbx];
+    const int lx = (int)(threadIdx.x & 7u), ly = (int)(threadIdx.x >> 3);
+    const int x = bx * 8 + lx, y = by * 8 + ly;
+    const bool xy_in = x >= P.lo[0] && x < P.hi[0] && y >= P.lo[1] && y < P.hi[1];
+    bool any = false;
+    for (int lz = 0; lz < 8; lz++) {
+        const int z = bz * 8 + lz;
+        uint8_t v;
+        if (xy_in && z >= P.lo[2] && z < P.hi[2]) v = bedit_box_id(P, x, y, z);     // a brick the box covers is decided by the ids alone
+        else v = ptr ? pool[(size_t)(ptr - 1u) * 512u + (size_t)(lx + ly * 8 + lz * 64)] : (uint8_t)0;
+        any = any || v != 0;
+    }
+    const uint64_t m = __ballot(any);
+    if (threadIdx.x == 0) after[t] = m ? 1u : 0u;
+}
+
+// new_ptr[t]: the brick's grid entry after the edit (0: empty; the old entry where it stays occupied; a fresh slot + 1 where it appears)
+__global__ __launch_bounds__(64) void k_bedit_write(const BrickEdit P, uint32_t* __restrict__ padded, uint8_t* __restrict__ occ,
+                                                    uint8_t* __restrict__ pool, const uint32_t* __restrict__ new_ptr)
+{
+    const uint32_t t = blockIdx.x;
+    const int bx = P.t_lo[0] + (int)(t % (uint32_t)P.t_n[0]), by = P.t_lo[1] + (int)((t / (uint32_t)P.t_n[0]) % (uint32_t)P.t_n[1]);
+    const int bz = P.t_lo[2] + (int)(t / ((uint32_t)P.t_n[0] * (uint32_t)P.t_n[1]));
+    const size_t pc = (size_t)(bx + 1) + ((size_t)(by + 1) + (size_t)(bz + 1) * (size_t)P.pby) * (size_t)P.pbx;
+    const uint32_t old = padded[pc], np = new_ptr[t];
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        padded[pc] = np;
+        occ[(size_t)bx + ((size_t)by + (size_t)bz * (size_t)P.nby) * (size_t)P.nbx] = np ? 1 : 0;
+    }
+    if (np == 0u) return;                                      // the slot of a brick that vanished keeps what it held: nothing points to it
+    const int lx = (int)(threadIdx.x & 7u), ly = (int)(threadIdx.x >> 3);
+    const int x = bx * 8 + lx, y = by * 8 + ly;
+    const bool xy_in = x >= P.lo[0] && x < P.hi[0] && y >= P.lo[1] && y < P.hi[1];
+    uint8_t* brick = pool + (size_t)(np - 1u) * 512u;
+    for (int lz = 0; lz < 8; lz++) {
+        const int z = bz * 8 + lz;
+        if (xy_in && z >= P.lo[2] && z < P.hi[2]) brick[lx + ly * 8 + lz * 64] = bedit_box_id(P, x, y, z);
+        else if (old == 0u) brick[lx + ly * 8 + lz * 64] = 0;
+    }
+}
+
+hipError_t launch_bedit_classify(const BrickEdit& p, const uint32_t* padded, const uint8_t* pool, uint32_t* after, hipStream_t s)
+{
+    const unsigned n = (unsigned)p.t_n[0] * (unsigned)p.t_n[1] * (unsigned)p.t_n[2];
+    hipLaunchKernelGGL(k_bedit_classify, dim3(n), dim3(64), 0, s, p, padded, pool, after);
+    return hipGetLastError();
+}
+
+hipError_t launch_bedit_write(const BrickEdit& p, uint32_t* padded, uint8_t* occ, uint8_t* pool, const uint32_t* new_ptr, hipStream_t s)
+{
+    const unsigned n = (unsigned)p.t_n[0] * (unsigned)p.t_n[1] * (unsigned)p.t_n[2];
+    hipLaunchKernelGGL(k_bedit_write, dim3(n), dim3(64), 0, s, p, padded, occ, pool, new_ptr);
+    return hipGetLastError();
+}
+
+// the coarse fields after a change of occupancy
+struct BrickCoarse {
+    int nbx, nby;
+    int e_lo[3], e_n[3];              // E
+    int r_lo[8][3], r_n[8][3];        // R_o
+    size_t cstride, sstride;          // bytes between the scene's fields / the sub-lattice's
+};
+
+__global__ __launch_bounds__(256) void k_bedit_extract(const BrickCoarse P, const uint8_t* __restrict__ occ, uint8_t* __restrict__ sub)
+{
+    const size_t n = (size_t)P.e_n[0] * P.e_n[1] * P.e_n[2], i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int x = P.e_lo[0] + (int)(i % (size_t)P.e_n[0]), y = P.e_lo[1] + (int)((i / (size_t)P.e_n[0]) % (size_t)P.e_n[1]);
+    const int z = P.e_lo[2] + (int)(i / ((size_t)P.e_n[0] * P.e_n[1]));
+    sub[i] = occ[(size_t)x + ((size_t)y + (size_t)z * (size_t)P.nby) * (size_t)P.nbx];
+}
+
+// blockIdx.y: the octant.  The open bit of the bricks written is cleared; the scans of Q_o (which holds R_o) set it again
+__global__ __launch_bounds__(256) void k_bedit_copy(const BrickCoarse P, const uint8_t* __restrict__ subdf, uint8_t* __restrict__ coarse)
+{
+    const int o = (int)blockIdx.y;
+    const size_t n = (size_t)P.r_n[o][0] * P.r_n[o][1] * P.r_n[o][2], i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int x = P.r_lo[o][0] + (int)(i % (size_t)P.r_n[o][0]), y = P.r_lo[o][1] + (int)((i / (size_t)P.r_n[o][0]) % (size_t)P.r_n[o][1]);
+    const int z = P.r_lo[o][2] + (int)(i / ((size_t)P.r_n[o][0] * P.r_n[o][1]));
+    coarse[(size_t)o * P.cstride + edit_pidx(x, y, z, P.nbx, P.nby)] =
+        subdf[(size_t)o * P.sstride + edit_pidx(x - P.e_lo[0], y - P.e_lo[1], z - P.e_lo[2], P.e_n[0], P.e_n[1])];
+}
+
+namespace {
+struct BrickCoarsePlan {
+    BrickCoarse k;
+    size_t sub_bytes, tmp_bytes;      // the sub-lattice; one of the two ping-pong buffers (the transform's, then the open scans')
+    unsigned copy_blocks;
+};
+BrickCoarsePlan bedit_coarse_plan(const BrickEdit& b, size_t cstride, bool open)
+{
+    BrickCoarsePlan p;
+    const int nb[3] = {b.nbx, b.nby, b.nbz};
+    p.k.nbx = b.nbx; p.k.nby = b.nby; p.k.cstride = cstride;
+    EditSpan t[3];
+    for (int a = 0; a < 3; a++) {
+        t[a].lo = b.t_lo[a]; t[a].hi = b.t_lo[a] + b.t_n[a];
+        const EditSpan e = brick_span_e(t[a], nb[a]);
+        p.k.e_lo[a] = e.lo; p.k.e_n[a] = e.hi - e.lo;
+    }
+    size_t rmax = 0, qmax = 0;
+    for (int o = 0; o < 8; o++) {
+        size_t rn = 1, qn = 1;
+        for (int a = 0; a < 3; a++) {
+            const int sign = ((o >> a) & 1) ? 1 : -1;
+            const EditSpan r = brick_span_r(t[a], nb[a], sign), q = brick_span_q(t[a], nb[a], sign);
+            p.k.r_lo[o][a] = r.lo; p.k.r_n[o][a] = r.hi - r.lo;
+            rn *= (size_t)(r.hi - r.lo); qn *= (size_t)(q.hi - q.lo);
+        }
+        rmax = rn > rmax ? rn : rmax; qmax = qn > qmax ? qn : qmax;
+    }
+    const size_t ne = (size_t)p.k.e_n[0] * p.k.e_n[1] * p.k.e_n[2];
+    p.k.sstride = df_field_bytes(p.k.e_n[0], p.k.e_n[1], p.k.e_n[2]);
+    p.sub_bytes = (ne + 255u) & ~(size_t)255u;
+    p.tmp_bytes = ((open && qmax > ne ? qmax : ne) + 255u) & ~(size_t)255u;
+    p.copy_blocks = (unsigned)((rmax + 255) / 256);
+    return p;
+}
+} // namespace
+
+size_t bedit_coarse_scratch_bytes(const BrickEdit& b, size_t cstride, bool open)
+{
+    const BrickCoarsePlan p = bedit_coarse_plan(b, cstride, open);
+    return p.sub_bytes + 8 * p.k.sstride + 2 * p.tmp_bytes;
+}
+
+// occ: the occupancy bytes AFTER the edit; coarse: the scene's eight unfolded fields as they were before it
+hipError_t launch_bedit_coarse(const BrickEdit& b, const uint8_t* occ, uint8_t* coarse, size_t cstride, uint8_t* scratch, bool open, hipStream_t s)
+{
+    const BrickCoarsePlan p = bedit_coarse_plan(b, cstride, open);
+    uint8_t *sub = scratch, *subdf = sub + p.sub_bytes, *tmp0 = subdf + 8 * p.k.sstride, *tmp1 = tmp0 + p.tmp_bytes;
+    const size_t ne = (size_t)p.k.e_n[0] * p.k.e_n[1] * p.k.e_n[2];
+    hipLaunchKernelGGL(k_bedit_extract, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, s, p.k, occ, sub);
+    hipError_t e = launch_build_df(sub, p.k.e_n[0], p.k.e_n[1], p.k.e_n[2], subdf, p.k.sstride, tmp0, tmp1, s, VRT_BRICK_EDIT_CAP);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_bedit_copy, dim3(p.copy_blocks, 8), dim3(256), 0, s, p.k, (const uint8_t*)subdf, coarse);
+    if (open) {
+        const int nb[3] = {b.nbx, b.nby, b.nbz};
+        for (int o = 0; o < 8; o++) {
+            EditOpen P;
+            P.vox = occ; P.field = coarse + (size_t)o * cstride; P.tmp0 = tmp0; P.tmp1 = tmp1;
+            P.W = b.nbx; P.H = b.nby; P.D = b.nbz; P.cap = VRT_BRICK_EDIT_CAP; P.mark = 0x80;
+            for (int a = 0; a < 3; a++) {
+                const int si = (o >> a) & 1;
+                EditSpan t; t.lo = b.t_lo[a]; t.hi = b.t_lo[a] + b.t_n[a];
+                const EditSpan q = brick_span_q(t, nb[a], si ? 1 : -1);
+                P.q_lo[a] = q.lo; P.q_n[a] = q.hi - q.lo; P.r_lo[a] = p.k.r_lo[o][a]; P.r_hi[a] = p.k.r_lo[o][a] + p.k.r_n[o][a]; P.sgn[a] = si ? 1 : -1;
             }
             const unsigned bx = (unsigned)((P.q_n[0] + 255) / 256);
             hipLaunchKernelGGL(k_edit_open_scan, dim3(bx, (unsigned)P.q_n[2]), dim3(256), 0, s, P, 1);

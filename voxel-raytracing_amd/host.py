@@ -379,8 +379,15 @@ class VoxelScene:
         """Drop the diagnostic copy of the clearance fields a launch with count planes built (vrt_scene_trim)."""
         check(lib().vrt_scene_trim(self.engine.ctx, self._h))
 
+    def reserve_bricks(self, capacity: int) -> None:
+        """Make a brick scene editable, with room for `capacity` bricks in its pool (vrt_scene_reserve_bricks); again with a larger
+        capacity to grow.  What the scene renders does not change."""
+        if not 0 <= int(capacity) <= 0xFFFFFFFF:
+            raise ValueError("VoxelScene.reserve_bricks: capacity outside 0..2^32-1")
+        self._raise(lib().vrt_scene_reserve_bricks(self.engine.ctx, self.handle, int(capacity)))
+
     def edit(self, lo, ids: np.ndarray) -> None:
-        """Rewrite a box of a dense scene (vrt_scene_edit_box).  lo: (x, y, z) of its low corner; ids: uint8 array indexed [z, y, x]
+        """Rewrite a box of a dense scene, or of a brick scene after reserve_bricks (vrt_scene_edit_box).  lo: (x, y, z) of its low corner; ids: uint8 array indexed [z, y, x]
         like from_dense's voxels (anything else is converted the same way), whose shape is the box.  Every later launch renders as
         on a scene newly built from the edited volume."""
         v = np.ascontiguousarray(ids, dtype=np.uint8)
@@ -398,13 +405,19 @@ class VoxelScene:
                                              (C.c_uint32 * 3)(*[int(t) for t in size]), int(id)))
 
     def debug_state(self, what: int) -> np.ndarray:
-        """One of a dense scene's device structures as it lies in memory (vrt_debug_scene_state; _capi.STATE_*): uint8 for the
-        voxels and the clearance fields, uint64 for the pyramid levels, uint32 for the occupied cells."""
+        """One of a scene's device structures as it lies in memory (vrt_debug_scene_state; _capi.STATE_*): uint8 for the voxels
+        and the clearance fields, uint64 for the pyramid levels, uint32 for the occupied cells; of a brick scene uint64 for the
+        packed entries, uint8 [slots, 512] for the pool and [slots, 8, 512] for the per-voxel clearances."""
         n = C.c_size_t()
         self._raise(lib().vrt_debug_scene_state(self.engine.ctx, self.handle, int(what), None, 0, C.byref(n)))
-        dt = {_capi.STATE_OCC1: np.uint64, _capi.STATE_OCC2: np.uint64, _capi.STATE_OCC3: np.uint64, _capi.STATE_CELLS: np.uint32}.get(int(what), np.uint8)
+        dt = {_capi.STATE_OCC1: np.uint64, _capi.STATE_OCC2: np.uint64, _capi.STATE_OCC3: np.uint64, _capi.STATE_CELLS: np.uint32,
+              _capi.STATE_BENTRY: np.uint64}.get(int(what), np.uint8)
         out = np.empty(n.value // np.dtype(dt).itemsize, dtype=dt)
         self._raise(lib().vrt_debug_scene_state(self.engine.ctx, self.handle, int(what), out.ctypes.data_as(C.c_void_p), out.nbytes, C.byref(n)))
+        if int(what) == _capi.STATE_BPOOL:
+            return out.reshape(-1, 512)
+        if int(what) == _capi.STATE_BFINE:
+            return out.reshape(-1, 8, 512)
         return out
 
     def memory_bytes(self) -> int:

@@ -157,6 +157,8 @@ public:
     // Rewrite the box [lo, lo + size) (no reference analogue; vrt_scene_edit_box / vrt_scene_fill_box): ids x-fastest, 0 = empty
     void edit(const std::array<int32_t, 3>& lo, const std::array<uint32_t, 3>& size, const uint8_t* ids) { check(vrt_scene_edit_box(engine->ctx, handle, lo.data(), size.data(), ids)); }
     void fill(const std::array<int32_t, 3>& lo, const std::array<uint32_t, 3>& size, uint8_t id) { check(vrt_scene_fill_box(engine->ctx, handle, lo.data(), size.data(), id)); }
+    // A brick scene becomes editable, with room for `capacity` bricks in its pool (vrt_scene_reserve_bricks); edit / fill then work on it
+    void reserveBricks(uint32_t capacity) { check(vrt_scene_reserve_bricks(engine->ctx, handle, capacity)); }
     void setSkybox(const float* rgba, uint32_t w, uint32_t h) { check(vrt_scene_set_sky(engine->ctx, handle, rgba, w, h)); }
     void setSkybox(const std::string& path) { check(vrt_scene_set_sky_file(engine->ctx, handle, path.c_str())); }          // Texture2D(.hdr)
     void setBlueNoise(const std::string& path) { check(vrt_scene_set_blue_noise_file(engine->ctx, handle, path.c_str())); }   // Texture2D(.png)

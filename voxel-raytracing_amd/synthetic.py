@@ -277,6 +277,42 @@ def bricks_from_dense(vol: np.ndarray):
     return grid.reshape(D // 8, H // 8, W // 8), np.ascontiguousarray(b[where])
 
 
+def edit_bricks(grid: np.ndarray, pool: np.ndarray, lo, ids: np.ndarray):
+    """VoxelScene.edit(lo, ids) on the (grid, pool) of vrt_scene_from_bricks, in numpy: lo = (x, y, z), ids indexed [z, y, x].
+    Returns the new pair: a brick that becomes all zero leaves the grid and the pool, one that appears is appended."""
+    d, h, w = ids.shape
+    grid = grid.copy()
+    pool = pool.copy()
+    added, removed = [], []
+    for bz in range(lo[2] >> 3, ((lo[2] + d - 1) >> 3) + 1):
+        for by in range(lo[1] >> 3, ((lo[1] + h - 1) >> 3) + 1):
+            for bx in range(lo[0] >> 3, ((lo[0] + w - 1) >> 3) + 1):
+                g = int(grid[bz, by, bx])
+                b = pool[g - 1].copy() if g else np.zeros((8, 8, 8), np.uint8)
+                z0, y0, x0 = max(lo[2], bz * 8), max(lo[1], by * 8), max(lo[0], bx * 8)
+                z1, y1, x1 = min(lo[2] + d, bz * 8 + 8), min(lo[1] + h, by * 8 + 8), min(lo[0] + w, bx * 8 + 8)
+                b[z0 - bz * 8:z1 - bz * 8, y0 - by * 8:y1 - by * 8, x0 - bx * 8:x1 - bx * 8] = \
+                    ids[z0 - lo[2]:z1 - lo[2], y0 - lo[1]:y1 - lo[1], x0 - lo[0]:x1 - lo[0]]
+                if b.any():
+                    if g:
+                        pool[g - 1] = b
+                    else:
+                        added.append(b)
+                        grid[bz, by, bx] = pool.shape[0] + len(added)
+                elif g:
+                    removed.append(g)
+                    grid[bz, by, bx] = 0
+    if added:
+        pool = np.concatenate([pool, np.stack(added)])
+    if removed:
+        keep = np.ones(pool.shape[0], bool)
+        keep[np.asarray(removed) - 1] = False
+        remap = np.zeros(pool.shape[0] + 1, np.uint32)
+        remap[1:][keep] = np.arange(1, int(keep.sum()) + 1, dtype=np.uint32)
+        grid, pool = remap[grid], pool[keep]
+    return grid, np.ascontiguousarray(pool)
+
+
 def dense_from_bricks(grid: np.ndarray, pool: np.ndarray) -> np.ndarray:
     nbz, nby, nbx = grid.shape
     b = np.zeros((grid.size, 8, 8, 8), np.uint8)

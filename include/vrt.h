@@ -231,7 +231,8 @@ int  vrt_scene_fill_box(vrt_ctx* ctx, vrt_scene* scene, const int32_t lo[3], con
 int  vrt_scene_reserve_bricks(vrt_ctx* ctx, vrt_scene* scene, uint32_t capacity_bricks);
 /* Diagnostics (tests): copy one of a scene's device structures to the host, as it lies in memory.  host == NULL only
  * reports *bytes; a capacity below that is VRT_ERR_INVALID.  VRT_STATE_DF is the whole allocation of the clearance fields: eight
- * zero-bordered fields, and where the layout has them the ninth with the voxel ids and the 0xFF byte behind it.  Selectors 0 - 4
+ * zero-bordered fields, and where the layout has them the ninth with the voxel ids and the 0xFF byte behind it; VRT_STATE_OCC2 and _OCC3 include the zero word that pads an odd count of
+ * words to an even one.  Selectors 0 - 4
  * are a dense scene's, 6 - 8 a brick scene's (the other kind: VRT_ERR_UNSUPPORTED), the cell list either's.  Waits for the
  * context's stream. */
 #define VRT_STATE_VOX   0

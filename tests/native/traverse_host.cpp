@@ -185,6 +185,13 @@ void* thb_create(const uint8_t* vox, int W, int H, int D)                // dime
 
 void thb_destroy(void* p) { delete (HostBricks*)p; }
 
+// the builder's clearance on its own (tests/test_scene_reference_cpu.py holds it against the definition in numpy)
+void thb_octant_clearance(const uint8_t* solid, int W, int H, int D, int o, int cap, uint8_t* out)
+{
+    const std::vector<uint8_t> c = octant_clearance(std::vector<uint8_t>(solid, solid + (size_t)W * H * D), W, H, D, o, cap);
+    memcpy(out, c.data(), c.size());
+}
+
 // same output record as th_trace; anyhit != 0: the any-hit form (only material and fetches are defined)
 void thb_trace(void* p, int n, const float* starts, const float* dirs, uint32_t maxSteps, int anyhit, uint32_t* out, uint64_t* lookups)
 {

@@ -1055,8 +1055,8 @@ int vrt_debug_scene_state(vrt_ctx* c, const vrt_scene* s, int what, void* host, 
     case VRT_STATE_VOX:   src = s->vox;  n = (size_t)d.W * d.H * d.D; break;
     case VRT_STATE_DF:    src = s->df;   n = s->df_bytes; break;
     case VRT_STATE_OCC1:  src = s->occ1; n = (size_t)d.n1x * d.n1y * d.n1z * 8; break;
-    case VRT_STATE_OCC2:  src = s->occ2; n = (size_t)d.n2x * d.n2y * d.n2z * 8; break;
-    case VRT_STATE_OCC3:  src = s->occ3; n = (size_t)d.n3x * d.n3y * d.n3z * 8; break;
+    case VRT_STATE_OCC2:  src = s->occ2; n = s->occ2_bytes; break;      // with the zero word that pads it to 16-byte multiples
+    case VRT_STATE_OCC3:  src = s->occ3; n = s->occ3_bytes; break;
     case VRT_STATE_CELLS: src = s->cells; n = (size_t)s->n_cells * 4; break;
     default: return fail(VRT_ERR_INVALID, "vrt_debug_scene_state: unknown structure");
     }

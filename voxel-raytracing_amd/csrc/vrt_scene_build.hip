@@ -68,7 +68,8 @@ hipError_t launch_build_pyramid(const uint8_t* vox, int W, int H, int D, uint64_
 
 // ---------------------------------------------------------------------------------------------
 // clearance fields (scene build).  For octant o = (sx, sy, sz) in {-1,+1}^3, c_o(p) = side of the largest empty
-// cube with corner p extending towards (sx, sy, sz), 0 for a solid voxel, capped at 63:
+// cube with corner p extending towards (sx, sy, sz), 0 for a solid voxel, capped at `cap` (VRT_DF_CAP = 127 for
+// the voxel fields, 16 for the bricks' coarse fields):
 //   c(p) = min_{c>=0} max(c, min_{b>=0} max(b, min_{a>=0} max(a, solid(p + (a sx, b sy, c sz)) ? 0 : INF)))
 // i.e. three one-sided 1-D min-max passes.  Outside the volume counts as solid, so a run never carries a ray more
 // than one voxel past a wall.

@@ -160,6 +160,7 @@ int  vrt_ctx_synchronize(vrt_ctx* ctx);                     /* device.waitIdle()
  *                                     with offsets 2 .. 5 compute every weight once, k_denoise_pair; 0: k_denoise_ver), "denoise_p0" (1: pass 0 through k_denoise_p0), "denoise_pair_wgs" (0; experiments: workgroups of a
  *                                     k_denoise_pair launch), "denoise_th16" (0: the tolerance kernel's 64 x 16 tiles
  *                                     are an experiment), and the tests' handles on the verified pass "denoise_guard_div8" (0), "denoise_count" (0)
+ *   vrt_trace_rays / vrt_occluded_rays / vrt_pick_pixels:  "thresh_runs" (1) and nothing else
  *   scene creation:                   "open_cells" (1), "df_prefetch" (1), "df_own" (1)
  * The environment seeds them ONCE, at vrt_ctx_create (VRT_TILE_TAGS=0, VRT_SKY_FAST=0, ...); nothing on the render path calls
  * getenv.  Values are non-negative integers (the switches: 0 / 1; a negative value is stored as 0).  Unknown name: VRT_ERR_INVALID. */
@@ -305,6 +306,50 @@ int  vrt_render_geometry_batch(vrt_ctx* ctx, const vrt_scene* sc, int32_t n, con
  * evenly over the ranks still cost every rank the same per step -- in one launch.  No reference analogue. */
 int  vrt_render_geometry_slots(vrt_ctx* ctx, const vrt_scene* sc, int32_t n, const vrt_push* pushes,
                                const vrt_settings* settings, const vrt_frame* frames, const vrt_shard* shards);
+
+/* ---- ray queries (no reference analogue as an interface; the rays are traceRay's) ----------------------------- */
+/* Trace rays the caller supplies, or the primary rays of single pixels, through a scene: which voxel a ray meets first
+ * (traceRay, voxel_volume.frag:176-196 over traceRayInt, :127-174), or only whether it meets one (traceRayHit, :198-202).
+ * Output planes of a batch of n rays: DEVICE pointers, any may be NULL (not written), at least one non-NULL; pos and voxel
+ * 4-byte aligned.  A miss -- the ray leaves the volume or exhausts max_steps -- is 0 in every plane. */
+typedef struct vrt_ray_hits {
+    uint8_t* material;  /* n:  voxel id at the hit, 0 = miss (traceRay, voxel_volume.frag:176-196)                          */
+    float*   pos;       /* 3n: RayHit.pos (frag:187-189), bit for bit what the position plane holds for a primary ray       */
+    int32_t* voxel;     /* 3n: grid cell of the hit (mapPos, frag:135,168); (0,0,0) on a miss, like the hit_voxel plane     */
+    int8_t*  normal;    /* 3n: -mask * rayStep (frag:190) before normalisation, each component in {-1,0,1}                  */
+} vrt_ray_hits;
+/* origins, dirs: DEVICE pointers to n x 3 packed floats in volume coordinates (voxel units, the volume is [0,W]x[0,H]x[0,D]).
+ * The direction is used as given -- traceRay does not normalise, and the +0.1 of boxIntersection (frag:122) is in units of
+ * it.  max_steps has MAX_RAY_STEPS' meaning (frag:68,151).  There is no per-ray distance limit: the reference has none.
+ * Rays are traced in the order given, one per lane, 64 consecutive rays per wave: neighbouring rays that walk neighbouring
+ * cells cost least (tools/exp_query.py measures the price of an order that does not).
+ * Asynchronous on the context's stream; n == 0 is VRT_OK and launches nothing.  A scene may be queried between edits under
+ * the rule of rendering: a query enqueued before vrt_scene_edit_box sees the old volume, a later one the new.
+ * n < 0, n > 2^28 (268 435 456: the kernel indexes the dwords of a plane, three per ray, and their byte offsets in 32
+ * bits -- split a larger batch), a NULL argument, no output plane, max_steps == 0: VRT_ERR_INVALID, before any device work.
+ * For every ray with finite origin and direction the planes equal the reference's traceRay of the same volume, pos by bit
+ * pattern, zero direction components included -- with one case left open: a zero direction component whose origin component
+ * is exactly 0 or exactly the volume's size on that axis.  boxIntersection multiplies 0 by infinity there (frag:113-114);
+ * this library's fminf / fmaxf drop the NaN, the axis' slab becomes empty (entry at +inf or exit at -inf), the box test
+ * fails, and the ray is marched from its origin's own cell without boxIntersection's advance: a miss at once where that cell
+ * lies outside the volume (origin component == size), else a march from the origin.  Never a fault, but pinned by nothing.
+ * Traversal is what VRT_TRAVERSAL_AUTO resolves to: the hand-written look-up loop on dense scenes whose fields it can
+ * address in 32 bits (for max_steps <= 1024, the budgets its position recovery is exact for; above, VRT_TRAVERSAL_DF),
+ * VRT_TRAVERSAL_DF with 64-bit offsets on larger volumes, the brick march on brick scenes.  Of the context options only
+ * "thresh_runs" is looked at. */
+int  vrt_trace_rays(vrt_ctx* ctx, const vrt_scene* scene, int64_t n, const float* origins, const float* dirs,
+                    uint32_t max_steps, const vrt_ray_hits* out);
+/* traceRayHit (frag:198-202): occluded[i] = 1 if ray i meets a voxel within max_steps, else 0 -- material != 0 of
+ * vrt_trace_rays, for less work (a ray whose clearance covers the rest of its budget is decided where it stands). */
+int  vrt_occluded_rays(vrt_ctx* ctx, const vrt_scene* scene, int64_t n, const float* origins, const float* dirs,
+                       uint32_t max_steps, uint8_t* occluded);
+/* The primary rays of n pixels: xy is a DEVICE pointer to n x (x, y), and ray i is the one main() generates for that pixel
+ * under `push` (frag:312-322, jitter included) -- by the device function the geometry stage itself uses, so record i equals
+ * what a frame rendered with that push and max_steps holds at the pixel in hit_id, position, hit_voxel and hit_mask / the
+ * sign of normal8.  A pixel outside push->screen_size is a miss, not an error.  push->volume_bounds must equal the scene's
+ * dimensions and screen_size be within vrt_render_geometry's limits (else VRT_ERR_INVALID). */
+int  vrt_pick_pixels(vrt_ctx* ctx, const vrt_scene* scene, const vrt_push* push, uint32_t max_steps,
+                     int64_t n, const int32_t* xy, const vrt_ray_hits* out);
 
 /* ---- denoiser stage -------------------------------------------------------------------------- */
 #define VRT_DENOISE_CANONICAL  0  /* the intended 9-tap a-trous filter                               */

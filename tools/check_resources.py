@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Register budget of the hand-scheduled kernels (csrc: the parts of vrt_device.hip, vrt_denoise.hip, vrt_scene_edit.hip), checked
+"""Register budget of the hand-scheduled kernels (csrc: the parts of vrt_device.hip, vrt_denoise.hip, vrt_scene_edit.hip, vrt_query.hip), checked
 at build time.
 
 K1's look-up loop pins physical registers and the kernel sits at two occupancy cliffs that the compiler's own remark does
@@ -54,11 +54,22 @@ BUDGET = {
     "k_bedit_writeENS_9BrickEditE": ("brick-scene edit: the box's ids into the pool bricks of T", 64, 96, 0),
     "k_bedit_extractENS_11BrickCoarseE": ("brick-scene edit: the occupancy of E as a lattice of its own", 64, 96, 0),
     "k_bedit_copyENS_11BrickCoarseE": ("brick-scene edit: R_o into the coarse fields", 64, 96, 0),
+    # ray queries (vrt_query.hip): k_query<TRAV, ANYHIT, PICK>; none may spill.  The closest-hit form over the look-up loop keeps the
+    # ray's direction and first mapPos across the march for the hit record: seven waves per SIMD, the others eight
+    "k_queryILi7ELb0ELb0EE": ("ray query, closest hit, look-up loop", 72, 80, 0),
+    "k_queryILi7ELb1ELb0EE": ("ray query, any hit, look-up loop", 64, 80, 0),
+    "k_queryILi7ELb0ELb1EE": ("pixel pick, look-up loop", 64, 80, 0),
+    "k_queryILi4ELb0ELb0EE": ("ray query, closest hit, DF (volumes past the 32-bit field layout)", 64, 80, 0),
+    "k_queryILi4ELb1ELb0EE": ("ray query, any hit, DF", 64, 80, 0),
+    "k_queryILi4ELb0ELb1EE": ("pixel pick, DF", 64, 80, 0),
+    "k_queryILi6ELb0ELb0EE": ("ray query, closest hit, brick march", 64, 80, 0),
+    "k_queryILi6ELb1ELb0EE": ("ray query, any hit, brick march", 64, 80, 0),
+    "k_queryILi6ELb0ELb1EE": ("pixel pick, brick march", 64, 80, 0),
 }
 
 
 # the objects that hold budgeted kernels, as the Makefile builds them: (source, extra flags); slowest first
-OBJECTS = [("vrt_device.hip", ["-DVRT_K1_PART=%d" % n]) for n in (3, 0, 1, 2)] + [("vrt_denoise.hip", []), ("vrt_scene_edit.hip", [])]
+OBJECTS = [("vrt_device.hip", ["-DVRT_K1_PART=%d" % n]) for n in (3, 0, 1, 2)] + [("vrt_denoise.hip", []), ("vrt_scene_edit.hip", []), ("vrt_query.hip", [])]
 
 
 def remarks(obj):

@@ -59,6 +59,13 @@ class DenoiserSettings(C.Structure):
                 ("phi_pos0", C.c_float), ("step_width", C.c_float), ("mode", C.c_int32)]
 
 
+class RayHits(C.Structure):
+    """vrt_ray_hits: the output planes of a ray query, device pointers, None = not written."""
+    _fields_ = [("material", C.c_void_p), ("pos", C.c_void_p), ("voxel", C.c_void_p), ("normal", C.c_void_p)]
+
+
+MAX_QUERY_RAYS = 1 << 28       # rays per vrt_trace_rays / vrt_occluded_rays / vrt_pick_pixels call
+
 assert C.sizeof(Push) == 96 and C.sizeof(Material) == 32
 
 # every symbol include/vrt.h declares: name -> (restype, argtypes)
@@ -110,6 +117,9 @@ SYMBOLS = {
     "vrt_render_geometry": (C.c_int, [_P, _P, C.POINTER(Push), C.POINTER(Settings), C.POINTER(Frame), C.POINTER(Shard)]),
     "vrt_render_geometry_batch": (C.c_int, [_P, _P, C.c_int32, C.POINTER(Push), C.POINTER(Settings), C.POINTER(Frame), C.POINTER(Shard)]),
     "vrt_render_geometry_slots": (C.c_int, [_P, _P, C.c_int32, C.POINTER(Push), C.POINTER(Settings), C.POINTER(Frame), C.POINTER(Shard)]),
+    "vrt_trace_rays": (C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_uint32, C.POINTER(RayHits)]),
+    "vrt_occluded_rays": (C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_uint32, _P]),
+    "vrt_pick_pixels": (C.c_int, [_P, _P, C.POINTER(Push), C.c_uint32, C.c_int64, _P, C.POINTER(RayHits)]),
     "vrt_denoiser_settings_default": (None, [C.POINTER(DenoiserSettings)]),
     "vrt_denoise": (C.c_int, [_P, C.c_int32, C.c_int32, C.POINTER(DenoiserSettings), _P, _P, _P, _P, _P,
                               C.POINTER(Shard), C.POINTER(_P)]),

@@ -25,6 +25,45 @@ __device__ __forceinline__ float decode_snorm8(int32_t c)
     return fmaxf(__builtin_fmaf(__builtin_fmaf(-127.0f, q0, cf), r, q0), -1.0f);
 }
 
+// primary_dir with fewer instructions (K1; an IEEE division expands to ~11 VALU instructions, and ray generation has five):
+//  * the two screen divisions by the 3-instruction sequence of screen_div_fast when the host found it exact for every
+//    pixel centre of this screen size (P.fast_screen_div);
+//  * normalize: the three divisions by the length share the reciprocal.  The instructions are those of the compiler's
+//    expansion of x / l without v_div_scale / v_div_fixup, which do nothing when numerator and denominator are normal
+//    numbers whose exponents differ by less than 96 and whose quotient is normal: guaranteed here for a whole wave by
+//    2^-40 <= min |component| and length <= 2^40 (a component never exceeds the length by more than rounding).  Any other
+//    wave -- zero components, huge or tiny camera vectors, NaN -- takes normalize3.
+__device__ __forceinline__ f3 primary_v(const RayGenConsts& g, float crx, float cry, float crz, float rcp_w, float rcp_h,
+                                        int fast_screen_div, int px, int py)
+{
+    float fx = (float)px + 0.5f, fy = (float)py + 0.5f;
+    float qx, qy;
+    if (fast_screen_div) { qx = screen_div_fast(fx, g.W, rcp_w); qy = screen_div_fast(fy, g.H, rcp_h); }
+    else                 { qx = fx / g.W; qy = fy / g.H; }
+    float sx = qx * 2.0f - 1.0f;
+    float sy = qy * 2.0f - 1.0f;
+    float vx = ((g.cd.x + sx * crx) + sy * g.planeV.x) + g.jx;
+    float vy = ((g.cd.y + sx * cry) + sy * g.planeV.y) + g.jy;
+    float vz = ((g.cd.z + sx * crz) + sy * g.planeV.z) + 0.0f;
+    return mk3(vx, vy, vz);
+}
+// ... and its normalize()
+__device__ __forceinline__ f3 primary_normalize(const f3 v)
+{
+    const float vx = v.x, vy = v.y, vz = v.z;
+    const float l = len3(v);
+    const float lo = __builtin_fminf(__builtin_fminf(__builtin_fabsf(vx), __builtin_fabsf(vy)), __builtin_fabsf(vz));
+    const bool tame = lo >= 0x1p-40f && l <= 0x1p40f;
+    if (__ballot(!tame) != 0ull) return normalize3(v);
+    const float r0 = __builtin_amdgcn_rcpf(l);
+    const float r = __builtin_fmaf(__builtin_fmaf(-l, r0, 1.0f), r0, r0);
+    f3 o;
+    { float q = vx * r; q = __builtin_fmaf(__builtin_fmaf(-l, q, vx), r, q); o.x = __builtin_fmaf(__builtin_fmaf(-l, q, vx), r, q); }
+    { float q = vy * r; q = __builtin_fmaf(__builtin_fmaf(-l, q, vy), r, q); o.y = __builtin_fmaf(__builtin_fmaf(-l, q, vy), r, q); }
+    { float q = vz * r; q = __builtin_fmaf(__builtin_fmaf(-l, q, vz), r, q); o.z = __builtin_fmaf(__builtin_fmaf(-l, q, vz), r, q); }
+    return o;
+}
+
 // Row mapping shared by the denoiser and the strip copy kernels: local row index -> frame row.
 __device__ __forceinline__ int strip_row(const ShardMap& sh, int extend, int r, int H)
 {

@@ -254,6 +254,25 @@ struct BlitParams {
     int32_t sw, sh, tw, th;
 };
 
+// A ray query (vrt_query.hip): n rays from two planes of 3n floats, or (pick) the primary rays of n pixels of the push block's
+// camera; planes of the record that are NULL are not written.  vol: the scene's view with the launch's march variants set.
+struct QueryParams {
+    VolumeView     vol;
+    const float*   origins;   // 3n (device); pick: unused
+    const float*   dirs;
+    const int32_t* xy;        // pick: 2n
+    uint8_t*       material;  // n (any-hit: the occluded plane)
+    float*         pos;       // 3n
+    int32_t*       voxel;     // 3n
+    int8_t*        normal;    // 3n
+    uint32_t       n, max_steps;
+    // pick: the pixel-independent part of main()'s ray generation, as K1 gets it (FrameSlot, GeomParams)
+    RayGenConsts   rg;
+    float          cam_right[3], cam_pos[3];
+    float          rcp_w, rcp_h;
+    int32_t        fast_screen_div, W, H;
+};
+
 // launchers: scene build (vrt_scene_build.hip), scene edits (vrt_scene_edit.hip), render (vrt_device.hip: sky, tile tags, hit
 // colours, K1, K2), K3 (vrt_denoise.hip), rows / blit / accumulate / resolve (vrt_post.hip)
 hipError_t launch_build_pyramid(const uint8_t* vox, int W, int H, int D, uint64_t* occ1, uint64_t* occ2,
@@ -294,6 +313,7 @@ size_t     bedit_coarse_scratch_bytes(const BrickEdit& b, size_t cstride, bool o
 hipError_t launch_bedit_coarse(const BrickEdit& b, const uint8_t* occ, uint8_t* coarse, size_t cstride, uint8_t* scratch, bool open, hipStream_t s);
 hipError_t launch_primary(const GeomParams& p, hipStream_t s);
 hipError_t launch_shade(const GeomParams& p, hipStream_t s);
+hipError_t launch_query(const QueryParams& p, int traversal /* VRT_TRAVERSAL_DF_FAST, _DF or _BRICK */, int anyhit, int pick, hipStream_t s);
 hipError_t launch_denoise_pass(const DenoiseParams& p, hipStream_t s);
 hipError_t launch_rows(const RowsParams& p, int rows_total, hipStream_t s);
 hipError_t launch_rows_batch(const RowsBatchParams& p, int rows_total, int images, hipStream_t s);

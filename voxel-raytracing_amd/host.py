@@ -404,6 +404,90 @@ class VoxelScene:
         self._raise(lib().vrt_scene_fill_box(self.engine.ctx, self.handle, (C.c_int32 * 3)(*[int(t) for t in lo]),
                                              (C.c_uint32 * 3)(*[int(t) for t in size]), int(id)))
 
+    # ---- ray queries (vrt_trace_rays, vrt_occluded_rays, vrt_pick_pixels) ----------------------------------------------
+    RAY_PLANES = {"material": (np.uint8, 1), "pos": (np.float32, 3), "voxel": (np.int32, 3), "normal": (np.int8, 3)}
+
+    def _query_in(self, a, dtype, cols, what):
+        """A query's input as a contiguous device tensor [n, cols]: torch device tensors as they are (no copy when they
+        already are contiguous and of the dtype), anything else uploaded.  Returns (tensor, came_from_torch)."""
+        torch = _torch()
+        tdt = {np.float32: torch.float32, np.int32: torch.int32}[dtype]
+        if isinstance(a, torch.Tensor):
+            if a.device != self.engine.torch_device:
+                raise ValueError(f"{what}: tensor on {a.device}, the engine is on {self.engine.torch_device}")
+            t = a.to(tdt).contiguous()
+            came = True
+        else:
+            t = torch.from_numpy(np.ascontiguousarray(a, dtype=dtype)).to(self.engine.torch_device)
+            came = False
+        if t.ndim != 2 or t.shape[1] != cols:
+            raise ValueError(f"{what}: expected shape (n, {cols}), got {tuple(t.shape)}")
+        return t, came
+
+    def _query_out(self, n, planes):
+        torch = _torch()
+        tdt = {np.uint8: torch.uint8, np.float32: torch.float32, np.int32: torch.int32, np.int8: torch.int8}
+        planes = tuple(planes)
+        if not planes or any(p not in self.RAY_PLANES for p in planes):
+            raise ValueError(f"planes: a non-empty subset of {tuple(self.RAY_PLANES)}")
+        out = {}
+        for p in planes:
+            dt, k = self.RAY_PLANES[p]
+            out[p] = torch.empty((n,) if k == 1 else (n, k), dtype=tdt[dt], device=self.engine.torch_device)
+        hits = _capi.RayHits(**{p: C.c_void_p(t.data_ptr()) for p, t in out.items()})
+        return out, hits
+
+    def _query_result(self, out, came):
+        if came:
+            return out
+        self.engine.synchronize()          # (the context may run on a stream of its own)
+        return {k: v.cpu().numpy() for k, v in out.items()}
+
+    def trace_rays(self, origins, dirs, max_steps=512, planes=("material", "pos", "voxel", "normal")):
+        """Closest hit of n rays (vrt_trace_rays): origins, dirs (n, 3) float32 in volume coordinates, directions used as given.
+        Returns {plane: array} for the planes asked for: material uint8 (n,), 0 = miss; pos float32 (n, 3); voxel int32 (n, 3);
+        normal int8 (n, 3); a miss is 0 everywhere.  Torch device tensors go in and come out without a copy, on the engine's
+        stream and without waiting for it; numpy arrays are uploaded and the results come back as numpy."""
+        o, came_o = self._query_in(origins, np.float32, 3, "trace_rays: origins")
+        d, came_d = self._query_in(dirs, np.float32, 3, "trace_rays: dirs")
+        if o.shape[0] != d.shape[0]:
+            raise ValueError("trace_rays: origins and dirs differ in length")
+        n = int(o.shape[0])
+        out, hits = self._query_out(n, planes)
+        if n == 0:                                   # (an empty tensor has no address to hand over; the C call would launch nothing)
+            return self._query_result(out, came_o and came_d)
+        self._raise(lib().vrt_trace_rays(self.engine.ctx, self.handle, n, C.c_void_p(o.data_ptr()), C.c_void_p(d.data_ptr()),
+                                         int(max_steps), C.byref(hits)))
+        return self._query_result(out, came_o and came_d)
+
+    def occluded(self, origins, dirs, max_steps=512):
+        """Any hit (vrt_occluded_rays): uint8 (n,), 1 where the ray meets a voxel within max_steps."""
+        torch = _torch()
+        o, came_o = self._query_in(origins, np.float32, 3, "occluded: origins")
+        d, came_d = self._query_in(dirs, np.float32, 3, "occluded: dirs")
+        if o.shape[0] != d.shape[0]:
+            raise ValueError("occluded: origins and dirs differ in length")
+        n = int(o.shape[0])
+        occ = torch.empty((n,), dtype=torch.uint8, device=self.engine.torch_device)
+        if n == 0:
+            return self._query_result({"occluded": occ}, came_o and came_d)["occluded"]
+        self._raise(lib().vrt_occluded_rays(self.engine.ctx, self.handle, n, C.c_void_p(o.data_ptr()), C.c_void_p(d.data_ptr()),
+                                            int(max_steps), C.c_void_p(occ.data_ptr())))
+        return self._query_result({"occluded": occ}, came_o and came_d)["occluded"]
+
+    def pick(self, push, xy, max_steps=512, planes=("material", "pos", "voxel", "normal")):
+        """The voxels under n pixels (vrt_pick_pixels): xy (n, 2) int32 pixel coordinates, push the frame's push constants
+        (make_push / VoxelRenderer.push_constants).  Record i is what a frame rendered with that push holds at pixel xy[i]; a
+        pixel outside the screen is a miss.  Results as trace_rays returns them."""
+        t, came = self._query_in(xy, np.int32, 2, "pick: xy")
+        n = int(t.shape[0])
+        out, hits = self._query_out(n, planes)
+        if n == 0:
+            return self._query_result(out, came)
+        self._raise(lib().vrt_pick_pixels(self.engine.ctx, self.handle, C.byref(push), int(max_steps), n, C.c_void_p(t.data_ptr()),
+                                          C.byref(hits)))
+        return self._query_result(out, came)
+
     def debug_state(self, what: int) -> np.ndarray:
         """One of a scene's device structures as it lies in memory (vrt_debug_scene_state; _capi.STATE_*): uint8 for the voxels
         and the clearance fields, uint64 for the pyramid levels, uint32 for the occupied cells; of a brick scene uint64 for the

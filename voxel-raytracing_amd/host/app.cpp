@@ -1,5 +1,8 @@
 // app.cpp -- offline counterpart of the reference's App (source/app.cpp:8-27, run/main.cpp:3): load a scene,
 // set camera + settings, render through the C++ host mirror (voxels.hpp) and write the RGBA image.
+// --rays IN --hits OUT [--ray-steps N]: no frame; the rays of IN (raw little-endian float32, n x 6: origin then direction) are
+// traced through the loaded scene (VoxelScene::traceRays) and OUT receives per ray material (u8), pos (3 x f32), voxel (3 x i32),
+// normal (3 x i8), packed in that order: 28 bytes.
 // Errors propagate as exceptions to run(), are printed, and the process exits with EXIT_FAILURE.
 #include <cstdio>
 #include <cstdlib>
@@ -45,7 +48,7 @@ std::shared_ptr<VoxelScene> loadDense(const std::shared_ptr<Engine>& engine, con
 int run(int argc, char** argv)
 {
     try {
-        std::string vox, dense, out, raw, dumpPush, sky, noise, png;
+        std::string vox, dense, out, raw, dumpPush, sky, noise, png, rays, hits; uint32_t raySteps = 512;
         auto settings = std::make_shared<VoxelRenderSettings>();
         vec3 pos{8, 8, -50}; float yaw = 90, pitch = 0; bool havePos = false; int device = 0;
         std::vector<int> devices;                                          // --devices a,b,...: one process drives several GPUs
@@ -56,6 +59,7 @@ int run(int argc, char** argv)
             if (a == "--vox") vox = next(); else if (a == "--dense") dense = next(); else if (a == "--out") out = next();
             else if (a == "--raw") raw = next(); else if (a == "--dump-push") dumpPush = next();
             else if (a == "--sky") sky = next(); else if (a == "--noise") noise = next(); else if (a == "--png") png = next();
+            else if (a == "--rays") rays = next(); else if (a == "--hits") hits = next(); else if (a == "--ray-steps") raySteps = (uint32_t)std::stoul(next());
             else if (a == "--width") settings->targetResolution[0] = (uint32_t)std::stoul(next());
             else if (a == "--height") settings->targetResolution[1] = (uint32_t)std::stoul(next());
             else if (a == "--pos") { pos.x = std::stof(next()); pos.y = std::stof(next()); pos.z = std::stof(next()); havePos = true; }
@@ -103,6 +107,24 @@ int run(int argc, char** argv)
         else scene = std::make_shared<VoxelScene>(engine, vox.empty() ? settings->voxPath : vox);
         if (!sky.empty()) scene->setSkybox(sky);
         if (!noise.empty()) scene->setBlueNoise(noise);
+        if (!rays.empty() || !hits.empty()) {
+            if (rays.empty() || hits.empty()) throw std::runtime_error("--rays and --hits go together");
+            const std::vector<uint8_t> in = readFile(rays);
+            if (in.size() % 24) throw std::runtime_error(rays + ": not a whole number of rays (6 float32 each)");
+            const size_t n = in.size() / 24;
+            std::vector<float> o(3 * n), d(3 * n);
+            for (size_t i = 0; i < n; i++) { memcpy(&o[3 * i], &in[24 * i], 12); memcpy(&d[3 * i], &in[24 * i + 12], 12); }
+            const VoxelScene::RayHits h = scene->traceRays(o, d, raySteps);
+            std::vector<uint8_t> rec(28 * n);
+            for (size_t i = 0; i < n; i++) {
+                uint8_t* r = &rec[28 * i];
+                r[0] = h.material[i]; memcpy(r + 1, &h.pos[3 * i], 12); memcpy(r + 13, &h.voxel[3 * i], 12); memcpy(r + 25, &h.normal[3 * i], 3);
+            }
+            std::ofstream f(hits, std::ios::binary);
+            if (!f.write((const char*)rec.data(), (std::streamsize)rec.size())) throw std::runtime_error("cannot write " + hits);
+            std::printf("traced %zu rays scene %ux%ux%u\n", n, scene->width, scene->height, scene->depth);
+            return EXIT_SUCCESS;
+        }
         VoxelRenderer renderer(engine, settings, scene);
         if (!havePos) pos = {scene->width / 2.0f, scene->height / 2.0f, -0.8f * scene->depth};
         renderer.camera().position = pos; renderer.camera().yaw = yaw; renderer.camera().pitch = pitch;

@@ -163,8 +163,51 @@ public:
     void setSkybox(const std::string& path) { check(vrt_scene_set_sky_file(engine->ctx, handle, path.c_str())); }          // Texture2D(.hdr)
     void setBlueNoise(const std::string& path) { check(vrt_scene_set_blue_noise_file(engine->ctx, handle, path.c_str())); }   // Texture2D(.png)
     void setBlueNoise(const uint8_t* rgba8, uint32_t w, uint32_t h) { check(vrt_scene_set_blue_noise(engine->ctx, handle, rgba8, w, h)); }
+    // Ray queries (no reference analogue as an interface; vrt_trace_rays / vrt_occluded_rays / vrt_pick_pixels): host vectors in, host
+    // vectors out.  origins, dirs: 3 floats per ray in volume coordinates, the direction used as given; a miss is 0 in every plane.
+    struct RayHits { std::vector<uint8_t> material; std::vector<float> pos; std::vector<int32_t> voxel; std::vector<int8_t> normal; };
+    RayHits traceRays(const std::vector<float>& origins, const std::vector<float>& dirs, uint32_t maxSteps = 512)
+    {
+        if (origins.size() != dirs.size() || origins.size() % 3) throw std::runtime_error("traceRays: origins and dirs hold 3 floats per ray");
+        const size_t n = origins.size() / 3;
+        if (n == 0) return RayHits{};
+        DeviceBuffer<float> o(engine, 3 * n), d(engine, 3 * n);
+        check(vrt_memcpy_h2d(engine->ctx, o.ptr, origins.data(), 12 * n)); check(vrt_memcpy_h2d(engine->ctx, d.ptr, dirs.data(), 12 * n));
+        HitPlanes h(engine, n);
+        check(vrt_trace_rays(engine->ctx, handle, (int64_t)n, o.ptr, d.ptr, maxSteps, &h.c));
+        return h.download();
+    }
+    std::vector<uint8_t> occluded(const std::vector<float>& origins, const std::vector<float>& dirs, uint32_t maxSteps = 512)
+    {
+        if (origins.size() != dirs.size() || origins.size() % 3) throw std::runtime_error("occluded: origins and dirs hold 3 floats per ray");
+        const size_t n = origins.size() / 3;
+        if (n == 0) return {};
+        DeviceBuffer<float> o(engine, 3 * n), d(engine, 3 * n);
+        check(vrt_memcpy_h2d(engine->ctx, o.ptr, origins.data(), 12 * n)); check(vrt_memcpy_h2d(engine->ctx, d.ptr, dirs.data(), 12 * n));
+        DeviceBuffer<uint8_t> occ(engine, n);
+        check(vrt_occluded_rays(engine->ctx, handle, (int64_t)n, o.ptr, d.ptr, maxSteps, occ.ptr));
+        return occ.download();
+    }
+    // xy: (x, y) per pixel; record i is what a frame rendered with `push` holds at pixel i
+    RayHits pick(const vrt_push& push, const std::vector<int32_t>& xy, uint32_t maxSteps = 512)
+    {
+        if (xy.size() % 2) throw std::runtime_error("pick: xy holds 2 coordinates per pixel");
+        const size_t n = xy.size() / 2;
+        if (n == 0) return RayHits{};
+        DeviceBuffer<int32_t> p(engine, 2 * n);
+        check(vrt_memcpy_h2d(engine->ctx, p.ptr, xy.data(), 8 * n));
+        HitPlanes h(engine, n);
+        check(vrt_pick_pixels(engine->ctx, handle, &push, maxSteps, (int64_t)n, p.ptr, &h.c));
+        return h.download();
+    }
     vrt_scene* handle = nullptr;
 private:
+    struct HitPlanes {
+        DeviceBuffer<uint8_t> material; DeviceBuffer<float> pos; DeviceBuffer<int32_t> voxel; DeviceBuffer<int8_t> normal; vrt_ray_hits c{};
+        HitPlanes(const std::shared_ptr<Engine>& e, size_t n) : material(e, n), pos(e, 3 * n), voxel(e, 3 * n), normal(e, 3 * n)
+        { c.material = material.ptr; c.pos = pos.ptr; c.voxel = voxel.ptr; c.normal = normal.ptr; }
+        RayHits download() const { return RayHits{material.download(), pos.download(), voxel.download(), normal.download()}; }   // (vrt_memcpy_d2h waits for the stream)
+    };
     void dims() { uint32_t d[3]; check(vrt_scene_info(handle, d)); width = d[0]; height = d[1]; depth = d[2]; }
     std::shared_ptr<Engine> engine;
 };

@@ -106,7 +106,7 @@ typedef struct vrt_settings {
 typedef struct vrt_frame {
     uint8_t*  color8;        /* RGBA8_UNORM, alpha = 0                     */
     float*    depth;         /* R32F                                        */
-    float*    motion;        /* RG32F (always 0, voxel_volume.frag:333)     */
+    float*    motion;        /* RG32F (always 0, voxel_volume.frag:333; vrt_reproject fills it) */
     uint8_t*  mask8;         /* R8_UNORM: 0.9 on hit / 0                    */
     float*    position;      /* RGBA32F, w = 0                              */
     int8_t*   normal8;       /* RGBA8_SNORM, w = 0                          */
@@ -458,6 +458,49 @@ int  vrt_blit(vrt_ctx* ctx, const void* src_rgba8, int32_t src_w, int32_t src_h,
  * vrt_resolve writes the mean of `frames` accumulated frames, rounded half up: (2*sum + frames) / (2*frames). */
 int  vrt_accumulate(vrt_ctx* ctx, const void* color_rgba8, void* accum_u32, int32_t W, int32_t H, int32_t reset);
 int  vrt_resolve(vrt_ctx* ctx, const void* accum_u32, void* out_rgba8, int32_t W, int32_t H, uint32_t frames);
+
+/* ---- temporal reprojection: history under a MOVING camera (no reference analogue: voxel_volume.frag:332 is a TODO, "use inverse
+ * of camera matrix to reproject old position and calculate motion vectors", and the motion target stays 0) ------------------------
+ * vrt_accumulate sums the frames pixel by pixel, which is right only while the camera stands still.  vrt_reproject finds, for every
+ * pixel, where the surface it shows was on the previous frame's screen, fetches the history there (bilinear, four taps, weights in
+ * 1/256), drops every tap that shows another surface -- the position plane is the world-space hit point and a voxel normal one of
+ * a few codes, so the test is exact: same normal code, hit points within tol_abs + tol_rel * depth voxels of each other --
+ * blends the current colour in, and writes the motion vectors.  csrc/vrt_reproject.h is the definition, step by step in fp32 and
+ * integers; the GPU result equals it bit for bit.
+ * A history is two planes of W * H texels (vrt_history_bytes): color16, 4 x uint16 per pixel, the accumulated colour in 8.8 fixed
+ * point; surface, 4 x 32 bit per pixel, xyz = the world position the pixel shows, w = normal8.xyz | count << 24 with count in
+ * 1..255 the number of frames accumulated (a miss pixel: position 0, normal bits 0, count 1). */
+typedef struct vrt_history {
+    uint16_t* color16;      /* DEVICE, 8-byte aligned  */
+    uint32_t* surface;      /* DEVICE, 16-byte aligned */
+} vrt_history;
+typedef struct vrt_reproject_settings {
+    uint32_t max_history;   /* 1..255: frames a pixel's history counts for at most (the blend weight of a new frame is >= 1/max); default 32 */
+    float    tol_abs;       /* voxels, default 0.5 */
+    float    tol_rel;       /* voxels per unit of depth, default 4 * |cam_right| / screen width: two pixel footprints */
+} vrt_reproject_settings;
+/* The defaults; tol_rel from cur->cam_right and cur->screen_size[0].  Needs no device. */
+void vrt_reproject_settings_default(const vrt_push* cur, vrt_reproject_settings* s);
+/* Bytes of the two planes of a W x H history (either pointer may be NULL).  Needs no device. */
+int  vrt_history_bytes(int32_t W, int32_t H, size_t* color16, size_t* surface);
+/* One frame of the sequence.  cur / prev: the push blocks this frame and the previous one were rendered with (their jitter is part
+ * of the projection: motion vectors without jitter come from pushes whose camera_jitter is 0); settings NULL: the defaults.
+ * color8 (RGBA8, normally the denoised image), position (RGBA32F) and normal8 (RGBA8_SNORM, w = 0) are the current frame's planes.
+ * history_in: what the previous call wrote, NULL to start a new sequence (every pixel: count 1, resolved = colour).  history_out:
+ * other buffers -- the kernel gathers, so in and out ping-pong.  resolved8 (RGBA8: the history rounded to codes) and motion (RG32F:
+ * previous screen position minus current, in pixels, x right and y down; written for every hit whose point lies in front of the
+ * previous camera, inside its frame or not; 0 for a miss) may each be NULL.  All DEVICE pointers, W * H texels, aligned to their
+ * texel.  Asynchronous on the context's stream.  Frame-size limits of vrt_render_geometry.
+ * VRT_ERR_INVALID, before any device work: a NULL required argument, max_history outside 1..255, a negative or non-finite
+ * tolerance, a previous camera whose basis is degenerate (zero or non-finite determinant), an output that overlaps another buffer
+ * of the call, a misaligned plane.
+ * The history lives in VOLUME coordinates: it knows nothing of the scene's content.  After vrt_scene_edit_box the caller starts a
+ * new sequence, or accepts that pixels whose geometry did not move keep their old lighting until the blend forgets it.
+ * There is no vrt_shard here: reprojecting a strip needs history rows that other ranks own, which is out of scope -- sharded
+ * renderers and the multi-GPU bench keep vrt_accumulate / vrt_resolve. */
+int  vrt_reproject(vrt_ctx* ctx, int32_t W, int32_t H, const vrt_push* cur, const vrt_push* prev,
+                   const vrt_reproject_settings* settings, const uint8_t* color8, const float* position, const int8_t* normal8,
+                   const vrt_history* history_in, const vrt_history* history_out, uint8_t* resolved8, float* motion);
 
 /* Replace ffxFsr2GetJitterPhaseCount / ffxFsr2GetJitterOffset as called by UpscalerStage::update
  * (source/voxels/stages/upscaler_stage.cpp:59-70): phase count int(8 * (display_width / render_width)^2);

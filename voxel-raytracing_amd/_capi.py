@@ -64,6 +64,16 @@ class RayHits(C.Structure):
     _fields_ = [("material", C.c_void_p), ("pos", C.c_void_p), ("voxel", C.c_void_p), ("normal", C.c_void_p)]
 
 
+class History(C.Structure):
+    """vrt_history: the two planes of a reprojection history, device pointers."""
+    _fields_ = [("color16", C.c_void_p), ("surface", C.c_void_p)]
+
+
+class ReprojectSettings(C.Structure):
+    """vrt_reproject_settings; vrt_reproject_settings_default fills it from a push block."""
+    _fields_ = [("max_history", C.c_uint32), ("tol_abs", C.c_float), ("tol_rel", C.c_float)]
+
+
 MAX_QUERY_RAYS = 1 << 28       # rays per vrt_trace_rays / vrt_occluded_rays / vrt_pick_pixels call
 
 assert C.sizeof(Push) == 96 and C.sizeof(Material) == 32
@@ -139,6 +149,10 @@ SYMBOLS = {
     "vrt_blit": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32]),
     "vrt_accumulate": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32]),
     "vrt_resolve": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_uint32]),
+    "vrt_reproject_settings_default": (None, [C.POINTER(Push), C.POINTER(ReprojectSettings)]),
+    "vrt_history_bytes": (C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+    "vrt_reproject": (C.c_int, [_P, C.c_int32, C.c_int32, C.POINTER(Push), C.POINTER(Push), C.POINTER(ReprojectSettings), _P, _P, _P,
+                                C.POINTER(History), C.POINTER(History), _P, _P]),
     "vrt_jitter_phase_count": (C.c_int32, [C.c_int32, C.c_int32]),
     "vrt_jitter_offset": (C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "vrt_last_timings": (C.c_int, [_P, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]),

@@ -1879,6 +1879,74 @@ int vrt_resolve(vrt_ctx* c, const void* accum_u32, void* out_rgba8, int32_t W, i
     return VRT_OK;
 }
 
+// ---- temporal reprojection (csrc/vrt_reproject.h is the definition, vrt_reproject.hip the kernel) ----
+
+void vrt_reproject_settings_default(const vrt_push* cur, vrt_reproject_settings* s)
+{
+    if (!s) return;
+    s->max_history = 32;
+    s->tol_abs = 0.5f;
+    s->tol_rel = (cur && cur->screen_size[0] > 0) ? reproject_default_tol_rel(cur->cam_right, cur->screen_size[0]) : 0.0f;
+}
+
+int vrt_history_bytes(int32_t W, int32_t H, size_t* color16, size_t* surface)
+{
+    if (W <= 0 || H <= 0 || W > 32768 || H > 32768) return fail(VRT_ERR_INVALID, "vrt_history_bytes: bad size");
+    const size_t n = (size_t)W * (size_t)H;
+    if (color16) *color16 = n * 8;
+    if (surface) *surface = n * 16;
+    return VRT_OK;
+}
+
+int vrt_reproject(vrt_ctx* c, int32_t W, int32_t H, const vrt_push* cur, const vrt_push* prev, const vrt_reproject_settings* settings,
+                  const uint8_t* color8, const float* position, const int8_t* normal8, const vrt_history* history_in,
+                  const vrt_history* history_out, uint8_t* resolved8, float* motion)
+{
+    // every argument error is reported before the context or a device is looked at
+    if (!c || !cur || !prev || !color8 || !position || !normal8 || !history_out || !history_out->color16 || !history_out->surface ||
+        (history_in && (!history_in->color16 || !history_in->surface)))
+        return fail(VRT_ERR_INVALID, "vrt_reproject: NULL argument");
+    if (W <= 0 || H <= 0 || W > 32768 || H > 32768) return fail(VRT_ERR_INVALID, "vrt_reproject: bad frame size");
+    if ((int64_t)W * (int64_t)H >= ((int64_t)1 << 28))
+        return fail(VRT_ERR_UNSUPPORTED, "vrt_reproject: 2^28 pixels or more per frame (the limit of vrt_render_geometry)");
+    vrt_reproject_settings st;
+    if (settings) st = *settings;
+    else { st.max_history = 32; st.tol_abs = 0.5f; st.tol_rel = reproject_default_tol_rel(cur->cam_right, W); }
+    if (st.max_history < 1u || st.max_history > 255u) return fail(VRT_ERR_INVALID, "vrt_reproject: max_history must be in 1..255");
+    if (!(st.tol_abs >= 0.0f) || !(st.tol_rel >= 0.0f) || !rp_finite(st.tol_abs) || !rp_finite(st.tol_rel))
+        return fail(VRT_ERR_INVALID, "vrt_reproject: a tolerance is negative or not finite");
+    ReprojectParams p;
+    if (!reproject_consts(W, H, prev->cam_pos, prev->cam_dir, prev->cam_right, prev->cam_up, prev->camera_jitter, cur->cam_pos,
+                          st.tol_abs, st.tol_rel, st.max_history, p.k))
+        return fail(VRT_ERR_INVALID, "vrt_reproject: the previous camera's basis is degenerate (zero or non-finite determinant)");
+    const size_t n = (size_t)W * (size_t)H;
+    struct Range { const char* lo; size_t bytes; bool out; };
+    const Range rg[9] = {
+        {(const char*)color8, n * 4, false}, {(const char*)position, n * 16, false}, {(const char*)normal8, n * 4, false},
+        {history_in ? (const char*)history_in->color16 : nullptr, n * 8, false},
+        {history_in ? (const char*)history_in->surface : nullptr, n * 16, false},
+        {(const char*)history_out->color16, n * 8, true}, {(const char*)history_out->surface, n * 16, true},
+        {(const char*)resolved8, n * 4, true}, {(const char*)motion, n * 8, true}};
+    for (int a = 0; a < 9; a++)
+        for (int b = a + 1; b < 9; b++) {
+            if (!rg[a].lo || !rg[b].lo || (!rg[a].out && !rg[b].out)) continue;
+            if ((uintptr_t)rg[a].lo < (uintptr_t)rg[b].lo + rg[b].bytes && (uintptr_t)rg[b].lo < (uintptr_t)rg[a].lo + rg[a].bytes)
+                return fail(VRT_ERR_INVALID, "vrt_reproject: an output overlaps another buffer (the history is gathered: in and out must differ)");
+        }
+    if ((((uintptr_t)position | (uintptr_t)history_out->surface | (uintptr_t)(history_in ? history_in->surface : nullptr)) & 15u) != 0u ||
+        (((uintptr_t)history_out->color16 | (uintptr_t)(history_in ? history_in->color16 : nullptr) | (uintptr_t)motion) & 7u) != 0u ||
+        (((uintptr_t)color8 | (uintptr_t)normal8 | (uintptr_t)resolved8) & 3u) != 0u)
+        return fail(VRT_ERR_INVALID, "vrt_reproject: a plane is not aligned to its texel size");
+    p.color8 = (const uint32_t*)color8; p.position = (const rp_u4*)position; p.normal8 = (const uint32_t*)normal8;
+    p.hist_color = history_in ? (const rp_u2*)history_in->color16 : nullptr;
+    p.hist_surface = history_in ? (const rp_u4*)history_in->surface : nullptr;
+    p.out_color = (rp_u2*)history_out->color16; p.out_surface = (rp_u4*)history_out->surface;
+    p.resolved8 = (uint32_t*)resolved8; p.motion = motion;
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(launch_reproject(p, c->stream));
+    return VRT_OK;
+}
+
 // ffxFsr2GetJitterPhaseCount / ffxFsr2GetJitterOffset as documented in FidelityFX-FSR2's ffx_fsr2.h (the prebuilt
 // library the reference links is absent from its tree): phase count int(8 * (display/render)^2), offset
 // Halton(2,3)(index % phases + 1) - 0.5 in pixel units.  Host-only arithmetic (two floats per frame).

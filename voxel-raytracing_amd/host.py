@@ -84,6 +84,22 @@ class TraceSettings:
     splitKernels: bool = False         # K1 + K2 over the compacted hit list instead of the megakernel
 
 
+@dataclass
+class ReprojectSettings:
+    """vrt_reproject_settings: how temporal reprojection accepts and weighs history (include/vrt.h)."""
+    maxHistory: int = 32               # 1..255 frames
+    tolAbs: float = 0.5                # voxels
+    tolRel: Optional[float] = None     # voxels per unit of depth; None: two pixel footprints of the push it is used with
+
+    def to_c(self, push: _capi.Push) -> _capi.ReprojectSettings:
+        s = _capi.ReprojectSettings()
+        lib().vrt_reproject_settings_default(C.byref(push), C.byref(s))
+        s.max_history, s.tol_abs = int(self.maxHistory), float(self.tolAbs)
+        if self.tolRel is not None:
+            s.tol_rel = float(self.tolRel)
+        return s
+
+
 def _scale(scaling: FsrScaling, dim: int) -> int:      # voxel_render_settings.cpp:3-6
     return int(np.float32(np.float32(10.0) / np.float32(int(scaling))) * np.float32(dim))
 
@@ -815,10 +831,15 @@ class UpscalerStage:
     (including the `frameCount > phaseCount` wrap, which lets frameCount reach phaseCount once per cycle).  The FSR2
     dispatch of record() (:72-161, a prebuilt third-party library) is out of scope; its stand-in is an exact N-frame
     accumulation of the jittered frames followed by the bilinear upscale to targetResolution (vrt_accumulate /
-    vrt_resolve / vrt_blit)."""
+    vrt_resolve / vrt_blit), right while the camera stands still; under a moving camera record_reprojected() keeps the history
+    by temporal reprojection (vrt_reproject) instead."""
 
     def __init__(self, engine: Engine, settings: VoxelRenderSettings):
         self.engine, self._settings = engine, settings
+        self.reprojectSettings = ReprojectSettings()
+        self._hist = None              # two (color16, surface) pairs, written in turn
+        self._hist_cur = -1            # the pair the latest frame wrote; -1: no history
+        self._prev_push = None
         self.jitterX = 0.0
         self.jitterY = 0.0
         self.frameCount = 0
@@ -842,12 +863,51 @@ class UpscalerStage:
     def reset(self):
         """Drop the accumulated history (camera or scene changed)."""
         self.accumulated = 0
+        self._hist_cur = -1
+
+    def record_reprojected(self, color, gbuffer: "GeometryBuffer", push: _capi.Push):
+        """The temporal pass under a moving camera (vrt_reproject): `color` (normally the denoised image) is blended into the
+        history fetched where each pixel's surface was on the previous frame's screen -- the frame recorded before this one, with
+        the push it was given -- and the motion vectors are written into gbuffer.motion.  Two histories are written in turn;
+        reset() starts a new sequence.  Returns the resolved image at targetResolution, like record()."""
+        torch = _torch()
+        H, W = color.shape[0], color.shape[1]
+        TW, TH = self._settings.targetResolution
+        if self._hist is None or self._hist[0][0].shape[:2] != (H, W):
+            self._hist = [(torch.zeros((H, W, 4), dtype=torch.int16, device=color.device),
+                           torch.zeros((H, W, 4), dtype=torch.int32, device=color.device)) for _ in range(2)]
+            self._resolved = torch.zeros((H, W, 4), dtype=torch.uint8, device=color.device)
+            self._accum = None
+            self._hist_cur = -1
+        if self._target is None or self._target.shape[:2] != (TH, TW):
+            self._target = torch.zeros((TH, TW, 4), dtype=torch.uint8, device=color.device)
+        prev = self._prev_push if self._hist_cur >= 0 else push
+        nxt = 1 - self._hist_cur if self._hist_cur >= 0 else 0
+        hin = _capi.History(self._hist[self._hist_cur][0].data_ptr(), self._hist[self._hist_cur][1].data_ptr()) if self._hist_cur >= 0 else None
+        hout = _capi.History(self._hist[nxt][0].data_ptr(), self._hist[nxt][1].data_ptr())
+        st = self.reprojectSettings.to_c(push)
+        motion = gbuffer.planes.get("motion")
+        check(lib().vrt_reproject(self.engine.ctx, W, H, C.byref(push), C.byref(prev), C.byref(st), color.data_ptr(),
+                                  gbuffer.position.data_ptr(), gbuffer.normal.data_ptr(), C.byref(hin) if hin is not None else None,
+                                  C.byref(hout), self._resolved.data_ptr(), motion.data_ptr() if motion is not None else None))
+        self._hist_cur = nxt
+        self._prev_push = _capi.Push.from_buffer_copy(push)
+        self.accumulated += 1
+        check(lib().vrt_blit(self.engine.ctx, self._resolved.data_ptr(), W, H, self._target.data_ptr(), TW, TH))
+        return self._target
+
+    def history(self):
+        """The latest history as (color16 uint16 [H, W, 4], surface uint32 [H, W, 4]) numpy arrays, or None."""
+        if self._hist_cur < 0:
+            return None
+        c, s = self._hist[self._hist_cur]
+        return c.cpu().numpy().view(np.uint16), s.cpu().numpy().view(np.uint32)
 
     def record(self, color):
         torch = _torch()
         H, W = color.shape[0], color.shape[1]
         TW, TH = self._settings.targetResolution
-        if self._accum is None or self._accum.shape[:2] != (H, W):
+        if self._accum is None or self._accum.shape[:2] != (H, W) or self._resolved.shape[:2] != (H, W):
             self._accum = torch.zeros((H, W, 4), dtype=torch.int32, device=color.device)
             self._resolved = torch.zeros((H, W, 4), dtype=torch.uint8, device=color.device)
             self.accumulated = 0
@@ -885,10 +945,12 @@ class VoxelRenderer:
 
     temporal=False (default) keeps the frame graph at the hot path: the FSR branch of :86-87 is skipped and the
     image stays at renderResolution(); temporal=True takes that branch through the accumulation stand-in.
-    windowSize=(w, h) appends the blit of :89."""
+    windowSize=(w, h) appends the blit of :89.  reproject=True (with temporal=True) keeps the history under a moving camera:
+    the temporal pass is UpscalerStage.record_reprojected instead of the pixel-by-pixel accumulation, and gBuffer.motion holds
+    the motion vectors; reproject=False is the accumulation exactly."""
 
     def __init__(self, engine: Engine, settings: Optional[VoxelRenderSettings] = None, scene: Optional[VoxelScene] = None,
-                 noise=None, debug_planes: bool = False, temporal: bool = False, windowSize=None):
+                 noise=None, debug_planes: bool = False, temporal: bool = False, windowSize=None, reproject: bool = False):
         self.engine = engine
         self._settings = settings or VoxelRenderSettings()
         self._camera = CameraController()
@@ -898,6 +960,7 @@ class VoxelRenderer:
         self._upscalerStage = UpscalerStage(engine, self._settings)
         self._blitStage = BlitStage(engine, self._settings)
         self.temporal = bool(temporal)
+        self.reproject = bool(reproject)
         self.windowSize = windowSize
         self._time = 0.0
 
@@ -952,7 +1015,12 @@ class VoxelRenderer:
             color = gBuffer.color
         self.gBuffer = gBuffer
         if self.temporal and self._settings.fsrSetttings.enable:      # :86-87
-            color = self._upscalerStage.record(color)
+            if self.reproject:
+                if shard is not None:
+                    raise ValueError("VoxelRenderer: reprojection across strips is not supported (include/vrt.h, vrt_reproject)")
+                color = self._upscalerStage.record_reprojected(color, gBuffer, push)
+            else:
+                color = self._upscalerStage.record(color)
         if self.windowSize is not None:                               # :89
             color = self._blitStage.record(color, self.windowSize)
         return color

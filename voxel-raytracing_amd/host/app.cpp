@@ -52,7 +52,8 @@ int run(int argc, char** argv)
         auto settings = std::make_shared<VoxelRenderSettings>();
         vec3 pos{8, 8, -50}; float yaw = 90, pitch = 0; bool havePos = false; int device = 0;
         std::vector<int> devices;                                          // --devices a,b,...: one process drives several GPUs
-        int frames = 1; uint32_t windowW = 0, windowH = 0; float flyForward = 0, flyStrafe = 0, flyMouseX = 0; bool temporal = false;
+        int frames = 1; uint32_t windowW = 0, windowH = 0; float flyForward = 0, flyStrafe = 0, flyMouseX = 0; bool temporal = false, reproject = false;
+        std::string dumpPushes; std::vector<vrt_push> allPushes;
         for (int i = 1; i < argc; i++) {
             std::string a = argv[i];
             auto next = [&]() { if (i + 1 >= argc) throw std::runtime_error("missing value for " + a); return std::string(argv[++i]); };
@@ -75,6 +76,8 @@ int run(int argc, char** argv)
             else if (a == "--devices") { std::string l = next(); size_t p0 = 0; while (p0 <= l.size()) { size_t c = l.find(',', p0); if (c == std::string::npos) c = l.size(); if (c > p0) devices.push_back(std::stoi(l.substr(p0, c - p0))); p0 = c + 1; } }
             else if (a == "--frames") frames = std::max(1, std::stoi(next()));                 // frames to run (update + render each)
             else if (a == "--temporal") temporal = true;                                       // accumulate jittered frames + upscale
+            else if (a == "--reproject") reproject = true;                                     // with --temporal: keep the history under --fly (vrt_reproject)
+            else if (a == "--dump-pushes") dumpPushes = next();                                // every frame's push block, 96 bytes each
             else if (a == "--window") { windowW = (uint32_t)std::stoul(next()); windowH = (uint32_t)std::stoul(next()); }
             else if (a == "--fly") { flyForward = std::stof(next()); flyStrafe = std::stof(next()); flyMouseX = std::stof(next()); }
             else throw std::runtime_error("unknown argument " + a);
@@ -129,18 +132,20 @@ int run(int argc, char** argv)
         if (!havePos) pos = {scene->width / 2.0f, scene->height / 2.0f, -0.8f * scene->depth};
         renderer.camera().position = pos; renderer.camera().yaw = yaw; renderer.camera().pitch = pitch;
         renderer.camera().updateDirectionVectors();
-        renderer.temporal = temporal; renderer.windowW = windowW; renderer.windowH = windowH;
+        renderer.temporal = temporal; renderer.reproject = reproject; renderer.windowW = windowW; renderer.windowH = windowH;
         std::vector<uint8_t> img; uint32_t res[2] = {0, 0};
         const bool moving = flyForward != 0 || flyStrafe != 0 || flyMouseX != 0;
         for (int f = 0; f < frames; f++) {                                                     // App::run loop (source/app.cpp:18-27)
             if (frames > 1 || temporal) {
                 if (flyMouseX != 0) renderer.camera().mouse(flyMouseX, 0.0f);
                 renderer.update(1.0f / 60.0f, flyForward, flyStrafe);
-                if (moving) renderer.upscaler().reset();                                       // no reprojection: history is per pose
+                if (moving && !reproject) renderer.upscaler().reset();                         // no reprojection: history is per pose
             }
+            allPushes.push_back(renderer.pushConstants());
             img = renderer.render(&res[0], &res[1]);
         }
         if (!dumpPush.empty()) { vrt_push p = renderer.pushConstants(); std::ofstream(dumpPush, std::ios::binary).write((const char*)&p, sizeof p); }
+        if (!dumpPushes.empty()) std::ofstream(dumpPushes, std::ios::binary).write((const char*)allPushes.data(), (std::streamsize)(allPushes.size() * sizeof(vrt_push)));
         if (!raw.empty()) std::ofstream(raw, std::ios::binary).write((const char*)img.data(), (std::streamsize)img.size());
         if (!png.empty()) check(vrt_image_write_png(png.c_str(), img.data(), res[0], res[1]));
         if (!out.empty()) {

@@ -285,7 +285,8 @@ private:
 };
 
 // UpscalerStage (upscaler_stage.cpp): update() is the reference's jitter / frame sequence (:59-70); record() replaces the
-// FSR2 dispatch (:72-161, prebuilt third party, out of scope) by exact N-frame accumulation + bilinear upscale.
+// FSR2 dispatch (:72-161, prebuilt third party, out of scope) by exact N-frame accumulation + bilinear upscale (a camera at
+// rest), recordReprojected() by temporal reprojection (a moving one).
 class UpscalerStage {
 public:
     float jitterX = 0, jitterY = 0; int frameCount = 0; uint32_t accumulated = 0;
@@ -299,11 +300,39 @@ public:
         frameCount++;
         if (frameCount > jitterPhaseCount) frameCount = 0;
     }
-    void reset() { accumulated = 0; }
+    void reset() { accumulated = 0; histCur = -1; }
+    // The temporal pass under a moving camera (vrt_reproject): `color` is blended into the history fetched where each pixel's
+    // surface was on the previous frame's screen, and the motion vectors are written into g.motion.  Two histories are written in
+    // turn; reset() starts a new sequence.
+    vrt_reproject_settings reprojectSettings{0, 0.5f, -1.0f};                          // max_history 0 / tol_rel < 0: the default
+    const uint8_t* recordReprojected(const uint8_t* color, const GeometryBuffer& g, const vrt_push& push)
+    {
+        const uint32_t w = g.width, h = g.height;
+        size_t n = (size_t)w * h;
+        if (!histColor[0] || histColor[0]->count != n * 4) {
+            for (int k = 0; k < 2; k++) { histColor[k] = std::make_shared<DeviceBuffer<uint16_t>>(engine, n * 4); histSurface[k] = std::make_shared<DeviceBuffer<uint32_t>>(engine, n * 4); }
+            histCur = -1;
+        }
+        if (!resolved || resolved->count != n * 4) { resolved = std::make_shared<DeviceBuffer<uint8_t>>(engine, n * 4); accum.reset(); }
+        size_t tn = (size_t)settings->targetResolution[0] * settings->targetResolution[1] * 4;
+        if (!target || target->count != tn) target = std::make_shared<DeviceBuffer<uint8_t>>(engine, tn);
+        vrt_reproject_settings st; vrt_reproject_settings_default(&push, &st);
+        if (reprojectSettings.max_history != 0) st.max_history = reprojectSettings.max_history;
+        st.tol_abs = reprojectSettings.tol_abs;
+        if (reprojectSettings.tol_rel >= 0) st.tol_rel = reprojectSettings.tol_rel;
+        const int nxt = histCur >= 0 ? 1 - histCur : 0;
+        vrt_history in{}, out{histColor[nxt]->ptr, histSurface[nxt]->ptr};
+        if (histCur >= 0) { in.color16 = histColor[histCur]->ptr; in.surface = histSurface[histCur]->ptr; }
+        check(vrt_reproject(engine->ctx, (int32_t)w, (int32_t)h, &push, histCur >= 0 ? &prevPush : &push, &st, color, g.position->ptr, g.normal->ptr,
+                            histCur >= 0 ? &in : nullptr, &out, resolved->ptr, g.motion->ptr));
+        histCur = nxt; prevPush = push; accumulated++;
+        check(vrt_blit(engine->ctx, resolved->ptr, (int32_t)w, (int32_t)h, target->ptr, (int32_t)settings->targetResolution[0], (int32_t)settings->targetResolution[1]));
+        return target->ptr;
+    }
     const uint8_t* record(const uint8_t* color, uint32_t w, uint32_t h)
     {
         size_t n = (size_t)w * h * 4;
-        if (!accum || accum->count != n) { accum = std::make_shared<DeviceBuffer<uint32_t>>(engine, n); resolved = std::make_shared<DeviceBuffer<uint8_t>>(engine, n); accumulated = 0; }
+        if (!accum || accum->count != n || !resolved || resolved->count != n) { accum = std::make_shared<DeviceBuffer<uint32_t>>(engine, n); resolved = std::make_shared<DeviceBuffer<uint8_t>>(engine, n); accumulated = 0; }
         size_t tn = (size_t)settings->targetResolution[0] * settings->targetResolution[1] * 4;
         if (!target || target->count != tn) target = std::make_shared<DeviceBuffer<uint8_t>>(engine, tn);
         check(vrt_accumulate(engine->ctx, color, accum->ptr, (int32_t)w, (int32_t)h, accumulated == 0));
@@ -315,6 +344,7 @@ public:
 private:
     std::shared_ptr<Engine> engine; std::shared_ptr<VoxelRenderSettings> settings; float _deltaMsec = 0;
     std::shared_ptr<DeviceBuffer<uint32_t>> accum; std::shared_ptr<DeviceBuffer<uint8_t>> resolved, target;
+    std::shared_ptr<DeviceBuffer<uint16_t>> histColor[2]; std::shared_ptr<DeviceBuffer<uint32_t>> histSurface[2]; int histCur = -1; vrt_push prevPush{};
 };
 
 // BlitStage::record + shader/blit.frag (blit_stage.cpp:41-75): centre-cropped bilinear copy to a window-sized target.
@@ -358,14 +388,15 @@ public:
         return p;
     }
     // recordCommands (:55-94); returns the RGBA8 image (host copy) and its size in outW / outH.
-    // temporal: take the FSR branch (:86-87) through the accumulation stand-in; windowW/H != 0: append the blit (:89).
+    // temporal: take the FSR branch (:86-87) through the accumulation stand-in -- or, with reproject, through temporal reprojection,
+    // which keeps the history under a moving camera and fills gBuffer.motion; windowW/H != 0: append the blit (:89).
     std::vector<uint8_t> render(uint32_t* outW = nullptr, uint32_t* outH = nullptr)
     {
         vrt_push push = pushConstants();
         GeometryBuffer g = _geometryStage->record(push);
         const uint8_t* img = _settings->denoiserSettings.enable ? _denoiserStage->record(g) : g.color->ptr;
         uint32_t w = g.width, h = g.height;
-        if (temporal && _settings->fsrSetttings.enable) { img = _upscalerStage->record(img, w, h); w = _settings->targetResolution[0]; h = _settings->targetResolution[1]; }
+        if (temporal && _settings->fsrSetttings.enable) { img = reproject ? _upscalerStage->recordReprojected(img, g, push) : _upscalerStage->record(img, w, h); w = _settings->targetResolution[0]; h = _settings->targetResolution[1]; }
         if (windowW && windowH) { img = _blitStage->record(img, w, h, windowW, windowH); w = windowW; h = windowH; }
         std::vector<uint8_t> host((size_t)w * h * 4);
         check(vrt_memcpy_d2h(engine->ctx, host.data(), img, host.size()));
@@ -374,7 +405,7 @@ public:
         if (outH) *outH = h;
         return host;
     }
-    bool temporal = false; uint32_t windowW = 0, windowH = 0; GeometryBuffer gBuffer;
+    bool temporal = false, reproject = false; uint32_t windowW = 0, windowH = 0; GeometryBuffer gBuffer;
 private:
     std::shared_ptr<Engine> engine; std::shared_ptr<VoxelRenderSettings> _settings; std::shared_ptr<VoxelScene> _scene;
     std::unique_ptr<CameraController> _camera; std::unique_ptr<GeometryStage> _geometryStage; std::unique_ptr<DenoiserStage> _denoiserStage;

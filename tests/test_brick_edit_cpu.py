@@ -32,10 +32,10 @@ def test_entry_point_and_selectors(vrt):
 
 
 def test_cap_matches_the_build():
-    api = open(os.path.join(ROOT, "voxel-raytracing_amd", "csrc", "vrt_api.hip")).read()
+    api = open(os.path.join(ROOT, "voxel-raytracing_amd", "csrc", "vrt_api_scene.hip")).read()
     hdr = open(os.path.join(ROOT, "voxel-raytracing_amd", "csrc", "vrt_brick_edit.h")).read()
     assert re.search(r"#define VRT_BRICK_EDIT_CAP (\d+)", hdr).group(1) == "16"
-    assert re.search(r"launch_build_df\(occ, \(int\)nbx, \(int\)nby, \(int\)nbz, s->bcoarse, cstride, tmp0, tmp1, c->stream, 16\)", api)
+    assert re.search(r"launch_build_df\(occ, \(int\)nbx, \(int\)nby, \(int\)nbz, s->bcoarse\.get\(\), cstride, tmp0, tmp1, c->stream, VRT_BRICK_EDIT_CAP\)", api)
 
 
 @pytest.mark.parametrize("seed", [1, 2, 3])

@@ -3,6 +3,7 @@ declares, the host-only entry points work, and compute entry points fail loudly 
 import ctypes as C
 import os
 import re
+import subprocess
 
 import numpy as np
 import pytest
@@ -19,6 +20,17 @@ def test_header_symbols_exported(vrt):
     for name in sorted(declared):
         assert hasattr(lib, name), f"{name} declared in include/vrt.h but not exported"
     assert declared == set(vrt._capi.SYMBOLS), declared ^ set(vrt._capi.SYMBOLS)
+
+
+def test_exported_symbols_declared(vrt):
+    # the converse: a helper of the host files that lost its `static` (or its namespace) would show up here
+    hdr = open(os.path.join(ROOT, "include", "vrt.h")).read()
+    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
+    declared = set(re.findall(r"\b(vrt_[a-z0-9_]+)\s*\(", hdr))
+    syms = subprocess.run(["nm", "-D", "--defined-only", vrt._capi.LIB_PATH], check=True, capture_output=True, text=True).stdout
+    exported = {line.split()[-1] for line in syms.splitlines() if line.split() and line.split()[-1].startswith("vrt_")}
+    assert len(exported) >= 30
+    assert exported <= declared, sorted(exported - declared)
 
 
 def test_struct_layouts(vrt):

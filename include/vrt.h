@@ -150,6 +150,7 @@ int  vrt_ctx_synchronize(vrt_ctx* ctx);                     /* device.waitIdle()
 /* Development switches of a context (no reference analogue; the reference's counterpart is recompiling a shader): each changes
  * speed only, never a result -- the tests render "the same frame without X" with them.  Name (default), who looks at it:
  *   every vrt_render_geometry* call:  "tile_tags" (1), "box_rect" (1), "fast_loop" (1), "thresh_runs" (1), "hit_table" (1), "sky_fast" (1),
+ *                                     "sky_span" (1: the sky waves of an all-sky 32x8 span store whole rows; needs sky_fast),
  *                                     "no_bounce_kernel" (1), "ao_batch" (1: the AO rays of a wave from a pool in LDS every lane draws on),
  *                                     "packed_bounces" (1: the bounce chain as one word per hit on dense scenes; 2: on brick scenes too,
  *                                     where it measured slower; 0: the stack of hits), "tags_async" (0: the tile tags of a launch on a

@@ -24,6 +24,7 @@ static const OptName kOptNames[] = {
     {"tile_tags", "VRT_TILE_TAGS", &DevOptions::tile_tags}, {"box_rect", "VRT_BOX_RECT", &DevOptions::box_rect},
     {"xcd_regions", "VRT_XCD_REGIONS", &DevOptions::xcd_regions}, {"fast_loop", "VRT_FAST_LOOP", &DevOptions::fast_loop},
     {"no_bounce_kernel", "VRT_NO_BOUNCE_KERNEL", &DevOptions::no_bounce_kernel}, {"sky_fast", "VRT_SKY_FAST", &DevOptions::sky_fast},
+    {"sky_span", "VRT_SKY_SPAN", &DevOptions::sky_span},
     {"packed_bounces", "VRT_PACKED_BOUNCES", &DevOptions::packed_bounces}, {"ao_batch", "VRT_AO_BATCH", &DevOptions::ao_batch}, {"tags_async", "VRT_TAGS_ASYNC", &DevOptions::tags_async},
     {"hit_table", "VRT_HIT_TABLE", &DevOptions::hit_table},
     {"thresh_runs", "VRT_THRESH_RUNS", &DevOptions::thresh_runs}, {"denoise_th16", "VRT_DENOISE_TH", &DevOptions::denoise_th16}, {"denoise_packed", "VRT_DENOISE_PACKED", &DevOptions::denoise_packed},
@@ -495,7 +496,8 @@ static int launch_plan(const DevOptions& opt, const vrt_scene* s, const Launch& 
         for (int f = 0; f < n && six; f++)
             six = frames[f].color8 && frames[f].depth && frames[f].motion && frames[f].mask8 && frames[f].position && frames[f].normal8 &&
                   !frames[f].hit_id && !frames[f].color8_strips;
-        m.flags = (st->flags & 0xFFFFu) | (p.sky_fast ? VRT_MAPFLAG_SKY_FAST : 0u) | (six ? VRT_MAPFLAG_SIX : 0u); m.n_frames = p.n_frames; m.xcd_turn = p.xcd_turn;
+        m.flags = (st->flags & 0xFFFFu) | (p.sky_fast ? VRT_MAPFLAG_SKY_FAST : 0u) | (six ? VRT_MAPFLAG_SIX : 0u) |
+                  ((p.sky_fast && opt.sky_span) ? VRT_MAPFLAG_SKY_SPAN : 0u); m.n_frames = p.n_frames; m.xcd_turn = p.xcd_turn;
         m.wgs_per_frame = p.wgs_per_frame; m.wgs_per_frame_rcp = p.wgs_per_frame_rcp;
         m.tiles_x = p.tiles_x; m.tiles_x_rcp = p.tiles_x_rcp; m.tiles_y_local = p.tiles_y_local; m.tiles_y_rcp = p.tiles_y_rcp;
         m.tps = p.tps; m.tps_rcp = p.tps_rcp; m.tile = p.tile_h; m.nranks = p.sh.nranks; m.strip_rows = p.sh.strip_rows;

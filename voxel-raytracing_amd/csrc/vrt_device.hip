@@ -747,12 +747,20 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(((MODE == 4
     // (A launch without tags points at one word per frame that holds its tile_gen, with tags_x = 0 and tags_per_frame = 1.)
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const uint32_t tile_gen = P.tile_gen;
-    uint32_t tag, tag_all;
+    // (vrt_span.h: with them leave the four tags of the block's 32x8 span -- neighbours in one tag row; the block's own four times
+    // over where the span is cut by the frame's right edge or the launch has no span path, the frame's one word without tags)
+    uint32_t tag, tag_all, st0, st1, st2, st3;
+    bool span_w;
     {
         const_u32_ptr tg = (const_u32_ptr)(P.tile_tags + (size_t)frame * P.tags_per_frame);
         const uint32_t tags_x = P.tags_x, sh = (uint32_t)M.tile >> 4;
         const uint32_t row8 = ((uint32_t)ty << sh) + (uint32_t)(wave >> 1), col8 = ((uint32_t)tx << sh) + (uint32_t)(wave & 1);
-        tag = tg[row8 * tags_x + (tags_x ? col8 : 0u)];
+        span_w = (M.flags & VRT_MAPFLAG_SKY_SPAN) != 0u && span_in_frame(span_x0(col8), (uint32_t)M.W);
+        const uint32_t own = row8 * tags_x + (tags_x ? col8 : 0u);
+        const uint32_t first = (span_w && tags_x) ? own - span_role(col8) : own, step = (span_w && tags_x) ? 1u : 0u;
+        st0 = tg[first]; st1 = tg[first + step]; st2 = tg[first + 2u * step]; st3 = tg[first + 3u * step];
+        const uint32_t k = own - first;                           // (the block's own is one of the four)
+        tag = k == 0u ? st0 : (k == 1u ? st1 : (k == 2u ? st2 : st3));
         tag_all = tg[P.tags_per_frame - 1u];
     }
     // ... and so does the frame's part of ray generation (camera, hoisted constants, strip assignment), in one batch
@@ -763,7 +771,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(((MODE == 4
     SlotOf<TABLE>::head(P, frame, g, cam_right, shard_rank, box);
     asm volatile("" : "+s"(box));
     // (one scalar from here on, not three: past 80 scalar registers a SIMD holds 7 of these waves, not 8)
-    const uint32_t untagged = (uint32_t)__builtin_amdgcn_readfirstlane((tag != tile_gen && tag_all != tile_gen) ? 1 : 0);
+    // (bit 0: the block has no tag; bit 1: its span may take the span path; bit 2: none of the span's blocks has a tag)
+    const uint32_t untagged = (uint32_t)__builtin_amdgcn_readfirstlane(((tag != tile_gen && tag_all != tile_gen) ? 1 : 0) | (span_w ? 2 : 0) |
+                                                                       (span_untagged(st0, st1, st2, st3, tag_all, tile_gen) ? 4 : 0));
     const uint4 boxr = make_uint4(box & 0xFFu, (box >> 8) & 0xFFu, (box >> 16) & 0xFFu, box >> 24);
     float crx = cam_right[0], cry = cam_right[1], crz = cam_right[2];
     float rcp_w = P.rcp_w, rcp_h = P.rcp_h;
@@ -782,10 +792,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(((MODE == 4
     // below are scalar -- a branch, not an EXEC mask around the traversal)
     int lane = threadIdx.x & 63;
     const int px0 = x0 + (wave & 1) * 8, py0 = y0 + (wave >> 1) * 8;       // the wave's 8x8 block (wave-uniform)
-    int px = px0 + (lane & 7);
-    int py = py0 + (lane >> 3);
+    // where the four blocks of the wave's 32x8 span all are skip blocks (below), the four waves trade pixels: each takes two whole
+    // rows of the span (vrt_span.h; every wave of the span reaches this verdict from the same words)
+    const bool span = (untagged & 2u) != 0u && block_skips(box, (uint32_t)px0 & ~31u, (uint32_t)py0, (untagged & 4u) != 0u);
+    int px, py;
+    span_pixel(span, span ? (uint32_t)px0 & ~31u : (uint32_t)px0, (uint32_t)py0, span_role((uint32_t)px0 >> 3), (uint32_t)lane, px, py);
     int W = M.W, H = M.H;
     if (px >= W || py >= H) return;
+    // (two vector registers from here on, whatever they were made from: without this the megakernels' register allocation
+    // changes with the choice above and the bounce chain spills one register more)
+    asm volatile("" : "+v"(px), "+v"(py));
     size_t i = (size_t)py * (size_t)W + (size_t)px;
 
     const DevScene& s = P.sc;
@@ -796,7 +812,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(((MODE == 4
     // volume: it writes what a miss writes without testing the box (wave-uniform: the rectangle is in units of 32 pixels) --
     // and inside the rectangle neither can a wave whose block no occupied 4^3 cell of the volume projects onto (k_tile_tags)
     const bool skip = box != 0xFF00FF00u && ((uint32_t)(px0 >> 5) < boxr.x || (uint32_t)(px0 >> 5) >= boxr.y || (uint32_t)(py0 >> 5) < boxr.z ||
-                                             (uint32_t)(py0 >> 5) >= boxr.w || untagged != 0u);
+                                             (uint32_t)(py0 >> 5) >= boxr.w || (untagged & 1u) != 0u);
     // ... and of everything normalize(), atan() and asin() compute for such a pixel only the sky TEXEL is ever seen: vrt_sky.h
     // decides it from the unnormalised direction with a bound on its distance to the spec's own coordinate; a wave in which
     // some lane lies within that bound of a texel edge goes the long way round, every other wave stores the miss pixel here
@@ -829,6 +845,19 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(((MODE == 4
             const uint32_t c8 = *gptr<const uint32_t>(sky8, (ty * k.w + tx) << 2);
             const uint32_t i32 = (uint32_t)py * (uint32_t)W + (uint32_t)px;
 #ifndef VRT_EXP_STAMPS
+            // (span path: the planes of zeros as NON-TEMPORAL stores -- a whole 128-byte row per instruction has nothing left to merge
+            // in the L2, which the 32-byte pieces of an 8x8 block do: those measured 4.88 against 3.2 ms this way)
+            // (the primary-only kernels, where it was measured; in the megakernels a scalar that lives this long costs the bounce
+            // chain a spilled register more)
+            if (MODE == 1 && span && (M.flags & VRT_MAPFLAG_SIX)) {
+                __builtin_nontemporal_store((vrt_f4){0.0f, 0.0f, 0.0f, 0.0f}, gptr<vrt_f4>(f.position, i32 << 4));
+                __builtin_nontemporal_store((vrt_f2){0.0f, 0.0f}, gptr<vrt_f2>(f.motion, i32 << 3));
+                __builtin_nontemporal_store(0.0f, gptr<float>(f.depth, i32 << 2));
+                __builtin_nontemporal_store(0u, gptr<uint32_t>(f.normal8, i32 << 2));
+                __builtin_nontemporal_store((uint8_t)0, gptr<uint8_t>(f.mask8, i32));
+                *gptr<uint32_t>(f.color8, i32 << 2) = c8;
+                return;
+            }
             if (M.flags & VRT_MAPFLAG_SIX) {                       // the reference's six targets and nothing else: six stores, no pointer tested
                 *gptr<vrt_f4>(f.position, i32 << 4) = (vrt_f4){0.0f, 0.0f, 0.0f, 0.0f};
                 *gptr<vrt_f2>(f.motion, i32 << 3) = (vrt_f2){0.0f, 0.0f};

@@ -70,6 +70,7 @@ struct DevOptions {
                                // tags on the context's stream, 58.5 / 34.1 / 52.2 us on their own; tools/exp_r4_inflight.py)
     int ao_batch = 1;          // the AO rays of a wave from a pool in LDS that every lane draws on (df_ao_pool_loop, brick_ao_pool)
     int sky_fast = 1;          // sky texel of waves that cannot hit anything by vrt_sky.h
+    int sky_span = 1;          // the sky waves of an all-sky 32x8 span store whole rows (vrt_span.h); 0: every wave its own 8x8 block
     int thresh_runs = 1;       // primary rays through df_prim_loop (long runs by threshold)
     int hit_table = 1;         // launches without secondary rays take a hit's colour from the table of colorHit() over materials x normals
     int denoise_th16 = 0;      // the tolerance denoiser on 64 x 16 tiles

@@ -9,6 +9,7 @@
 #include "vrt_traverse.h"
 #include "vrt_sky.h"
 #include "vrt_tags.h"
+#include "vrt_span.h"
 #include "vrt_edit.h"
 #include "vrt_brick_edit.h"
 #include "vrt_reproject.h"
@@ -145,6 +146,7 @@ static_assert(sizeof(FrameSlot) == 256, "FrameSlot is sized for aligned scalar l
 // Everything a workgroup needs to find its tile, in one 64-byte block of the kernel arguments: a wave fetches it with one
 // scalar load and one wait instead of ten loads of one or two dwords, each waited for before the next could be issued.
 #define VRT_MAPFLAG_SKY_FAST 0x10000u   // TileMap::flags: GeomParams::sky_fast, where the wave finds it without a load of its own
+#define VRT_MAPFLAG_SKY_SPAN 0x40000u   // (with SKY_FAST only) the sky waves of an all-sky 32x8 span store whole rows (vrt_span.h; context option sky_span)
 #define VRT_MAPFLAG_SIX      0x20000u   // every frame of the launch holds exactly the reference's six targets (color8, depth, motion, mask8,
                                         // position, normal8; geometry_stage.hpp:19-27): the stores need no test of their pointers
 struct alignas(64) TileMap {

@@ -278,7 +278,7 @@ class Engine:
         return int(v.value)
 
     def options(self, **kv):
-        """with engine.options(tile_tags=0, sky_fast=0): ...  -- the switches are put back on exit."""
+        """with engine.options(tile_tags=0, sky_fast=0, sky_span=0): ...  -- the switches are put back on exit."""
         eng = self
 
         class _Scope:

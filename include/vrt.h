@@ -503,6 +503,33 @@ int  vrt_reproject(vrt_ctx* ctx, int32_t W, int32_t H, const vrt_push* cur, cons
                    const vrt_reproject_settings* settings, const uint8_t* color8, const float* position, const int8_t* normal8,
                    const vrt_history* history_in, const vrt_history* history_out, uint8_t* resolved8, float* motion);
 
+/* ---- temporal upsampling: a DISPLAY-resolution history from jittered render-resolution frames (the part of the FSR2 dispatch,
+ * upscaler_stage.cpp:72-161, that the jitter sequence exists for; the library itself stays out of scope) -----------------------
+ * vrt_reproject keeps its history at render resolution, and the step to the display is one bilinear vrt_blit of it.  vrt_upsample
+ * keeps the history, and writes its outputs, at TW x TH >= w x h: for every display pixel it takes the sample of the render
+ * pixel under it, finds where that sample really fell on the display grid -- its hit point projected through the UNJITTERED
+ * current camera, because the reference adds the jitter to the ray in world x / y (voxel_volume.frag:319) -- and weighs it by a
+ * tent of one display pixel; the history is fetched where the surface was under the unjittered previous camera, with the taps and
+ * the tap test of vrt_reproject, and blended with that weight.  A pixel no sample of this frame fell on carries its history on:
+ * blended with weight 0, or -- where the far sample it was given matches no tap -- the nearest history texel copied whole.
+ * csrc/vrt_upsample.h is the definition, step by step in fp32 and integers; the GPU result equals it bit for bit.
+ * w, h: the size of color8 / position / normal8, the current frame's planes; cur->screen_size and prev->screen_size must both be
+ * (w, h).  TW, TH: the size of both histories (the format of vrt_reproject; vrt_history_bytes(TW, TH, ...) sizes them), of
+ * resolved8 and of motion.  settings: vrt_reproject's; NULL: vrt_reproject_settings_default(cur, ...), whose tol_rel is then two
+ * RENDER-pixel footprints.  history_in NULL starts a new sequence (every pixel: count 1, resolved = its render pixel's colour, what
+ * a nearest-sample blit shows); history_out: other buffers.  resolved8 (RGBA8) and motion (RG32F, in DISPLAY pixels: where the
+ * surface was minus where it is, both without jitter; 0 for a miss and for a point not in front of the previous camera) may each
+ * be NULL.  All DEVICE pointers, aligned to their texel.  Asynchronous on the context's stream.  The frame-size limits of
+ * vrt_render_geometry apply to TW x TH.
+ * VRT_ERR_INVALID, before any device work: a NULL required argument, TW < w or TH < h, a push block whose screen_size is not
+ * (w, h), max_history outside 1..255, a negative or non-finite tolerance, a current or previous camera whose basis is degenerate
+ * (zero or non-finite determinant), a misaligned plane, an output that overlaps another buffer of the call.
+ * Sky pixels keep no history (a miss shows its nearest sample); after vrt_scene_edit_box the caller decides as for vrt_reproject.
+ * There is no vrt_shard here, for the reason vrt_reproject gives. */
+int  vrt_upsample(vrt_ctx* ctx, int32_t w, int32_t h, int32_t TW, int32_t TH, const vrt_push* cur, const vrt_push* prev,
+                  const vrt_reproject_settings* settings, const uint8_t* color8, const float* position, const int8_t* normal8,
+                  const vrt_history* history_in, const vrt_history* history_out, uint8_t* resolved8, float* motion);
+
 /* Replace ffxFsr2GetJitterPhaseCount / ffxFsr2GetJitterOffset as called by UpscalerStage::update
  * (source/voxels/stages/upscaler_stage.cpp:59-70): phase count int(8 * (display_width / render_width)^2);
  * offset = Halton(2,3)(index % phase_count + 1) - 0.5, in pixels; feeds vrt_push.camera_jitter. */

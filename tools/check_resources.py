@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Register budget of the hand-scheduled kernels (csrc: the parts of vrt_device.hip, vrt_denoise.hip, vrt_scene_edit.hip, vrt_query.hip, vrt_reproject.hip), checked
+"""Register budget of the hand-scheduled kernels (csrc: the parts of vrt_device.hip, vrt_denoise.hip, vrt_scene_edit.hip, vrt_query.hip, vrt_reproject.hip, vrt_upsample.hip), checked
 at build time.
 
 K1's look-up loop pins physical registers and the kernel sits at two occupancy cliffs that the compiler's own remark does
@@ -67,12 +67,15 @@ BUDGET = {
     "k_queryILi6ELb0ELb1EE": ("pixel pick, brick march", 64, 80, 0),
     # temporal reprojection (vrt_reproject.hip): a streaming kernel with a four-tap gather; eight waves per SIMD, no scratch (40 VGPRs, 58 SGPRs)
     "k_reprojectENS_15ReprojectParamsE": ("temporal reprojection", 64, 80, 0),
+    # temporal upsampling (vrt_upsample.hip): one thread per display pixel, two projections and the same four-tap gather; eight
+    # waves per SIMD, no scratch (40 VGPRs, 62 SGPRs)
+    "k_upsampleENS_14UpsampleParamsE": ("temporal upsampling", 64, 80, 0),
 }
 
 
 # the objects that hold budgeted kernels, as the Makefile builds them: (source, extra flags); slowest first
 OBJECTS = [("vrt_device.hip", ["-DVRT_K1_PART=%d" % n]) for n in (3, 0, 1, 2)] + [("vrt_denoise.hip", []), ("vrt_scene_edit.hip", []), ("vrt_query.hip", []),
-                                                                                     ("vrt_reproject.hip", [])]
+                                                                                     ("vrt_reproject.hip", []), ("vrt_upsample.hip", [])]
 
 
 def remarks(obj):

@@ -1,8 +1,9 @@
 """Scripted fly-through: replays keyboard / mouse input through CameraController (camera_controller.cpp:30-68)
 and renders every frame through the whole frame graph of voxel_renderer.cpp:55-94 -- geometry (reference defaults: AO 4,
 shadow, <= 5 bounces), 2 denoiser passes, jittered accumulation stand-in for FSR2 at the BALANCED render scale, window blit.
-   python tools/flythrough.py [--frames N] [--png-dir DIR] [--vox FILE] [--reproject]
---reproject keeps the history across the moving frames by temporal reprojection (vrt_reproject) instead of dropping it every frame.
+   python tools/flythrough.py [--frames N] [--png-dir DIR] [--vox FILE] [--reproject [--upsample]]
+--reproject keeps the history across the moving frames by temporal reprojection (vrt_reproject) instead of dropping it every frame;
+--upsample (with --reproject) keeps that history at the target resolution (vrt_upsample) instead of blitting a render-resolution one.
 Prints frame-time statistics measured with HIP events over the whole run (no per-frame synchronisation)."""
 import argparse, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -15,6 +16,7 @@ ap.add_argument("--png-dir", default=None)
 ap.add_argument("--vox", default=None)
 ap.add_argument("--target", default="1920x1080")
 ap.add_argument("--reproject", action="store_true")
+ap.add_argument("--upsample", action="store_true")
 args = ap.parse_args()
 TW, TH = (int(v) for v in args.target.split("x"))
 eng = vrt.Engine(0)
@@ -25,7 +27,7 @@ else:
     sc = vrt.VoxelScene.from_dense(eng, vrt.synthetic.treehouse(N, seed=2), vrt.synthetic.default_palette(metallic_ids=range(200, 256)),
                                    sky=vrt.synthetic.sky_gradient(512, 256), noise=vrt.synthetic.blue_noise_standin(512))
 st = vrt.VoxelRenderSettings(targetResolution=(TW, TH))                      # reference defaults incl. FSR BALANCED render scale
-r = vrt.VoxelRenderer(eng, st, sc, temporal=True, windowSize=(TW, TH), reproject=args.reproject)
+r = vrt.VoxelRenderer(eng, st, sc, temporal=True, windowSize=(TW, TH), reproject=args.reproject, upsample=args.upsample)
 pos, yaw, pitch = vrt.synthetic.default_camera_for(sc.width, sc.height, sc.depth)
 r.camera.position = np.array(pos, np.float32); r.camera.yaw, r.camera.pitch = yaw, pitch; r.camera.updateDirectionVectors()
 third = max(1, args.frames // 3)

@@ -153,6 +153,8 @@ SYMBOLS = {
     "vrt_history_bytes": (C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
     "vrt_reproject": (C.c_int, [_P, C.c_int32, C.c_int32, C.POINTER(Push), C.POINTER(Push), C.POINTER(ReprojectSettings), _P, _P, _P,
                                 C.POINTER(History), C.POINTER(History), _P, _P]),
+    "vrt_upsample": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(Push), C.POINTER(Push), C.POINTER(ReprojectSettings),
+                               _P, _P, _P, C.POINTER(History), C.POINTER(History), _P, _P]),
     "vrt_jitter_phase_count": (C.c_int32, [C.c_int32, C.c_int32]),
     "vrt_jitter_offset": (C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "vrt_last_timings": (C.c_int, [_P, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]),

@@ -1,5 +1,6 @@
 // vrt_api_post.hip -- what the C-ABI does with rendered images: the denoiser stage, strip packing, presentation (blit, accumulate,
-// resolve) and temporal reprojection.  Host code only; the kernels are vrt_denoise.hip, vrt_post.hip and vrt_reproject.hip.
+// resolve), temporal reprojection and temporal upsampling.  Host code only; the kernels are vrt_denoise.hip, vrt_post.hip,
+// vrt_reproject.hip and vrt_upsample.hip.
 //
 // Call surface mirrored from the reference (paths relative to its root):
 //   DenoiserStage::record      source/voxels/stages/denoiser_stage.cpp:143-154,156-258
@@ -355,6 +356,61 @@ int vrt_reproject(vrt_ctx* c, int32_t W, int32_t H, const vrt_push* cur, const v
     p.resolved8 = (uint32_t*)resolved8; p.motion = motion;
     HIPCHK(hipSetDevice(c->device));
     HIPCHK(launch_reproject(p, c->stream));
+    return VRT_OK;
+}
+
+// ---- temporal upsampling (csrc/vrt_upsample.h is the definition, vrt_upsample.hip the kernel) ----
+
+int vrt_upsample(vrt_ctx* c, int32_t w, int32_t h, int32_t TW, int32_t TH, const vrt_push* cur, const vrt_push* prev,
+                 const vrt_reproject_settings* settings, const uint8_t* color8, const float* position, const int8_t* normal8,
+                 const vrt_history* history_in, const vrt_history* history_out, uint8_t* resolved8, float* motion)
+{
+    // every argument error is reported before the context or a device is looked at
+    if (!c || !cur || !prev || !color8 || !position || !normal8 || !history_out || !history_out->color16 || !history_out->surface ||
+        (history_in && (!history_in->color16 || !history_in->surface)))
+        return fail(VRT_ERR_INVALID, "vrt_upsample: NULL argument");
+    if (w <= 0 || h <= 0 || TW <= 0 || TH <= 0 || TW > 32768 || TH > 32768) return fail(VRT_ERR_INVALID, "vrt_upsample: bad frame size");
+    if (TW < w || TH < h) return fail(VRT_ERR_INVALID, "vrt_upsample: the display size is smaller than the render size");
+    if ((int64_t)TW * (int64_t)TH >= ((int64_t)1 << 28))
+        return fail(VRT_ERR_UNSUPPORTED, "vrt_upsample: 2^28 pixels or more per frame (the limit of vrt_render_geometry)");
+    if (cur->screen_size[0] != w || cur->screen_size[1] != h || prev->screen_size[0] != w || prev->screen_size[1] != h)
+        return fail(VRT_ERR_INVALID, "vrt_upsample: screen_size of a push block is not the render size (w, h)");
+    vrt_reproject_settings st;
+    if (settings) st = *settings;
+    else reproject_defaults(cur, w, &st);
+    if (st.max_history < 1u || st.max_history > 255u) return fail(VRT_ERR_INVALID, "vrt_upsample: max_history must be in 1..255");
+    if (!(st.tol_abs >= 0.0f) || !(st.tol_rel >= 0.0f) || !rp_finite(st.tol_abs) || !rp_finite(st.tol_rel))
+        return fail(VRT_ERR_INVALID, "vrt_upsample: a tolerance is negative or not finite");
+    UpsampleParams p;
+    const int bad = upsample_consts(w, h, TW, TH, cur->cam_pos, cur->cam_dir, cur->cam_right, cur->cam_up, prev->cam_pos, prev->cam_dir,
+                                    prev->cam_right, prev->cam_up, st.tol_abs, st.tol_rel, st.max_history, p.k);
+    if (bad) return fail(VRT_ERR_INVALID, bad == 1 ? "vrt_upsample: the current camera's basis is degenerate (zero or non-finite determinant)"
+                                                   : "vrt_upsample: the previous camera's basis is degenerate (zero or non-finite determinant)");
+    const size_t n = (size_t)w * (size_t)h, tn = (size_t)TW * (size_t)TH;
+    struct Range { const char* lo; size_t bytes; bool out; };
+    const Range rg[9] = {
+        {(const char*)color8, n * 4, false}, {(const char*)position, n * 16, false}, {(const char*)normal8, n * 4, false},
+        {history_in ? (const char*)history_in->color16 : nullptr, tn * 8, false},
+        {history_in ? (const char*)history_in->surface : nullptr, tn * 16, false},
+        {(const char*)history_out->color16, tn * 8, true}, {(const char*)history_out->surface, tn * 16, true},
+        {(const char*)resolved8, tn * 4, true}, {(const char*)motion, tn * 8, true}};
+    for (int a = 0; a < 9; a++)
+        for (int b = a + 1; b < 9; b++) {
+            if (!rg[a].lo || !rg[b].lo || (!rg[a].out && !rg[b].out)) continue;
+            if ((uintptr_t)rg[a].lo < (uintptr_t)rg[b].lo + rg[b].bytes && (uintptr_t)rg[b].lo < (uintptr_t)rg[a].lo + rg[a].bytes)
+                return fail(VRT_ERR_INVALID, "vrt_upsample: an output overlaps another buffer (the history is gathered: in and out must differ)");
+        }
+    if ((((uintptr_t)position | (uintptr_t)history_out->surface | (uintptr_t)(history_in ? history_in->surface : nullptr)) & 15u) != 0u ||
+        (((uintptr_t)history_out->color16 | (uintptr_t)(history_in ? history_in->color16 : nullptr) | (uintptr_t)motion) & 7u) != 0u ||
+        (((uintptr_t)color8 | (uintptr_t)normal8 | (uintptr_t)resolved8) & 3u) != 0u)
+        return fail(VRT_ERR_INVALID, "vrt_upsample: a plane is not aligned to its texel size");
+    p.color8 = (const uint32_t*)color8; p.position = (const rp_u4*)position; p.normal8 = (const uint32_t*)normal8;
+    p.hist_color = history_in ? (const rp_u2*)history_in->color16 : nullptr;
+    p.hist_surface = history_in ? (const rp_u4*)history_in->surface : nullptr;
+    p.out_color = (rp_u2*)history_out->color16; p.out_surface = (rp_u4*)history_out->surface;
+    p.resolved8 = (uint32_t*)resolved8; p.motion = motion;
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(launch_upsample(p, c->stream));
     return VRT_OK;
 }
 

@@ -13,6 +13,7 @@
 #include "vrt_edit.h"
 #include "vrt_brick_edit.h"
 #include "vrt_reproject.h"
+#include "vrt_upsample.h"
 
 namespace vrt {
 
@@ -291,8 +292,24 @@ struct ReprojectParams {
     float*          motion;        // RG32F
 };
 
+// Temporal upsampling (vrt_upsample.hip): the call's constants (vrt_upsample.h), the current planes (w * h texels), the previous
+// history (TW * TH texels; both nullptr: a new sequence) and the outputs (TW * TH texels; resolved8 and motion may be nullptr).
+struct UpsampleParams {
+    UpsampleConsts  k;
+    const uint32_t* color8;        // RGBA8
+    const rp_u4*    position;      // RGBA32F
+    const uint32_t* normal8;       // RGBA8_SNORM
+    const rp_u2*    hist_color;
+    const rp_u4*    hist_surface;
+    rp_u2*          out_color;
+    rp_u4*          out_surface;
+    uint32_t*       resolved8;
+    float*          motion;        // RG32F
+};
+
 // launchers: scene build (vrt_scene_build.hip), scene edits (vrt_scene_edit.hip), render (vrt_device.hip: sky, tile tags, hit
-// colours, K1, K2), K3 (vrt_denoise.hip), rows / blit / accumulate / resolve (vrt_post.hip), reprojection (vrt_reproject.hip)
+// colours, K1, K2), K3 (vrt_denoise.hip), rows / blit / accumulate / resolve (vrt_post.hip), reprojection (vrt_reproject.hip),
+// upsampling (vrt_upsample.hip)
 hipError_t launch_build_pyramid(const uint8_t* vox, int W, int H, int D, uint64_t* occ1, uint64_t* occ2,
                                 uint64_t* occ3, hipStream_t s);
 hipError_t launch_build_df(const uint8_t* vox, int W, int H, int D, uint8_t* df, size_t stride, uint8_t* tmp0, uint8_t* tmp1, hipStream_t s, int cap = 0 /* 0: the dense scene's cap */);
@@ -339,6 +356,7 @@ hipError_t launch_blit(const BlitParams& p, hipStream_t s);
 hipError_t launch_accumulate(const void* color_rgba8, void* accum_u32x4, size_t n, int reset, hipStream_t s);
 hipError_t launch_resolve(const void* accum_u32x4, void* out_rgba8, size_t n, uint32_t frames, hipStream_t s);
 hipError_t launch_reproject(const ReprojectParams& p, hipStream_t s);
+hipError_t launch_upsample(const UpsampleParams& p, hipStream_t s);
 const char* primary_kernel_name(int traversal, int fused, int occ2_lds);
 
 } // namespace vrt

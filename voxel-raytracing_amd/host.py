@@ -832,11 +832,13 @@ class UpscalerStage:
     dispatch of record() (:72-161, a prebuilt third-party library) is out of scope; its stand-in is an exact N-frame
     accumulation of the jittered frames followed by the bilinear upscale to targetResolution (vrt_accumulate /
     vrt_resolve / vrt_blit), right while the camera stands still; under a moving camera record_reprojected() keeps the history
-    by temporal reprojection (vrt_reproject) instead."""
+    by temporal reprojection (vrt_reproject) instead, at render resolution, and record_upsampled() keeps it at targetResolution
+    (vrt_upsample): every jittered sample goes where it fell on the display grid, and no blit follows."""
 
     def __init__(self, engine: Engine, settings: VoxelRenderSettings):
         self.engine, self._settings = engine, settings
         self.reprojectSettings = ReprojectSettings()
+        self.motion = None             # record_upsampled: motion vectors at targetResolution (RG32F)
         self._hist = None              # two (color16, surface) pairs, written in turn
         self._hist_cur = -1            # the pair the latest frame wrote; -1: no history
         self._prev_push = None
@@ -873,7 +875,7 @@ class UpscalerStage:
         torch = _torch()
         H, W = color.shape[0], color.shape[1]
         TW, TH = self._settings.targetResolution
-        if self._hist is None or self._hist[0][0].shape[:2] != (H, W):
+        if self._hist is None or self._hist[0][0].shape[:2] != (H, W) or self._resolved is None or self._resolved.shape[:2] != (H, W):
             self._hist = [(torch.zeros((H, W, 4), dtype=torch.int16, device=color.device),
                            torch.zeros((H, W, 4), dtype=torch.int32, device=color.device)) for _ in range(2)]
             self._resolved = torch.zeros((H, W, 4), dtype=torch.uint8, device=color.device)
@@ -894,6 +896,36 @@ class UpscalerStage:
         self._prev_push = _capi.Push.from_buffer_copy(push)
         self.accumulated += 1
         check(lib().vrt_blit(self.engine.ctx, self._resolved.data_ptr(), W, H, self._target.data_ptr(), TW, TH))
+        return self._target
+
+    def record_upsampled(self, color, gbuffer: "GeometryBuffer", push: _capi.Push):
+        """The temporal pass at display resolution (vrt_upsample): `color` (normally the denoised image, at render resolution)
+        feeds a history pair at targetResolution, each sample where it fell on the display grid, the history fetched where each
+        display pixel's surface was under the previous frame's camera.  The motion vectors, in display pixels, go into
+        self.motion; gbuffer.motion is not touched.  reset() starts a new sequence.  Returns the resolved image at
+        targetResolution -- there is no blit."""
+        torch = _torch()
+        H, W = color.shape[0], color.shape[1]
+        TW, TH = self._settings.targetResolution
+        if self._hist is None or self._hist[0][0].shape[:2] != (TH, TW):
+            self._hist = [(torch.zeros((TH, TW, 4), dtype=torch.int16, device=color.device),
+                           torch.zeros((TH, TW, 4), dtype=torch.int32, device=color.device)) for _ in range(2)]
+            self._hist_cur = -1
+        if self._target is None or self._target.shape[:2] != (TH, TW):
+            self._target = torch.zeros((TH, TW, 4), dtype=torch.uint8, device=color.device)
+        if self.motion is None or self.motion.shape[:2] != (TH, TW):
+            self.motion = torch.zeros((TH, TW, 2), dtype=torch.float32, device=color.device)
+        prev = self._prev_push if self._hist_cur >= 0 else push
+        nxt = 1 - self._hist_cur if self._hist_cur >= 0 else 0
+        hin = _capi.History(self._hist[self._hist_cur][0].data_ptr(), self._hist[self._hist_cur][1].data_ptr()) if self._hist_cur >= 0 else None
+        hout = _capi.History(self._hist[nxt][0].data_ptr(), self._hist[nxt][1].data_ptr())
+        st = self.reprojectSettings.to_c(push)
+        check(lib().vrt_upsample(self.engine.ctx, W, H, TW, TH, C.byref(push), C.byref(prev), C.byref(st), color.data_ptr(),
+                                 gbuffer.position.data_ptr(), gbuffer.normal.data_ptr(), C.byref(hin) if hin is not None else None,
+                                 C.byref(hout), self._target.data_ptr(), self.motion.data_ptr()))
+        self._hist_cur = nxt
+        self._prev_push = _capi.Push.from_buffer_copy(push)
+        self.accumulated += 1
         return self._target
 
     def history(self):
@@ -947,10 +979,15 @@ class VoxelRenderer:
     image stays at renderResolution(); temporal=True takes that branch through the accumulation stand-in.
     windowSize=(w, h) appends the blit of :89.  reproject=True (with temporal=True) keeps the history under a moving camera:
     the temporal pass is UpscalerStage.record_reprojected instead of the pixel-by-pixel accumulation, and gBuffer.motion holds
-    the motion vectors; reproject=False is the accumulation exactly."""
+    the motion vectors; reproject=False is the accumulation exactly.  upsample=True (with reproject=True) keeps that history at
+    targetResolution instead (UpscalerStage.record_upsampled: no blit, display-resolution motion in upscaler.motion);
+    upsample=False is the render-resolution path exactly."""
 
     def __init__(self, engine: Engine, settings: Optional[VoxelRenderSettings] = None, scene: Optional[VoxelScene] = None,
-                 noise=None, debug_planes: bool = False, temporal: bool = False, windowSize=None, reproject: bool = False):
+                 noise=None, debug_planes: bool = False, temporal: bool = False, windowSize=None, reproject: bool = False,
+                 upsample: bool = False):
+        if upsample and not reproject:
+            raise ValueError("VoxelRenderer: upsample=True needs reproject=True (the display-resolution history is a reprojected one)")
         self.engine = engine
         self._settings = settings or VoxelRenderSettings()
         self._camera = CameraController()
@@ -961,6 +998,7 @@ class VoxelRenderer:
         self._blitStage = BlitStage(engine, self._settings)
         self.temporal = bool(temporal)
         self.reproject = bool(reproject)
+        self.upsample = bool(upsample)
         self.windowSize = windowSize
         self._time = 0.0
 
@@ -1007,6 +1045,8 @@ class VoxelRenderer:
                          self._settings.renderResolution(), self.frameCount, self.jitter)
 
     def recordCommands(self, shard: Optional[_capi.Shard] = None):    # :55-94
+        if self.upsample and shard is not None:
+            raise ValueError("VoxelRenderer: upsampling across strips is not supported (include/vrt.h, vrt_upsample)")
         push = self.push_constants()
         gBuffer = self._geometryStage.record(push, shard)
         if self._settings.denoiserSettings.enable:
@@ -1018,7 +1058,10 @@ class VoxelRenderer:
             if self.reproject:
                 if shard is not None:
                     raise ValueError("VoxelRenderer: reprojection across strips is not supported (include/vrt.h, vrt_reproject)")
-                color = self._upscalerStage.record_reprojected(color, gBuffer, push)
+                if self.upsample:
+                    color = self._upscalerStage.record_upsampled(color, gBuffer, push)
+                else:
+                    color = self._upscalerStage.record_reprojected(color, gBuffer, push)
             else:
                 color = self._upscalerStage.record(color)
         if self.windowSize is not None:                               # :89

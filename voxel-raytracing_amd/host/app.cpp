@@ -52,7 +52,7 @@ int run(int argc, char** argv)
         auto settings = std::make_shared<VoxelRenderSettings>();
         vec3 pos{8, 8, -50}; float yaw = 90, pitch = 0; bool havePos = false; int device = 0;
         std::vector<int> devices;                                          // --devices a,b,...: one process drives several GPUs
-        int frames = 1; uint32_t windowW = 0, windowH = 0; float flyForward = 0, flyStrafe = 0, flyMouseX = 0; bool temporal = false, reproject = false;
+        int frames = 1; uint32_t windowW = 0, windowH = 0; float flyForward = 0, flyStrafe = 0, flyMouseX = 0; bool temporal = false, reproject = false, upsample = false;
         std::string dumpPushes; std::vector<vrt_push> allPushes;
         for (int i = 1; i < argc; i++) {
             std::string a = argv[i];
@@ -77,6 +77,7 @@ int run(int argc, char** argv)
             else if (a == "--frames") frames = std::max(1, std::stoi(next()));                 // frames to run (update + render each)
             else if (a == "--temporal") temporal = true;                                       // accumulate jittered frames + upscale
             else if (a == "--reproject") reproject = true;                                     // with --temporal: keep the history under --fly (vrt_reproject)
+            else if (a == "--upsample") upsample = true;                                       // with --temporal --reproject: the history at display resolution (vrt_upsample)
             else if (a == "--dump-pushes") dumpPushes = next();                                // every frame's push block, 96 bytes each
             else if (a == "--window") { windowW = (uint32_t)std::stoul(next()); windowH = (uint32_t)std::stoul(next()); }
             else if (a == "--fly") { flyForward = std::stof(next()); flyStrafe = std::stof(next()); flyMouseX = std::stof(next()); }
@@ -104,6 +105,7 @@ int run(int argc, char** argv)
             std::printf("rendered %ux%u on %zu device(s), RCCL gather\n", res[0], res[1], devices.size());
             return EXIT_SUCCESS;
         }
+        if (upsample && !(temporal && reproject)) throw std::runtime_error("--upsample needs --temporal --reproject");
         auto engine = std::make_shared<Engine>(device);
         std::shared_ptr<VoxelScene> scene;
         if (!dense.empty()) scene = loadDense(engine, dense);
@@ -132,7 +134,7 @@ int run(int argc, char** argv)
         if (!havePos) pos = {scene->width / 2.0f, scene->height / 2.0f, -0.8f * scene->depth};
         renderer.camera().position = pos; renderer.camera().yaw = yaw; renderer.camera().pitch = pitch;
         renderer.camera().updateDirectionVectors();
-        renderer.temporal = temporal; renderer.reproject = reproject; renderer.windowW = windowW; renderer.windowH = windowH;
+        renderer.temporal = temporal; renderer.reproject = reproject; renderer.upsample = upsample; renderer.windowW = windowW; renderer.windowH = windowH;
         std::vector<uint8_t> img; uint32_t res[2] = {0, 0};
         const bool moving = flyForward != 0 || flyStrafe != 0 || flyMouseX != 0;
         for (int f = 0; f < frames; f++) {                                                     // App::run loop (source/app.cpp:18-27)

@@ -286,7 +286,8 @@ private:
 
 // UpscalerStage (upscaler_stage.cpp): update() is the reference's jitter / frame sequence (:59-70); record() replaces the
 // FSR2 dispatch (:72-161, prebuilt third party, out of scope) by exact N-frame accumulation + bilinear upscale (a camera at
-// rest), recordReprojected() by temporal reprojection (a moving one).
+// rest), recordReprojected() by temporal reprojection (a moving one), recordUpsampled() by temporal upsampling (the history at
+// targetResolution, no blit).
 class UpscalerStage {
 public:
     float jitterX = 0, jitterY = 0; int frameCount = 0; uint32_t accumulated = 0;
@@ -329,6 +330,31 @@ public:
         check(vrt_blit(engine->ctx, resolved->ptr, (int32_t)w, (int32_t)h, target->ptr, (int32_t)settings->targetResolution[0], (int32_t)settings->targetResolution[1]));
         return target->ptr;
     }
+    // The temporal pass at display resolution (vrt_upsample): the history pair, the resolved image and the motion vectors
+    // (motion(), in display pixels; g.motion is not touched) live at targetResolution, every sample where it fell on the display grid.
+    const uint8_t* recordUpsampled(const uint8_t* color, const GeometryBuffer& g, const vrt_push& push)
+    {
+        const uint32_t w = g.width, h = g.height, tw = settings->targetResolution[0], th = settings->targetResolution[1];
+        size_t tn = (size_t)tw * th;
+        if (!histColor[0] || histColor[0]->count != tn * 4) {
+            for (int k = 0; k < 2; k++) { histColor[k] = std::make_shared<DeviceBuffer<uint16_t>>(engine, tn * 4); histSurface[k] = std::make_shared<DeviceBuffer<uint32_t>>(engine, tn * 4); }
+            histCur = -1;
+        }
+        if (!target || target->count != tn * 4) target = std::make_shared<DeviceBuffer<uint8_t>>(engine, tn * 4);
+        if (!displayMotion || displayMotion->count != tn * 2) displayMotion = std::make_shared<DeviceBuffer<float>>(engine, tn * 2);
+        vrt_reproject_settings st; vrt_reproject_settings_default(&push, &st);
+        if (reprojectSettings.max_history != 0) st.max_history = reprojectSettings.max_history;
+        st.tol_abs = reprojectSettings.tol_abs;
+        if (reprojectSettings.tol_rel >= 0) st.tol_rel = reprojectSettings.tol_rel;
+        const int nxt = histCur >= 0 ? 1 - histCur : 0;
+        vrt_history in{}, out{histColor[nxt]->ptr, histSurface[nxt]->ptr};
+        if (histCur >= 0) { in.color16 = histColor[histCur]->ptr; in.surface = histSurface[histCur]->ptr; }
+        check(vrt_upsample(engine->ctx, (int32_t)w, (int32_t)h, (int32_t)tw, (int32_t)th, &push, histCur >= 0 ? &prevPush : &push, &st, color,
+                           g.position->ptr, g.normal->ptr, histCur >= 0 ? &in : nullptr, &out, target->ptr, displayMotion->ptr));
+        histCur = nxt; prevPush = push; accumulated++;
+        return target->ptr;
+    }
+    const float* motion() const { return displayMotion ? displayMotion->ptr : nullptr; }
     const uint8_t* record(const uint8_t* color, uint32_t w, uint32_t h)
     {
         size_t n = (size_t)w * h * 4;
@@ -345,6 +371,7 @@ private:
     std::shared_ptr<Engine> engine; std::shared_ptr<VoxelRenderSettings> settings; float _deltaMsec = 0;
     std::shared_ptr<DeviceBuffer<uint32_t>> accum; std::shared_ptr<DeviceBuffer<uint8_t>> resolved, target;
     std::shared_ptr<DeviceBuffer<uint16_t>> histColor[2]; std::shared_ptr<DeviceBuffer<uint32_t>> histSurface[2]; int histCur = -1; vrt_push prevPush{};
+    std::shared_ptr<DeviceBuffer<float>> displayMotion;
 };
 
 // BlitStage::record + shader/blit.frag (blit_stage.cpp:41-75): centre-cropped bilinear copy to a window-sized target.
@@ -389,14 +416,15 @@ public:
     }
     // recordCommands (:55-94); returns the RGBA8 image (host copy) and its size in outW / outH.
     // temporal: take the FSR branch (:86-87) through the accumulation stand-in -- or, with reproject, through temporal reprojection,
-    // which keeps the history under a moving camera and fills gBuffer.motion; windowW/H != 0: append the blit (:89).
+    // which keeps the history under a moving camera and fills gBuffer.motion -- with upsample too, at targetResolution (temporal
+    // upsampling: no blit, motion in upscaler().motion()); windowW/H != 0: append the blit (:89).
     std::vector<uint8_t> render(uint32_t* outW = nullptr, uint32_t* outH = nullptr)
     {
         vrt_push push = pushConstants();
         GeometryBuffer g = _geometryStage->record(push);
         const uint8_t* img = _settings->denoiserSettings.enable ? _denoiserStage->record(g) : g.color->ptr;
         uint32_t w = g.width, h = g.height;
-        if (temporal && _settings->fsrSetttings.enable) { img = reproject ? _upscalerStage->recordReprojected(img, g, push) : _upscalerStage->record(img, w, h); w = _settings->targetResolution[0]; h = _settings->targetResolution[1]; }
+        if (temporal && _settings->fsrSetttings.enable) { if (upsample && !reproject) throw std::runtime_error("VoxelRenderer: upsample needs reproject"); img = !reproject ? _upscalerStage->record(img, w, h) : upsample ? _upscalerStage->recordUpsampled(img, g, push) : _upscalerStage->recordReprojected(img, g, push); w = _settings->targetResolution[0]; h = _settings->targetResolution[1]; }
         if (windowW && windowH) { img = _blitStage->record(img, w, h, windowW, windowH); w = windowW; h = windowH; }
         std::vector<uint8_t> host((size_t)w * h * 4);
         check(vrt_memcpy_d2h(engine->ctx, host.data(), img, host.size()));
@@ -405,7 +433,7 @@ public:
         if (outH) *outH = h;
         return host;
     }
-    bool temporal = false, reproject = false; uint32_t windowW = 0, windowH = 0; GeometryBuffer gBuffer;
+    bool temporal = false, reproject = false, upsample = false; uint32_t windowW = 0, windowH = 0; GeometryBuffer gBuffer;
 private:
     std::shared_ptr<Engine> engine; std::shared_ptr<VoxelRenderSettings> _settings; std::shared_ptr<VoxelScene> _scene;
     std::unique_ptr<CameraController> _camera; std::unique_ptr<GeometryStage> _geometryStage; std::unique_ptr<DenoiserStage> _denoiserStage;

@@ -352,6 +352,34 @@ int  vrt_occluded_rays(vrt_ctx* ctx, const vrt_scene* scene, int64_t n, const fl
 int  vrt_pick_pixels(vrt_ctx* ctx, const vrt_scene* scene, const vrt_push* push, uint32_t max_steps,
                      int64_t n, const int32_t* xy, const vrt_ray_hits* out);
 
+/* ---- ray generation for caller-side cameras (no reference analogue: the only camera the reference draws is main()'s pinhole,
+ * voxel_volume.frag:312-322, whose horizontal field of view is fixed at 90 degrees because camDir is re-normalised -- the
+ * CameraController's focal length has no effect) ---------------------------------------------------------------------------------
+ * vrt_camera_rays writes the primary rays of a W x H frame under one of three camera models into the two planes of 3 packed
+ * floats per ray that vrt_trace_rays and vrt_occluded_rays take: which voxel every pixel of a wide-angle, an orthographic or a
+ * panoramic view sees, or whether it sees one, is then one more call.  csrc/vrt_raygen.h defines the three models step by step in
+ * fp32; the GPU result equals it bit for bit.  (The rays are traced, not shaded: the geometry stage's G-buffer is still drawn by
+ * the built-in camera only.) */
+#define VRT_CAMERA_PERSPECTIVE  0   /* main()'s pinhole with a field of view: tan_half = tan(horizontal FOV / 2); 1.0f is the reference's camera bit for bit */
+#define VRT_CAMERA_ORTHOGRAPHIC 1   /* parallel rays along cam_dir; half_width: half the view's width in voxels */
+#define VRT_CAMERA_PANORAMA     2   /* equirectangular around cam_pos, the inverse of skyColor's mapping (frag:98-105); the basis is not used */
+typedef struct vrt_ray_camera {
+    int32_t  model;        /* VRT_CAMERA_* */
+    vrt_push basis;        /* cam_pos, cam_dir, cam_right, cam_up, camera_jitter (perspective only); the other fields are not read */
+    float    tan_half;     /* perspective: > 0 and finite */
+    float    half_width;   /* orthographic: > 0 and finite */
+} vrt_ray_camera;
+/* The rays of a W x H frame: origins and dirs are DEVICE pointers to W * H x 3 packed floats, ray py * W + px for pixel (px, py),
+ * 4-byte aligned, not overlapping.  Perspective and panorama directions are unit vectors, the orthographic one is
+ * normalize(cam_dir).  With VRT_CAMERA_PERSPECTIVE and tan_half == 1.0f ray py * W + px is the ray vrt_pick_pixels traces for
+ * pixel (px, py) under `basis` with screen_size (W, H).  Asynchronous on the context's stream (the panorama's tables --
+ * 8 (W + H) bytes -- are uploaded with the call; a second panorama call on the context waits for the first one's kernel).
+ * Frame-size limits of vrt_render_geometry.
+ * VRT_ERR_INVALID, before any device work: a NULL argument, W or H < 1 or beyond the limits, a misaligned or overlapping
+ * pointer, an unknown model, a tan_half (perspective) or half_width (orthographic) that is not finite and positive, a
+ * degenerate basis (non-finite position or jitter; perspective and orthographic: a zero or non-finite determinant). */
+int  vrt_camera_rays(vrt_ctx* ctx, const vrt_ray_camera* camera, int32_t W, int32_t H, float* origins, float* dirs);
+
 /* ---- denoiser stage -------------------------------------------------------------------------- */
 #define VRT_DENOISE_CANONICAL  0  /* the intended 9-tap a-trous filter                               */
 #define VRT_DENOISE_AS_SHIPPED 1  /* the std140-aliased 3-tap filter the shipped UBO upload produces  */

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Register budget of the hand-scheduled kernels (csrc: the parts of vrt_device.hip, vrt_denoise.hip, vrt_scene_edit.hip, vrt_query.hip, vrt_reproject.hip, vrt_upsample.hip), checked
+"""Register budget of the hand-scheduled kernels (csrc: the parts of vrt_device.hip, vrt_denoise.hip, vrt_scene_edit.hip, vrt_query.hip, vrt_reproject.hip, vrt_upsample.hip, vrt_rays.hip), checked
 at build time.
 
 K1's look-up loop pins physical registers and the kernel sits at two occupancy cliffs that the compiler's own remark does
@@ -70,12 +70,14 @@ BUDGET = {
     # temporal upsampling (vrt_upsample.hip): one thread per display pixel, two projections and the same four-tap gather; eight
     # waves per SIMD, no scratch (40 VGPRs, 62 SGPRs)
     "k_upsampleENS_14UpsampleParamsE": ("temporal upsampling", 64, 80, 0),
+    # ray generation for caller-side cameras (vrt_rays.hip): a stream of 24 B per pixel; eight waves per SIMD, no scratch (15 VGPRs, 35 SGPRs)
+    "k_camera_raysENS_12RayCamConstsE": ("ray generation, three camera models", 32, 48, 0),
 }
 
 
 # the objects that hold budgeted kernels, as the Makefile builds them: (source, extra flags); slowest first
 OBJECTS = [("vrt_device.hip", ["-DVRT_K1_PART=%d" % n]) for n in (3, 0, 1, 2)] + [("vrt_denoise.hip", []), ("vrt_scene_edit.hip", []), ("vrt_query.hip", []),
-                                                                                     ("vrt_reproject.hip", []), ("vrt_upsample.hip", [])]
+                                                                                     ("vrt_reproject.hip", []), ("vrt_upsample.hip", []), ("vrt_rays.hip", [])]
 
 
 def remarks(obj):

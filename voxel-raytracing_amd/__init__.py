@@ -6,7 +6,7 @@ from . import _capi
 from ._capi import (TRAVERSAL_AUTO, TRAVERSAL_DENSE, TRAVERSAL_BITMASK, TRAVERSAL_JUMP, TRAVERSAL_DF, TRAVERSAL_DFJ,
                     DENOISE_CANONICAL, DENOISE_AS_SHIPPED, DENOISE_FAST, VrtError, lib)
 from .host import (AmbientOcclusionSettings, BlitStage, CameraController, CameraKey, DenoiserSettings, DenoiserStage, Engine,
-                   FsrScaling, FsrSettings, GeometryBuffer, GeometryStage, LightSettings, ReprojectSettings, TraceSettings,
+                   FsrScaling, FsrSettings, GeometryBuffer, GeometryStage, LightSettings, RayCamera, ReprojectSettings, TraceSettings,
                    UpscalerStage, camera_path,                   VoxelRenderSettings, VoxelRenderer, VoxelScene, load_image, make_push, make_shard, vox_flatten_host,
                    write_image)
 from . import synthetic

@@ -74,6 +74,14 @@ class ReprojectSettings(C.Structure):
     _fields_ = [("max_history", C.c_uint32), ("tol_abs", C.c_float), ("tol_rel", C.c_float)]
 
 
+CAMERA_PERSPECTIVE, CAMERA_ORTHOGRAPHIC, CAMERA_PANORAMA = 0, 1, 2       # vrt_ray_camera.model
+
+
+class RayCamera(C.Structure):
+    """vrt_ray_camera: a camera model for vrt_camera_rays (csrc/vrt_raygen.h)."""
+    _fields_ = [("model", C.c_int32), ("basis", Push), ("tan_half", C.c_float), ("half_width", C.c_float)]
+
+
 MAX_QUERY_RAYS = 1 << 28       # rays per vrt_trace_rays / vrt_occluded_rays / vrt_pick_pixels call
 
 assert C.sizeof(Push) == 96 and C.sizeof(Material) == 32
@@ -130,6 +138,7 @@ SYMBOLS = {
     "vrt_trace_rays": (C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_uint32, C.POINTER(RayHits)]),
     "vrt_occluded_rays": (C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_uint32, _P]),
     "vrt_pick_pixels": (C.c_int, [_P, _P, C.POINTER(Push), C.c_uint32, C.c_int64, _P, C.POINTER(RayHits)]),
+    "vrt_camera_rays": (C.c_int, [_P, C.POINTER(RayCamera), C.c_int32, C.c_int32, _P, _P]),
     "vrt_denoiser_settings_default": (None, [C.POINTER(DenoiserSettings)]),
     "vrt_denoise": (C.c_int, [_P, C.c_int32, C.c_int32, C.POINTER(DenoiserSettings), _P, _P, _P, _P, _P,
                               C.POINTER(Shard), C.POINTER(_P)]),

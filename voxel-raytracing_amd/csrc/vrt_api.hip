@@ -1,7 +1,7 @@
 // vrt_api.hip -- the C-ABI of libvrt_hip.so (include/vrt.h): the error string, contexts and their options, device memory, the
 // host-only calls (settings defaults, images, .vox flattening, jitter), the geometry stage and the instrumentation.  Scenes are in
 // vrt_api_scene.hip, the denoiser / strip packing / presentation / reprojection in vrt_api_post.hip, the ray queries in
-// vrt_api_query.hip, RCCL in vrt_api_comm.hip; vrt_host.h is what they share.  Host code only; kernels live in the other .hip files.
+// vrt_api_query.hip, ray generation in vrt_api_rays.hip, RCCL in vrt_api_comm.hip; vrt_host.h is what they share.  Host code only; kernels live in the other .hip files.
 //
 // Call surface mirrored from the reference (paths relative to its root):
 //   GeometryStage::record      source/voxels/stages/geometry_stage.cpp:106-153
@@ -78,6 +78,8 @@ void vrt_ctx_destroy(vrt_ctx* c)
         if (c->tab_uploaded[i]) hipEventDestroy(c->tab_uploaded[i]);
         if (c->tab_consumed[i]) hipEventDestroy(c->tab_consumed[i]);
     }
+    if (c->pano_host) hipHostFree(c->pano_host);
+    if (c->pano_done) hipEventDestroy(c->pano_done);
     hipEventDestroy(c->ev_geo0); hipEventDestroy(c->ev_prim1); hipEventDestroy(c->ev_geo1);
     hipEventDestroy(c->ev_den0); hipEventDestroy(c->ev_den1);
     if (c->own_stream && c->stream) hipStreamDestroy(c->stream);
@@ -93,7 +95,7 @@ int vrt_ctx_set_stream(vrt_ctx* c, void* hip_stream)
     c->stream = (hipStream_t)hip_stream;      // NULL is a valid handle: the HIP null (legacy default) stream
     c->own_stream = false;
     c->have_geo = c->have_den = false;
-    c->checked_ptrs[0] = c->checked_ptrs[1] = 0;
+    c->checked_ptrs[0] = c->checked_ptrs[1] = c->checked_ptrs[3] = 0;
     return VRT_OK;
 }
 
@@ -152,7 +154,7 @@ int vrt_device_free(vrt_ctx* c, void* p)
     HIPCHK(hipSetDevice(c->device));
     HIPCHK(hipStreamSynchronize(c->stream));
     if (p) HIPCHK(hipFree(p));
-    c->checked_ptrs[0] = c->checked_ptrs[1] = 0;     // a freed address may come back as something else: verify again
+    c->checked_ptrs[0] = c->checked_ptrs[1] = c->checked_ptrs[3] = 0;     // a freed address may come back as something else: verify again
     return VRT_OK;
 }
 

@@ -98,7 +98,7 @@ struct vrt_ctx {
     vrt::DevBuf<uint32_t> hit_list;   // [records_px] + 1 counter word at the end
     size_t records_px = 0;
     int div_w = 0, div_h = 0, div_ok = 0;   // screen size last examined by screen_div_ok, and its verdict
-    uint64_t checked_ptrs[3] = {0, 0, 0};   // digests of the image pointers last verified to be device memory (geometry, denoiser, ray queries)
+    uint64_t checked_ptrs[4] = {0, 0, 0, 0};   // digests of the image pointers last verified to be device memory (geometry, denoiser, ray queries, vrt_camera_rays)
     // frame-slot tables of launches with more than VRT_MAX_BATCH frames: a ring of device tables, each with a pinned host
     // image that is uploaded on a stream of its own (the copy runs while the previous launch is still tracing)
     static constexpr int kTabRing = 4;
@@ -127,6 +127,13 @@ struct vrt_ctx {
     vrt::DevBuf<uint32_t> den_counts;  // [10 passes][VRT_DENOISE_SEGS]
     int den_last_passes = 0;           // passes of the latest vrt_denoise call that went through k_denoise_ver (bit i = pass i)
     vrt_settings hit_settings{};
+    // vrt_camera_rays, panorama: the column and row tables (vrt_raygen.h) in device memory, their pinned host image, and the
+    // event behind the kernel that last read them
+    vrt::DevBuf<float> pano_dev;
+    float* pano_host = nullptr;
+    size_t pano_floats = 0;
+    hipEvent_t pano_done = nullptr;
+    bool pano_busy = false;
 };
 
 struct vrt_scene {

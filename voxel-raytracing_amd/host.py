@@ -640,6 +640,49 @@ def make_push(camera: CameraController, scene_dims, resolution, frame=0, jitter=
     return p
 
 
+class RayCamera:
+    """A camera model whose rays vrt_camera_rays makes on the device (csrc/vrt_raygen.h defines the three models): the built-in
+    pinhole with any field of view, an orthographic view, an equirectangular panorama -- as the two (W * H, 3) tensors that
+    VoxelScene.trace_rays and VoxelScene.occluded take."""
+
+    def __init__(self, model: int, camera: CameraController, tan_half: float = 1.0, half_width: float = 1.0):
+        self.model, self.camera = int(model), camera
+        self.tan_half, self.half_width = float(tan_half), float(half_width)
+
+    @classmethod
+    def perspective(cls, controller: CameraController, fov_deg: float = 90.0) -> "RayCamera":
+        """main()'s pinhole with a horizontal field of view of fov_deg; 90 is the reference's camera bit for bit (tan_half = 1)."""
+        return cls(_capi.CAMERA_PERSPECTIVE, controller, tan_half=float(np.float32(math.tan(math.radians(float(fov_deg)) / 2.0))))
+
+    @classmethod
+    def orthographic(cls, controller: CameraController, half_width: float) -> "RayCamera":
+        """Parallel rays along the controller's direction; the view is 2 * half_width voxels wide."""
+        return cls(_capi.CAMERA_ORTHOGRAPHIC, controller, half_width=half_width)
+
+    @classmethod
+    def panorama(cls, position) -> "RayCamera":
+        """Equirectangular around `position`, the inverse of the sky's own mapping."""
+        return cls(_capi.CAMERA_PANORAMA, CameraController(position=position))
+
+    def to_c(self, resolution, jitter=(0.0, 0.0)) -> _capi.RayCamera:
+        c = _capi.RayCamera()
+        c.model = self.model
+        c.basis = make_push(self.camera, (0, 0, 0), resolution, 0, jitter)
+        c.tan_half, c.half_width = self.tan_half, self.half_width
+        return c
+
+    def rays(self, engine: "Engine", resolution, jitter=(0.0, 0.0)):
+        """(origins, dirs): two float32 device tensors (W * H, 3), ray py * W + px for pixel (px, py); the jitter, in pixels,
+        applies to the perspective model only.  Enqueued on the engine's stream, not waited for."""
+        torch = _torch()
+        W, H = int(resolution[0]), int(resolution[1])
+        cam = self.to_c((W, H), jitter)
+        o = torch.empty((max(W * H, 0), 3), dtype=torch.float32, device=engine.torch_device)
+        d = torch.empty_like(o)
+        check(lib().vrt_camera_rays(engine.ctx, C.byref(cam), W, H, C.c_void_p(o.data_ptr()), C.c_void_p(d.data_ptr())))
+        return o, d
+
+
 # --------------------------------------------------------------------------------------------------
 # stages
 # --------------------------------------------------------------------------------------------------

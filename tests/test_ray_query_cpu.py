@@ -14,7 +14,8 @@ NATIVE = os.path.join(ROOT, "tests", "native")
 SRC = os.path.join(NATIVE, "query_host.cpp")
 LIB = os.path.join(NATIVE, "libquery_host.so")
 DEPS = [SRC, os.path.join(NATIVE, "traverse_host.cpp"), os.path.join(ROOT, "include", "vrt.h")] + \
-       [os.path.join(ROOT, "voxel-raytracing_amd", "csrc", h) for h in ("vrt_query.h", "vrt_traverse.h", "vrt_spec.h")]
+       [os.path.join(ROOT, "voxel-raytracing_amd", "csrc", h) for h in
+        ("vrt_query.h", "vrt_traverse.h", "vrt_volume.h", "vrt_dda.h", "vrt_spec.h")]
 
 N_RAYS = 5000
 BUDGETS = (512, 64, 37, 1)

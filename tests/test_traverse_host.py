@@ -11,7 +11,8 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "tests", "native", "traverse_host.cpp")
 LIB = os.path.join(ROOT, "tests", "native", "libtraverse_host.so")
-HDRS = [os.path.join(ROOT, "voxel-raytracing_amd", "csrc", h) for h in ("vrt_traverse.h", "vrt_spec.h")]
+HDRS = [os.path.join(ROOT, "voxel-raytracing_amd", "csrc", h) for h in
+        ("vrt_traverse.h", "vrt_volume.h", "vrt_dda.h", "vrt_spec.h")]
 
 
 @pytest.fixture(scope="module")

@@ -6,6 +6,9 @@
 //   k_sky_*, k_hit_colors, k_tile_tags   the tables and tags K1 reads
 // (scene build: vrt_scene_build.hip; scene edits: vrt_scene_edit.hip; K3: vrt_denoise.hip; strips, blit, accumulate, resolve:
 // vrt_post.hip.)  Compiled in four parts, -DVRT_K1_PART=0..3: the list behind launch_shade_t.
+// This file is the kernels and their launch code.  What they are made of: vrt_shade.h (traceRay, the secondary rays, colorHit,
+// colorMainRay -- and, at its head, what a kernel that calls them owes them), vrt_frame_slot.h (the frame slot from the kernel
+// arguments or the table, the workgroup -> tile map, the colour store), vrt_traverse.h (the march).
 //
 // A wave owns an 8x8 pixel block so that its 64 rays stay spatially coherent; the default (clearance-field)
 // traversal runs one wave per workgroup, the LDS-staged ones 16x16 tiles of four waves.  Rays are generated in-kernel
@@ -15,705 +18,14 @@
 // All arithmetic follows vrt_spec.h (fp32, -ffp-contract=off); the DDA state (sideDist, mapPos, mask)
 // is advanced with exactly the additions of voxel_volume.frag:164-170 in every traversal mode, so hit
 // voxel, mask, t and step budget are independent of the mode.
-#include "vrt_device_common.h"
+#include "vrt_shade.h"
+#include "vrt_frame_slot.h"
 
 namespace vrt {
 
 // ---------------------------------------------------------------------------------------------
-// traversal
-// ---------------------------------------------------------------------------------------------
-
-struct RayHit {            // RayHit, voxel_volume.frag:43-49
-    uint32_t material;
-    f3 pos, normal, dir;
-    uint32_t ncode;        // which of the 26 face / edge / corner normals `normal` is: mask | (sx<0)<<3 | (sy<0)<<4 | (sz<0)<<5;
-                           // 0xFFFFFFFF: none of them (the zero vector of rule A, or a masked axis the ray does not move along)
-};
-
-// Occupancy summaries as seen by a workgroup: LDS copies when they fit (typed address_space(3) pointers, so
-// that the lookups compile to ds_read_b64 and not to flat loads), the L2-resident originals otherwise.
-typedef const __attribute__((address_space(3))) uint64_t* lds_u64_ptr;
-template <bool LDS> struct OccT;
-template <> struct OccT<true>  { lds_u64_ptr o2, o3; };
-template <> struct OccT<false> { const uint64_t* o2; const uint64_t* o3; };
-
-__device__ __forceinline__ f3 hit_normal(uint32_t mask, int sx, int sy, int sz)
-{
-    // normalize(-mask * rayStep) (frag:190): the vector has k = popcount(mask) components of +-1, so its length is
-    // RN(sqrt(k)) and every non-zero component is +-RN(1 / RN(sqrt(k))) -- three constants instead of a square root
-    // and three IEEE divisions (k = 0: the zero vector, canonical rule A).  A masked axis with rayStep = 0 (possible only
-    // through rule A's initial mask) changes k's meaning; that case keeps the general form.
-    const uint32_t k = __builtin_popcount(mask & 7u);
-    const float c = k == 1u ? 1.0f : (k == 2u ? __uint_as_float(0x3f3504f3u) : __uint_as_float(0x3f13cd3au));
-    const bool general = ((mask & 1u) && sx == 0) || ((mask & 2u) && sy == 0) || ((mask & 4u) && sz == 0);
-    f3 n = mk3((mask & 1u) ? (float)(-sx) : 0.0f, (mask & 2u) ? (float)(-sy) : 0.0f, (mask & 4u) ? (float)(-sz) : 0.0f);
-    if (general) return normalize3(n);
-    return mk3(n.x * c, n.y * c, n.z * c);
-}
-
-// traceRay, voxel_volume.frag:176-196
-template <int TRAV, class Occ, bool AHEAD = false, bool PF = false>
-__device__ __forceinline__ void trace_ray(const DevScene& s, const Occ occ, f3 start, f3 dir,
-                                          uint32_t maxSteps, RayHit& h, RayInt& r)
-{
-    trace_int<TRAV, decltype(occ.o2), AHEAD, false, PF>(s.vol, occ.o2, occ.o3, start, dir, maxSteps, r);
-    h.material = r.material;
-    h.dir = dir;
-    // values first, one assignment to h afterwards: stores to h from both sides of the branch were being merged into
-    // address-selected scratch stores (28 B of scratch per lane, which also slows the wave launch)
-    f3 pos = mk3(0.0f, 0.0f, 0.0f), nrm = mk3(0.0f, 0.0f, 0.0f);
-    uint32_t ncode = 0xFFFFFFFFu;
-    if (r.material != 0) {
-        nrm = hit_normal(r.mask, r.sx, r.sy, r.sz);
-        const bool general = (r.mask & 7u) == 0u || ((r.mask & 1u) && r.sx == 0) || ((r.mask & 2u) && r.sy == 0) || ((r.mask & 4u) && r.sz == 0);
-        if (!general) ncode = (r.mask & 7u) | ((uint32_t)(r.sx < 0) << 3) | ((uint32_t)(r.sy < 0) << 4) | ((uint32_t)(r.sz < 0) << 5);
-        f3 m = mk3((r.mask & 1u) ? (r.side.x - r.delta.x) : 0.0f,
-                   (r.mask & 2u) ? (r.side.y - r.delta.y) : 0.0f,
-                   (r.mask & 4u) ? (r.side.z - r.delta.z) : 0.0f);
-        float d = len3(m);
-        pos = mk3(r.pos.x + d * dir.x, r.pos.y + d * dir.y, r.pos.z + d * dir.z);
-    }
-    h.pos = pos;
-    h.normal = nrm;
-    h.ncode = ncode;
-}
-
-// ---------------------------------------------------------------------------------------------
-// shading helpers
-// ---------------------------------------------------------------------------------------------
-
-// pc: the push block of the pixel's frame; noise: the pixel's blue-noise texel, decoded on first use (it is the same for
-// every AO sample and every bounce of the pixel)
-// (kernels of VRT_TRAVERSAL_DF_FAST never fill iteration-count planes -- vrt_api.hip sends every launch that has them to the counting twins,
-// VRT_TRAVERSAL_DF_FAST_CNT -- so for them `fetches` is dead and the compiler drops it: VRT_COUNTS(TRAV))
-#define VRT_COUNTS(TRAV) ((TRAV) != VRT_TRAVERSAL_DF_FAST && (TRAV) != VRT_TRAVERSAL_BRICK)
-struct PixCtx { int px, py; uint32_t fetches, rays; const vrt_push* pc; f3 noise;
-                uint32_t ldsw; };    // ldsw: byte address of the wave's VRT_AO_SLOT bytes of LDS (df_ao_pool_loop): kernels that trace AO rays through the hand-written loop
-
-// skyColor, voxel_volume.frag:98-105
-__device__ __forceinline__ f3 sky_color(const DevScene& s, f3 d)
-{
-    float u = atan2_spec(d.z, d.x) * 0.1591f + 0.5f;
-    float v = asin_spec(-d.y) * 0.3183f + 0.5f;
-    uint32_t x = wrap_texel(u, s.sky_w), y = wrap_texel(v, s.sky_h);
-    const float4 t = reinterpret_cast<const float4*>(s.sky)[(size_t)y * s.sky_w + x];
-    return mk3(t.x, t.y, t.z);
-}
-
-// fragmentNoiseSeq + randomDir, voxel_volume.frag:80-95
-__device__ __forceinline__ f3 random_dir(const DevScene& s, const vrt_push& pc, PixCtx& c, uint32_t num)
-{
-    uint32_t offset = num * 32u + pc.frame % 32u;
-    const float g = 1.22074408460575947536f;
-    const float a0 = 1.0f / g, a1 = 1.0f / (g * g), a2 = 1.0f / ((g * g) * g);
-    {   // (the pixel's blue-noise texel is fetched anew for every sample: kept across the traces it cost four registers and, through the
-        // branch around the fetch, a second copy of everything after it -- 1 350 instructions of the megakernel)
-        float pxf = ((float)c.px + 0.5f) / 512.0f + 0.5f;
-        float pyf = ((float)c.py + 0.5f) / 512.0f + 0.5f;
-        uint32_t tx = wrap_texel(pxf, s.noise_w), ty = wrap_texel(pyf, s.noise_h);
-        const uchar4 t = reinterpret_cast<const uchar4*>(s.noise)[(size_t)ty * s.noise_w + tx];
-        c.noise = mk3(decode_unorm8(t.x), decode_unorm8(t.y), decode_unorm8(t.z));          // = t / 255.0f, exactly
-    }
-    float fo = (float)offset;
-    float n0 = c.noise.x + fo * a0;
-    float n1 = c.noise.y + fo * a1;
-    float n2 = c.noise.z + fo * a2;
-    n0 = n0 - floorf(n0); n1 = n1 - floorf(n1); n2 = n2 - floorf(n2);
-    return normalize3(mk3(n0 * 2.0f - 1.0f, n1 * 2.0f - 1.0f, n2 * 2.0f - 1.0f));
-}
-
-// main() ray generation, voxel_volume.frag:312-322 (+ screen_quad.vert:18-31)
-__device__ __forceinline__ f3 primary_dir(const FrameSlot& S, int px, int py)
-{
-    const RayGenConsts& g = S.rg;
-    float sx = (((float)px + 0.5f) / g.W) * 2.0f - 1.0f;
-    float sy = (((float)py + 0.5f) / g.H) * 2.0f - 1.0f;
-    float vx = ((g.cd.x + sx * S.pc.cam_right[0]) + sy * g.planeV.x) + g.jx;
-    float vy = ((g.cd.y + sx * S.pc.cam_right[1]) + sy * g.planeV.y) + g.jy;
-    float vz = ((g.cd.z + sx * S.pc.cam_right[2]) + sy * g.planeV.z) + 0.0f;
-    return normalize3(mk3(vx, vy, vz));
-}
-
-// (primary_v and primary_normalize, K1's form of the same: vrt_device_common.h -- the pick kernel of vrt_query.hip generates its rays with them too)
-
-// calcAmbient + isShadowed + color + colorHit, voxel_volume.frag:205-264, in two halves: the secondary rays of a hit (what they
-// find: how many AO rays hit something, whether the light is hidden) and the arithmetic on what they found.  color_hit is the two
-// one after the other; the packed bounce chain (color_main_ray_packed) runs the first half on the way out and the second on the
-// way back.
-// SEC = false: the host has established ao_samples == 0 and shadows == 0 (K1 MODE 1), so neither loop is compiled in.
-// active: the lane has a hit whose secondary rays are wanted.  Where the AO rays go through the wave's pool the function must be reached
-// by the wave's other lanes as well (wave-uniform control flow at the call site): a lane without a hit of its own has no rays in
-// the pool but takes rays from it like everybody else -- the pixels of a block's silhouette, and the few metallic pixels of a bounce,
-// get the whole wave's help.  (Called from divergent code the pool simply serves the lanes that are there.)
-template <int TRAV, class Occ, bool SEC = true>
-__device__ __forceinline__ void secondary_rays(const GeomParams& P, const Occ occ, PixCtx& c, const f3 pos, const f3 normal, uint32_t depth,
-                                               float& ambient, uint32_t& ao_hits, bool& shadowed, const bool active = true)
-{
-    const DevScene& s = P.sc;
-    const vrt_settings& st = P.st;
-    ambient = 0.0f; ao_hits = 0u;
-    constexpr bool kBatch = TRAV == VRT_TRAVERSAL_DF_FAST || TRAV == VRT_TRAVERSAL_DF_FAST_CNT;
-    if (!SEC || st.ao_samples == 0) {
-        ambient = 1.0f;
-    } else if (kBatch && __builtin_amdgcn_readfirstlane((int)s.vol.ao_batch) != 0) {
-        // the hand-written loop: the AO rays of the wave's pixels from a pool in LDS that every lane draws on (df_ao_pool_loop) --
-        // sample after sample each lane writes its pixel's ray into its column, and whichever lane is free traces it and reports
-        // to the column's counter; which lane traces a ray changes nothing about what the ray finds
-        constexpr bool kCnt = TRAV == VRT_TRAVERSAL_DF_FAST_CNT;
-        const uint32_t ldsw = c.ldsw;
-        const uint64_t act = __ballot(active);
-        const uint32_t col = __builtin_amdgcn_mbcnt_hi((uint32_t)(act >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)act, 0u));
-        __attribute__((address_space(3))) uint32_t* cnt = (__attribute__((address_space(3))) uint32_t*)(uintptr_t)(ldsw + 3072u + col * 4u);
-        if (active) { cnt[0] = 0u; if (kCnt) cnt[64] = 0u; }
-        // the fields as the loops address them (offsets count from one slice in front of field 0)
-        const uint8_t* const fld = s.vol.df - (size_t)(s.vol.W + 2) * (size_t)(s.vol.H + 2);
-        AoLane lane;
-        ao_lane_rest(s.vol, lane);
-        uint32_t next = 0u, looks = 0u, direct_hits = 0u, direct_fet = 0u;
-        for (uint32_t i = 0; i < st.ao_samples; i++) {
-            // The OWNER looks at its ray's first voxel itself -- every lane at once, where in the pool a ray's first look is a round of
-            // the loop like any other: a ray in the open (the clearance covers its budget) and a ray that starts on a 0 byte are
-            // decided here and never enter the pool; the others bring their first clearance with them and are marched from the round
-            // they are taken up in.  The rays that will creep (clearance 1 or 2) wait in FRONT of the pool: the longest rays of a
-            // sample start first, which is what the end of the AO phase waits for.
-            bool store = false;
-            uint32_t c0 = 0u;
-            AoRay a;
-            if (active) {
-                f3 rd = random_dir(s, *c.pc, c, i + depth * st.ao_samples);
-                f3 dir = mk3(normal.x + rd.x, normal.y + rd.y, normal.z + rd.z);
-                f3 o = mk3(pos.x + dir.x * 0.01f, pos.y + dir.y * 0.01f, pos.z + dir.z * 0.01f);
-                ao_ray_setup(s.vol, o, dir, a);
-                c0 = fld[a.idx0];
-                if (kCnt) looks += 1u;
-                if (c0 == 0u) {                                // solid, border or open cell: the voxel id says which (frag:157 at iteration 0)
-                    const uint32_t id = fld[a.idx0 + a.voxoff];
-                    if (id != 0u) direct_hits++;
-                    if (kCnt) { looks += 1u; direct_fet += id != 0u ? 1u : 0u; }
-                } else if (c0 >= st.ao_steps) {                // nothing but empty voxels until the budget ends: a miss
-                    if (kCnt) direct_fet += s.vol.count_marched != 0u ? 0u : st.ao_steps;
-                } else store = true;
-            }
-            const bool creeps = store && c0 <= 2u;
-            const uint64_t mc = __ballot(creeps), mo = __ballot(store && !creeps);
-            const uint32_t nc = (uint32_t)__builtin_popcountll(mc);
-            if (store) {
-                const uint32_t slot = creeps ? __builtin_amdgcn_mbcnt_hi((uint32_t)(mc >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mc, 0u))
-                                             : nc + __builtin_amdgcn_mbcnt_hi((uint32_t)(mo >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mo, 0u));
-                ao_ray_store(ldsw, slot, a, col | (c0 << 8));
-            }
-            next = 0u;
-            trace_ao_pool<kCnt>(s.vol, lane, ldsw, nc + (uint32_t)__builtin_popcountll(mo), i + 1u < st.ao_samples ? 1u : 0u, next, st.ao_steps, looks);
-        }
-        if (active) {
-            ao_hits = cnt[0] + direct_hits;
-            c.rays += st.ao_samples;
-        }
-        // (look-ups are counted by the lane that makes them, iterations for the pixel the ray belongs to)
-        if (kCnt) c.fetches += s.vol.count_lookups != 0u ? looks : (active ? cnt[64] + direct_fet : 0u);
-        // calcAmbient's sum (frag:219-222): one addition of 1 / aoSamples per ray that hit -- the value depends on their number only
-        float sample_frac = 1.0f / (float)st.ao_samples;
-        for (uint32_t q = 0; q < ao_hits; q++) ambient += sample_frac;
-    } else if ((TRAV == VRT_TRAVERSAL_BRICK || TRAV == VRT_TRAVERSAL_BRICK_CNT) && __builtin_amdgcn_readfirstlane((int)s.vol.ao_batch) != 0) {
-        // brick scenes: the same pool in the generic loop (brick_ao_pool)
-        constexpr bool kCnt = TRAV == VRT_TRAVERSAL_BRICK_CNT;
-        const uint32_t ldsw = c.ldsw;
-        const uint64_t act = __ballot(active);
-        const uint32_t col = __builtin_amdgcn_mbcnt_hi((uint32_t)(act >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)act, 0u));
-        __attribute__((address_space(3))) uint32_t* cnt = (__attribute__((address_space(3))) uint32_t*)(uintptr_t)(ldsw + 3328u + col * 4u);
-        if (active) { cnt[0] = 0u; if (kCnt) cnt[64] = 0u; }
-        BrickAoLane lane;
-        brick_ao_rest(lane);
-        uint32_t next = 0u, looks = 0u, direct_hits = 0u, direct_fet = 0u;
-        for (uint32_t i = 0; i < st.ao_samples; i++) {
-            // (the owner looks at its ray's first voxel itself, as on dense scenes: rays in the open, rays on a 0 byte and rays that never
-            // enter the volume are decided here; the rays that will creep wait in front of the pool)
-            bool store = false;
-            uint32_t c0 = 0u;
-            DdaState rs; float gx = 0.0f, gy = 0.0f, gz = 0.0f;
-            if (active) {
-                f3 rd = random_dir(s, *c.pc, c, i + depth * st.ao_samples);
-                f3 dir = mk3(normal.x + rd.x, normal.y + rd.y, normal.z + rd.z);
-                f3 o = mk3(pos.x + dir.x * 0.01f, pos.y + dir.y * 0.01f, pos.z + dir.z * 0.01f);
-                brick_ao_setup(s.vol, o, dir, rs, gx, gy, gz);
-                if (!oob(s.vol, rs.mx, rs.my, rs.mz)) {          // (else: starts outside and misses the volume: leaves in iteration 0, no fetch)
-                    const uint32_t oct = (uint32_t)(rs.sx > 0) | ((uint32_t)(rs.sy > 0) << 1) | ((uint32_t)(rs.sz > 0) << 2);
-                    uint32_t m = 0u;
-                    c0 = brick_clear(s.vol, rs.mx, rs.my, rs.mz, oct, rs.sx, rs.sy, rs.sz, m, kCnt ? &looks : nullptr);
-                    if (c0 == 0u) { if (m != 0u) direct_hits++; if (kCnt) direct_fet += m != 0u ? 1u : 0u; }
-                    else if (c0 >= st.ao_steps) { if (kCnt) direct_fet += s.vol.count_marched != 0u ? 0u : st.ao_steps; }
-                    else store = true;
-                }
-            }
-            const bool creeps = store && c0 <= 2u;
-            const uint64_t mc = __ballot(creeps), mo = __ballot(store && !creeps);
-            const uint32_t nc = (uint32_t)__builtin_popcountll(mc);
-            if (store) {
-                const uint32_t slot = creeps ? __builtin_amdgcn_mbcnt_hi((uint32_t)(mc >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mc, 0u))
-                                             : nc + __builtin_amdgcn_mbcnt_hi((uint32_t)(mo >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mo, 0u));
-                brick_ao_store(ldsw, slot, rs, gx, gy, gz, col | (c0 << 8));
-            }
-            next = 0u;
-            brick_ao_pool<kCnt>(s.vol, lane, ldsw, nc + (uint32_t)__builtin_popcountll(mo), i + 1u < st.ao_samples, next, st.ao_steps, looks);
-        }
-        if (active) {
-            ao_hits = cnt[0] + direct_hits;
-            c.rays += st.ao_samples;
-        }
-        if (kCnt) c.fetches += s.vol.count_lookups != 0u ? looks : (active ? cnt[64] + direct_fet : 0u);
-        float sample_frac = 1.0f / (float)st.ao_samples;
-        for (uint32_t q = 0; q < ao_hits; q++) ambient += sample_frac;
-    } else if (active) {
-        float sample_frac = 1.0f / (float)st.ao_samples;
-        for (uint32_t i = 0; i < st.ao_samples; i++) {
-            f3 rd = random_dir(s, *c.pc, c, i + depth * st.ao_samples);
-            f3 dir = mk3(normal.x + rd.x, normal.y + rd.y, normal.z + rd.z);
-            f3 o = mk3(pos.x + dir.x * 0.01f, pos.y + dir.y * 0.01f, pos.z + dir.z * 0.01f);
-            RayInt r;
-            // AO rays have a 64-iteration budget: too short for jumps to pay, and budget ties would force re-traces
-            // (the hand-written loop's kernels: every lane its own clearance is the batched path above; here the wave's smallest)
-            trace_int<((TRAV == VRT_TRAVERSAL_JUMP || TRAV == VRT_TRAVERSAL_DFJ) ? VRT_TRAVERSAL_DF : TRAV), decltype(occ.o2), false, true, false, !kBatch>(s.vol, occ.o2, occ.o3, o, dir, st.ao_steps, r);   // (no prefetch: AO rays point every way, three gathers instead of one measured +18 %)
-            if (VRT_COUNTS(TRAV)) c.fetches += r.fetches;
-            c.rays++;
-            if (r.material != 0) { ambient += sample_frac; ao_hits++; }
-        }
-    }
-    shadowed = false;
-    if (SEC && st.shadows && active) {
-        f3 L = mk3(st.light_dir[0], st.light_dir[1], st.light_dir[2]);
-        f3 o = mk3(pos.x + normal.x * 0.01f, pos.y + normal.y * 0.01f, pos.z + normal.z * 0.01f);
-        RayInt r;
-        trace_int<TRAV, decltype(occ.o2), false, true, true>(s.vol, occ.o2, occ.o3, o, L, st.max_steps, r);      // traceRayHit: only "did it hit" is used
-        if (VRT_COUNTS(TRAV)) c.fetches += r.fetches;
-        c.rays++;
-        shadowed = r.material != 0;
-    }
-}
-
-// color() of a hit (frag:236-248) and colorHit's division by depth + 1 (frag:258).  `sky` = skyColor(normal).
-__device__ __forceinline__ f3 shade_eval(const GeomParams& P, uint32_t material, const f3 normal, const f3 sky, float ambient, bool shadowed,
-                                         f3 reflection, uint32_t depth)
-{
-    const vrt_settings& st = P.st;
-    float k = ambient * st.ambient_intensity;
-    f3 amb = mk3(k * sky.x, k * sky.y, k * sky.z);
-    f3 L = mk3(st.light_dir[0], st.light_dir[1], st.light_dir[2]);
-    f3 diffuse = mk3(0.0f, 0.0f, 0.0f);
-    if (!shadowed) {
-        float diff = fmaxf(dot3(normal, L), 0.0f);
-        diffuse = mk3((diff * st.light_color[0]) * st.light_intensity,
-                      (diff * st.light_color[1]) * st.light_intensity,
-                      (diff * st.light_color[2]) * st.light_intensity);
-    }
-    const vrt_material mat = P.sc.palette[material];
-    float inv = (float)(depth + 1);
-    f3 out;
-    out.x = ((((diffuse.x + reflection.x * mat.metallic) + amb.x) * mat.diffuse[0]) * 1.0f) / inv;
-    out.y = ((((diffuse.y + reflection.y * mat.metallic) + amb.y) * mat.diffuse[1]) * 1.0f) / inv;
-    out.z = ((((diffuse.z + reflection.z * mat.metallic) + amb.z) * mat.diffuse[2]) * 1.0f) / inv;
-    return out;
-}
-
-// active = false: the lane has nothing to shade and is here for the others' AO rays (secondary_rays); its result is not used
-template <int TRAV, class Occ, bool SEC = true>
-__device__ f3 color_hit(const GeomParams& P, const Occ occ, PixCtx& c, const RayHit& hit,
-                        f3 reflection, uint32_t depth, const bool active = true)
-{
-    const DevScene& s = P.sc;
-    float ambient; uint32_t ao_hits; bool shadowed;
-    secondary_rays<TRAV, Occ, SEC>(P, occ, c, hit.pos, hit.normal, depth, ambient, ao_hits, shadowed, active && hit.material != 0);
-    if (!active) return mk3(0.0f, 0.0f, 0.0f);
-    if (hit.material == 0) return sky_color(s, hit.dir);
-    // skyColor(hit.normal): the normal is one of 26 vectors, whose sky texels the scene holds in a table (computed by this very
-    // function, k_sky_normals); any other normal is looked up here
-    f3 sky;
-#if defined(VRT_NO_SKY_TABLE)
-    if (false) {
-#else
-    if (__ballot(hit.ncode == 0xFFFFFFFFu) == 0ull) {
-#endif
-        const float4 t = reinterpret_cast<const float4*>(s.sky_normals)[hit.ncode];
-        sky = mk3(t.x, t.y, t.z);
-    } else sky = sky_color(s, hit.normal);
-    return shade_eval(P, hit.material, hit.normal, sky, ambient, shadowed, reflection, depth);
-}
-
-// colorMainRay, voxel_volume.frag:267-307
-// BOUNCE = false: the host has established that no ray of the frame can bounce (max_bounces == 0, or no voxel of the scene has
-// a metallic material): the loop and its stack of hits -- 352 bytes of scratch per lane, which every wave of the kernel is
-// given whether it bounces or not -- are compiled out
-template <int TRAV, class Occ, bool BOUNCE = true>
-__device__ f3 color_main_ray(const GeomParams& P, const Occ occ, PixCtx& c, const RayHit& hit, const bool active = true)
-{
-    const DevScene& s = P.sc;
-    const vrt_settings& st = P.st;
-    f3 reflection = mk3(0.0f, 0.0f, 0.0f);
-    if (BOUNCE && active && s.palette[hit.material].metallic > 0.0f && st.max_bounces > 0) {
-        RayHit bounces[VRT_MAX_BOUNCES];
-        RayHit last = hit;
-        int last_idx = -1;
-        int nb = st.max_bounces > VRT_MAX_BOUNCES ? VRT_MAX_BOUNCES : (int)st.max_bounces;
-        for (int i = 0; i < nb; i++) {
-            float k = 2.0f * dot3(last.normal, last.dir);
-            f3 rdir = mk3(last.dir.x - k * last.normal.x, last.dir.y - k * last.normal.y, last.dir.z - k * last.normal.z);
-            f3 o = mk3(last.pos.x + last.normal.x * 0.01f, last.pos.y + last.normal.y * 0.01f, last.pos.z + last.normal.z * 0.01f);
-            RayHit rh; RayInt ri;
-            trace_ray<TRAV, Occ, false, true>(s, occ, o, rdir, st.max_steps, rh, ri);
-            if (VRT_COUNTS(TRAV)) c.fetches += ri.fetches;
-            c.rays++;
-            bounces[i] = rh;
-            last = rh;
-            if (last.material == 0 || s.palette[last.material].metallic <= 0.0f) { last_idx = i; break; }
-        }
-        for (int i = last_idx; i >= 0; i--) {
-            f3 col = color_hit<TRAV>(P, occ, c, bounces[i], reflection, (uint32_t)i);
-            reflection = mk3(reflection.x + col.x, reflection.y + col.y, reflection.z + col.z);
-        }
-    }
-    return color_hit<TRAV>(P, occ, c, hit, reflection, 0, active);        // (wave-uniform again: the lanes without a hit help with the AO rays)
-}
-
-// colorMainRay with the bounce chain as ONE WORD per hit instead of a stack of RayHits (44 B each: 352 B of scratch per lane for
-// every wave of the launch, and 0.6 GB of scratch writes per 4K frame on the Mandelbulb).  What the way back needs of a hit on the
-// chain is what color() consumes: its material, which of the 27 normals it has (26 face / edge / corner vectors or the zero
-// vector of rule A: every normal traceRay can produce, hit_normal), how many of its AO rays hit and whether its shadow ray did --
-// 8 + 6 + 16 + 1 bits.  So the secondary rays of every hit are traced on the way OUT, where the hit is at hand, at one call
-// site for the primary hit and every bounce; the way back is arithmetic on the words, in the order frag:300-303 prescribes.
-// The secondary rays of a METALLIC bounce are traced before it is known whether the chain will end (frag:281-298: a chain of
-// max_bounces metallic hits shades none of them, lastIdx = -1): in that one case they were traced for nothing, and their rays
-// and steps are taken out of the count planes again, which then hold the reference's numbers as before.
-// Entry k of the chain: k = 0 the primary hit, k = i + 1 bounce i (shaded with depth i; the primary with depth 0).
-__device__ __forceinline__ uint32_t chain_pack(uint32_t material, const f3 n, uint32_t ao_hits, bool shadowed)
-{
-    // the normal's code from the vector itself: bit a = component a is not 0, bit 3 + a = it is positive (hit_normal's ncode: the
-    // component is -rayStep); a masked axis the ray does not move along has a zero component and drops out of the mask, which is
-    // the same vector hit_normal's general form returns
-    const uint32_t nc = (uint32_t)(n.x != 0.0f) | ((uint32_t)(n.y != 0.0f) << 1) | ((uint32_t)(n.z != 0.0f) << 2) |
-                        ((uint32_t)(n.x > 0.0f) << 3) | ((uint32_t)(n.y > 0.0f) << 4) | ((uint32_t)(n.z > 0.0f) << 5);
-    return material | (nc << 8) | ((uint32_t)shadowed << 14) | (ao_hits << 16);
-}
-__device__ __forceinline__ f3 chain_shade(const GeomParams& P, uint32_t code, f3 reflection, uint32_t depth)
-{
-    const DevScene& s = P.sc;
-    const uint32_t nc = (code >> 8) & 63u, hits = code >> 16;
-    const f3 normal = hit_normal(nc & 7u, (nc & 8u) ? -1 : 1, (nc & 16u) ? -1 : 1, (nc & 32u) ? -1 : 1);
-    f3 sky;
-    if ((nc & 7u) != 0u) { const float4 t = reinterpret_cast<const float4*>(s.sky_normals)[nc]; sky = mk3(t.x, t.y, t.z); }
-    else sky = sky_color(s, normal);                         // the zero normal of rule A
-    // calcAmbient's sum: `hits` additions of 1 / ao_samples (frag:219-222), not a product
-    float ambient = 1.0f;
-    if (P.st.ao_samples != 0u) {
-        const float sample_frac = 1.0f / (float)P.st.ao_samples;
-        ambient = 0.0f;
-        for (uint32_t q = 0; q < hits; q++) ambient += sample_frac;
-    }
-    return shade_eval(P, code & 0xFFu, normal, sky, ambient, ((code >> 14) & 1u) != 0u, reflection, depth);
-}
-
-// NBT: the most bounces the launch can ask for (the chain's words are registers: 2, 5 or VRT_MAX_BOUNCES + 1 of them)
-template <int TRAV, class Occ, int NBT>
-__device__ f3 color_main_ray_packed(const GeomParams& P, const Occ occ, PixCtx& c, const RayHit& hit, const bool is_hit = true)
-{
-    const DevScene& s = P.sc;
-    const vrt_settings& st = P.st;
-    const int nb = st.max_bounces > NBT ? NBT : (int)st.max_bounces;
-    uint32_t codes[NBT + 1];
-#pragma unroll
-    for (int q = 0; q <= NBT; q++) codes[q] = 0u;
-    f3 reflection = mk3(0.0f, 0.0f, 0.0f);
-    RayHit cur = hit;
-    int last = 0;                                              // the chain's last entry that is shaded: 0 = the primary hit alone
-    uint32_t spec_fetches = 0u, spec_rays = 0u;
-    // The loop over the chain's entries is WAVE-UNIFORM: a lane whose chain has ended (or that never had a hit) stays in it for as long
-    // as some lane's chain goes on, and takes AO rays from the pool like the others (secondary_rays) -- the few metallic pixels of a
-    // bounce get the whole wave's help.  Everything else a lane does here is under `on`: its own chain is still being followed.
-    bool on = is_hit;
-    for (int k = 0; __ballot(on) != 0ull; k++) {
-        // the secondary rays of entry k (a hit: the primary, or a bounce that found something)
-        float ambient; uint32_t ao_hits; bool shadowed;
-        const uint32_t f0 = c.fetches, r0 = c.rays;
-        secondary_rays<TRAV, Occ, true>(P, occ, c, cur.pos, cur.normal, k > 0 ? (uint32_t)(k - 1) : 0u, ambient, ao_hits, shadowed, on);
-        if (on) {
-            codes[k] = chain_pack(cur.material, cur.normal, ao_hits, shadowed);
-            last = k;
-            const bool metal = s.palette[cur.material].metallic > 0.0f;
-            if (!metal) on = false;                            // (k = 0: no chain at all; k > 0: the chain ends on a hit that does not reflect)
-            else {
-                if (k > 0) { if (VRT_COUNTS(TRAV)) spec_fetches += c.fetches - f0; spec_rays += c.rays - r0; }    // a metallic bounce: shaded only if the chain ends
-                if (k >= nb) { last = -1; on = false; }        // max_bounces metallic bounces (or max_bounces == 0): nothing on the chain is shaded
-            }
-        }
-        if (on) {
-            float d2 = 2.0f * dot3(cur.normal, cur.dir);
-            f3 rdir = mk3(cur.dir.x - d2 * cur.normal.x, cur.dir.y - d2 * cur.normal.y, cur.dir.z - d2 * cur.normal.z);
-            f3 o = mk3(cur.pos.x + cur.normal.x * 0.01f, cur.pos.y + cur.normal.y * 0.01f, cur.pos.z + cur.normal.z * 0.01f);
-            RayHit rh; RayInt ri;
-            trace_ray<TRAV, Occ, false, true>(s, occ, o, rdir, st.max_steps, rh, ri);
-            if (VRT_COUNTS(TRAV)) c.fetches += ri.fetches;
-            c.rays++;
-            if (rh.material == 0u) {                           // the chain ends in the sky: colorHit of a miss is skyColor(dir)
-                const f3 col = sky_color(s, rh.dir);
-                reflection = mk3(reflection.x + col.x, reflection.y + col.y, reflection.z + col.z);
-                on = false;
-            } else cur = rh;
-        }
-    }
-    if (!is_hit) return mk3(0.0f, 0.0f, 0.0f);
-    if (last < 0) {
-        // frag:281-303 with lastIdx = -1: the bounces' secondary rays were traced for nothing -- the reference never traces them
-        if (VRT_COUNTS(TRAV)) c.fetches -= spec_fetches;
-        c.rays -= spec_rays;
-        last = 0;
-    }
-    // the way back: entry j (bounce j - 1) with the reflection gathered behind it, frag:300-303
-#pragma unroll
-    for (int j = NBT; j >= 1; j--) {
-        if (j <= last) {
-            const f3 col = chain_shade(P, codes[j], reflection, (uint32_t)(j - 1));
-            reflection = mk3(reflection.x + col.x, reflection.y + col.y, reflection.z + col.z);
-        }
-    }
-    return chain_shade(P, codes[0], reflection, 0u);
-}
-
-// ---------------------------------------------------------------------------------------------
-// tile mapping
-// ---------------------------------------------------------------------------------------------
-
-// Workgroup -> screen tile.  Workgroups are dealt round-robin over the 8 XCDs (b and b+8 share an
-// XCD and its private 4 MiB L2), so XCD slot (b % 8) gets one contiguous run of `chunk` tiles in
-// row-major tile order: neighbouring tiles traverse neighbouring volume cells and share L2 lines.
-// n / d for wave-uniform operands with rcp = floor(2^32 / d): mulhi is the quotient or one below it, one correction
-// step makes it exact for every n < 2^32.  Stays on the scalar unit (a generic 32-bit division is ~20 VALU ops).
-__device__ __forceinline__ uint32_t udiv_uniform(uint32_t n, uint32_t d, uint32_t rcp, uint32_t& rem)
-{
-    uint32_t q = (uint32_t)(((uint64_t)n * (uint64_t)rcp) >> 32);
-    uint32_t r = n - q * d;
-    if (r >= d) { q++; r -= d; }
-    rem = r;
-    return q;
-}
-
-// The slot (camera, planes, strip assignment) of frame `frame` of the launch.  TABLE = false: a reference into the kernel
-// arguments.  TABLE = true (launches of more than VRT_MAX_BATCH frames): a copy read from the table in device memory
-// through the constant address space -- the table is not written while the kernel runs, and only loads the compiler
-// knows to be invariant become scalar loads (a plain global pointer gives vector loads and the slot in VGPRs).
-typedef const __attribute__((address_space(4))) uint32_t* const_u32_ptr;
-// n dwords starting at byte offset `off` of slot `frame` of the table, read through the constant address space
-template <int N> __device__ __forceinline__ void table_read(const GeomParams& P, uint32_t frame, size_t off, void* dst)
-{
-    const_u32_ptr w = (const_u32_ptr)((const char*)(P.table + frame) + off);
-    uint32_t tmp[N];
-#pragma unroll
-    for (int i = 0; i < N; i++) tmp[i] = w[i];
-    __builtin_memcpy(dst, tmp, sizeof tmp);
-}
-// The kernel's own arguments (GeomParams is the one argument, at offset 0 of the segment) as words to be read NOW: the
-// compiler hoists ordinary argument loads to the top of the kernel, where each costs scalar registers across ray generation;
-// what only a rare or late branch needs is read through this pointer, which it cannot see through.
-__device__ __forceinline__ const_u32_ptr kernarg_words(size_t byte_offset)
-{
-    const_u32_ptr p = (const_u32_ptr)((const __attribute__((address_space(4))) char*)__builtin_amdgcn_kernarg_segment_ptr() + byte_offset);
-    asm volatile("" : "+s"(p));
-    return p;
-}
-// base + 32-bit byte offset as a pointer into GLOBAL memory (address space 1): global_load / global_store with the base in a
-// scalar pair and the offset in one vector register
-template <class T> __device__ __forceinline__ __attribute__((address_space(1))) T* gptr(const void* base, uint32_t byte_offset)
-{
-    return (__attribute__((address_space(1))) T*)((__attribute__((address_space(1))) char*)base + byte_offset);
-}
-typedef float vrt_f4 __attribute__((ext_vector_type(4)));
-typedef float vrt_f2 __attribute__((ext_vector_type(2)));
-// the planes a miss pixel is stored to (the fast sky wave reads these eight pointers, not all fourteen)
-struct MissPlanes { uint8_t* color8; float* depth; float* motion; uint8_t* mask8; float* position; int8_t* normal8; uint8_t* hit_id; uint8_t* color8_strips; };
-template <bool TABLE> struct SlotOf;
-template <> struct SlotOf<false> {
-    static __device__ __forceinline__ void head(const GeomParams& P, uint32_t frame, RayGenConsts& g, float* cam_right, int& shard_rank, uint32_t& box)
-    {
-        const FrameSlot& S = P.slot[frame];
-        box = (uint32_t)S.box[0] | ((uint32_t)S.box[1] << 8) | ((uint32_t)S.box[2] << 16) | ((uint32_t)S.box[3] << 24);
-        g = S.rg;
-        cam_right[0] = S.pc.cam_right[0]; cam_right[1] = S.pc.cam_right[1]; cam_right[2] = S.pc.cam_right[2];
-        shard_rank = S.shard_rank;
-    }
-    static __device__ __forceinline__ vrt_frame planes(const GeomParams& P, uint32_t frame) { return P.slot[frame].fr; }
-    // the camera position: only waves that trace need it, and they read it when they know they do (three scalar registers
-    // less across ray generation for everybody)
-    static __device__ __forceinline__ f3 cam_pos(const GeomParams& P, uint32_t frame)
-    {
-        const_u32_ptr w = kernarg_words(offsetof(GeomParams, slot) + (size_t)frame * sizeof(FrameSlot) + offsetof(FrameSlot, pc) + offsetof(vrt_push, cam_pos));
-        return mk3(__uint_as_float(w[0]), __uint_as_float(w[1]), __uint_as_float(w[2]));
-    }
-    // N plane pointers of the frame starting with field `first` of vrt_frame, read NOW (kernarg_words)
-    template <int N> static __device__ __forceinline__ void ptrs(const GeomParams& P, uint32_t frame, int first, void** out)
-    {
-        const_u32_ptr fp = kernarg_words(offsetof(GeomParams, slot) + (size_t)frame * sizeof(FrameSlot) + offsetof(FrameSlot, fr) + 8u * (size_t)first);
-        uint32_t tmp[2 * N];
-#pragma unroll
-        for (int q = 0; q < 2 * N; q++) tmp[q] = fp[q];
-        __builtin_memcpy(out, tmp, sizeof tmp);
-    }
-    static __device__ __forceinline__ MissPlanes miss_planes(const GeomParams& P, uint32_t frame)
-    {
-        // (read late, like the fast path's other constants: through a pointer into the arguments the compiler cannot hoist from)
-        const_u32_ptr fp = kernarg_words(offsetof(GeomParams, slot) + (size_t)frame * sizeof(FrameSlot) + offsetof(FrameSlot, fr));
-        MissPlanes m;
-        uint32_t tmp[16];
-#pragma unroll
-        for (int q = 0; q < 12; q++) tmp[q] = fp[q];
-        tmp[12] = fp[14]; tmp[13] = fp[15]; tmp[14] = fp[26]; tmp[15] = fp[27];
-        __builtin_memcpy(&m, tmp, sizeof m);
-        return m;
-    }
-    static __device__ __forceinline__ const vrt_push* push(const GeomParams& P, uint32_t frame) { return &P.slot[frame].pc; }
-};
-// The table form reads the pieces when they are needed, like the kernel-argument form does: a copy of the whole slot at the
-// top keeps the fourteen plane pointers in scalar registers through the traversal (82 + 6 SGPRs: one wave per SIMD less).
-template <> struct SlotOf<true> {
-    static __device__ __forceinline__ void head(const GeomParams& P, uint32_t frame, RayGenConsts& g, float* cam_right, int& shard_rank, uint32_t& box)
-    {
-        table_read<1>(P, frame, offsetof(FrameSlot, box), &box);
-        table_read<sizeof(RayGenConsts) / 4>(P, frame, offsetof(FrameSlot, rg), &g);
-        table_read<3>(P, frame, offsetof(FrameSlot, pc) + offsetof(vrt_push, cam_right), cam_right);
-        table_read<1>(P, frame, offsetof(FrameSlot, shard_rank), &shard_rank);
-    }
-    static __device__ __forceinline__ vrt_frame planes(const GeomParams& P, uint32_t frame)
-    {
-        vrt_frame f;
-        table_read<sizeof(vrt_frame) / 4>(P, frame, offsetof(FrameSlot, fr), &f);
-        return f;
-    }
-    static __device__ __forceinline__ f3 cam_pos(const GeomParams& P, uint32_t frame)
-    {
-        const_u32_ptr w = (const_u32_ptr)((const char*)(P.table + frame) + offsetof(FrameSlot, pc) + offsetof(vrt_push, cam_pos));
-        asm volatile("" : "+s"(w));
-        return mk3(__uint_as_float(w[0]), __uint_as_float(w[1]), __uint_as_float(w[2]));
-    }
-    template <int N> static __device__ __forceinline__ void ptrs(const GeomParams& P, uint32_t frame, int first, void** out)
-    {
-        const_u32_ptr w = (const_u32_ptr)((const char*)(P.table + frame) + offsetof(FrameSlot, fr) + 8u * (size_t)first);
-        asm volatile("" : "+s"(w));                            // (read NOW: not hoisted to where the slot's head is read)
-        uint32_t tmp[2 * N];
-#pragma unroll
-        for (int q = 0; q < 2 * N; q++) tmp[q] = w[q];
-        __builtin_memcpy(out, tmp, sizeof tmp);
-    }
-    static __device__ __forceinline__ MissPlanes miss_planes(const GeomParams& P, uint32_t frame)
-    {
-        // color8 .. normal8 are the first six pointers of vrt_frame, hit_id the eighth, color8_strips the fourteenth
-        static_assert(offsetof(vrt_frame, normal8) == 40 && offsetof(vrt_frame, hit_id) == 56 && offsetof(vrt_frame, color8_strips) == 104, "vrt_frame layout");
-        MissPlanes m;
-        table_read<12>(P, frame, offsetof(FrameSlot, fr), &m);
-        table_read<2>(P, frame, offsetof(FrameSlot, fr) + offsetof(vrt_frame, hit_id), &m.hit_id);
-        table_read<2>(P, frame, offsetof(FrameSlot, fr) + offsetof(vrt_frame, color8_strips), &m.color8_strips);
-        return m;
-    }
-    static __device__ __forceinline__ const vrt_push* push(const GeomParams& P, uint32_t frame) { return &P.table[frame].pc; }
-};
-
-// workgroup -> frame of the launch and tile row within the frame's local rows (ty) and tile column (tx).  Frames of a
-// batch follow one another in the grid: the next frame's first tiles start while this one drains.
-// XCD x (= workgroup id & 7) owns every 8th tile row: every XCD gets an even sample of sky and geometry (a contiguous
-// band per XCD leaves the XCDs that drew the sky idle), while the tiles of one row -- which walk neighbouring volume cells
-// -- still share that XCD's L2.
-//   xcd_turn == 0: per frame, row ty belongs to XCD ty % 8; ceil(rows / 8) * 8 row slots per frame (the surplus
-//                  workgroups exit at once).
-//   xcd_turn == 1: the rows of ALL frames of the launch are dealt round-robin in one sequence (row L = frame * rows + ty
-//                  to XCD L % 8).  For row counts far from a multiple of 8 -- a rank's 18 rows of a sharded 1080p frame
-//                  would be 3 rows for two XCDs and 2 for the others, and a third of the grid would be surplus -- the XCDs
-//                  stay even and only the last seven row slots of the launch can be empty.
-// MAP: the launch's xcd_turn as a compile-time constant (the product traversals), or -1: looked at here
-template <int MAP>
-__device__ __forceinline__ bool block_to_tile(const TileMap& M, uint32_t& frame, int& ty, int& tx)
-{
-    // xcd_turn 0 and 2 are launched as THREE-dimensional grids (8 x columns, rows, frames): the workgroup's three indices are in
-    // scalar registers when the wave starts, and the XCD (workgroups are dealt to the eight XCDs in dispatch order, x fastest)
-    // is the low three bits of the x index because the grid's x extent is a multiple of 8 -- no division, where the linear
-    // form spends two or three (ten scalar instructions each, in a kernel whose scalar unit -- ONE per CU, shared by its four
-    // SIMDs -- is as busy as its vector units: a 1080p frame of sky-only waves that return once they know their block takes
-    // 11 us, 158 scalar instructions per wave).
-    if (MAP == 2 || (MAP < 0 && M.xcd_turn == 2)) {
-        // per frame every XCD owns ONE of 8 screen regions (2 columns x 4 rows of tiles), and the assignment rotates from frame
-        // to frame (XCD x traces region (x + frame) % 8): an XCD's rays of one frame then walk one eighth of the volume in one
-        // or two direction octants -- a working set of clearance bytes that fits its 4 MiB L2 instead of the whole 17 MB field
-        // -- while over 8 frames every XCD traces every region once, so sky and geometry regions balance.
-        const uint32_t rw = ((uint32_t)M.tiles_x + 1u) >> 1, rh = ((uint32_t)M.tiles_y_local + 3u) >> 2;
-        frame = blockIdx.z;
-        const uint32_t region = ((blockIdx.x & 7u) + frame) & 7u;
-        tx = (int)((blockIdx.x >> 3) + (region & 1u) * rw);
-        ty = (int)(blockIdx.y + (region >> 1) * rh);
-        return tx < M.tiles_x && ty < M.tiles_y_local;
-    }
-    if (MAP == 0 || (MAP < 0 && M.xcd_turn == 0)) {
-        // per frame, row ty belongs to XCD ty % 8: every XCD gets an even sample of sky and geometry (a contiguous band per XCD
-        // leaves the XCDs that drew the sky idle), while the tiles of one row -- which walk neighbouring volume cells -- still
-        // share that XCD's L2; ceil(rows / 8) * 8 row slots per frame (the surplus workgroups exit at once)
-        frame = blockIdx.z;
-        tx = (int)(blockIdx.x >> 3);
-        ty = (int)(blockIdx.y * 8u + (blockIdx.x & 7u));
-        return ty < M.tiles_y_local;
-    }
-    // xcd_turn == 1 (a one-dimensional grid): the rows of ALL frames of the launch are dealt round-robin in one sequence (row
-    // L = frame * rows + ty to XCD L % 8).  For row counts far from a multiple of 8 -- a rank's 18 rows of a sharded 1080p
-    // frame would be 3 rows for two XCDs and 2 for the others, and a third of the grid would be surplus -- the XCDs stay even
-    // and only the last seven row slots of the launch can be empty.
-    uint32_t b = blockIdx.x, utx, uty;
-    uint32_t L = udiv_uniform(b >> 3, (uint32_t)M.tiles_x, M.tiles_x_rcp, utx) * 8u + (b & 7u);
-    frame = udiv_uniform(L, (uint32_t)M.tiles_y_local, M.tiles_y_rcp, uty);
-    ty = (int)uty; tx = (int)utx;
-    return frame < (uint32_t)M.n_frames;
-}
-
-// yp0: the row of y0 in the rank's packed strips (vrt_pack_rows order)
-__device__ __forceinline__ bool tile_origin(const TileMap& M, int ty, int tx, int shard_rank, int& x0, int& y0, int& yp0)
-{
-    // bottom rows first: the rows dispatched last only have the drain of the machine to hide in, and the top of a
-    // frame is where the cheap sky-only tiles usually are
-    ty = M.tiles_y_local - 1 - ty;
-    uint32_t within = (uint32_t)ty;
-    int strip_local = 0;                                       // (unsharded: the frame is one strip)
-    if (M.nranks > 1) strip_local = (int)udiv_uniform((uint32_t)ty, M.tps, M.tps_rcp, within);
-    x0 = tx * M.tile;
-    yp0 = strip_local * M.strip_rows + (int)within * M.tile;
-    y0 = (strip_local * M.nranks + shard_rank) * M.strip_rows + (int)within * M.tile;
-    return y0 < M.H;
-}
-
-// Stage the 16^3 and 64^3 occupancy summaries into LDS (16 B per lane per iteration, coalesced).
-template <bool LDS> __device__ __forceinline__ OccT<LDS> stage_occ(const GeomParams& P, uint64_t* lds);
-template <> __device__ __forceinline__ OccT<false> stage_occ<false>(const GeomParams& P, uint64_t*)
-{
-    OccT<false> o; o.o2 = P.sc.vol.occ2; o.o3 = P.sc.vol.occ3; return o;
-}
-template <> __device__ __forceinline__ OccT<true> stage_occ<true>(const GeomParams& P, uint64_t* lds)
-{
-    const uint4* src2 = reinterpret_cast<const uint4*>(P.sc.vol.occ2);
-    const uint4* src3 = reinterpret_cast<const uint4*>(P.sc.vol.occ3);
-    uint4* dst = reinterpret_cast<uint4*>(lds);
-    uint32_t n2 = P.occ2_bytes / 16, n3 = P.occ3_bytes / 16;
-    for (uint32_t i = threadIdx.x; i < n2; i += blockDim.x) dst[i] = src2[i];
-    for (uint32_t i = threadIdx.x; i < n3; i += blockDim.x) dst[n2 + i] = src3[i];
-    __syncthreads();
-    OccT<true> o;
-    o.o2 = (lds_u64_ptr)lds; o.o3 = (lds_u64_ptr)(lds + P.occ2_bytes / 8);
-    return o;
-}
-
-// ---------------------------------------------------------------------------------------------
 // K1: primary rays
 // ---------------------------------------------------------------------------------------------
-
-// the pixel's colour into color_f (debug), color8 and the packed strips
-__device__ __forceinline__ void store_color(const vrt_frame& f, f3 col, size_t i, uint32_t i32, uint32_t strip_off)
-{
-    if (f.color_f) { f.color_f[i * 3 + 0] = col.x; f.color_f[i * 3 + 1] = col.y; f.color_f[i * 3 + 2] = col.z; }
-    if (f.color8 || f.color8_strips) {
-        const uint32_t c8 = (uint32_t)unorm8(col.x) | ((uint32_t)unorm8(col.y) << 8) | ((uint32_t)unorm8(col.z) << 16);
-        if (f.color8) *gptr<uint32_t>(f.color8, i32 << 2) = c8;
-        if (f.color8_strips) *gptr<uint32_t>(f.color8_strips, strip_off) = c8;
-    }
-}
 
 // MODE 0: write hit records for K2 (split);  1: no secondary rays enabled, shade inline;  4: the megakernel without its bounce loop;
 // MODE 5, 6, 7: the megakernel with the bounce chain as one word per hit (color_main_ray_packed: no stack of hits; what the product
@@ -721,23 +33,15 @@ __device__ __forceinline__ void store_color(const vrt_frame& f, f3 col, size_t i
 // MODE 2: megakernel -- the lanes that hit go on to trace their AO / shadow / bounce rays in this same kernel, so that
 //         the secondary rays' latency hides under the primary work of the other waves (a separate K2 launch has a
 //         single round of waves and is bound by the longest ray's dependency chain).
-#ifndef VRT_CHAIN_WAVES
-#define VRT_CHAIN_WAVES 7     // (development: the packed-chain megakernels at 6 or 5 waves per SIMD, i.e. 80 / 96 VGPRs)
-#endif
-#ifndef VRT_MODE4_WAVES
-#define VRT_MODE4_WAVES 7     // (development: 8 forces the megakernel without its bounce loop into 64 VGPRs, at the price of 12 B of scratch per lane)
-#endif
+// At least 7 waves per SIMD for every MODE: the packed-chain megakernels measured 1 075 us at 7 (72 VGPRs, spilling), 1 148 at 6 and 1 165 at 5
+// (Mandelbulb 4K); forcing the megakernel without its bounce loop to 8 (64 VGPRs) costs 12 B of scratch per lane.
 template <int TRAV, bool OCC_LDS, int MODE, bool TABLE, int MAP>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(((MODE == 4 && TRAV == VRT_TRAVERSAL_DF_FAST) ? VRT_MODE4_WAVES : (MODE >= 5 ? VRT_CHAIN_WAVES : 7)), 8))) void k_primary(const GeomParams P)
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 8))) void k_primary(const GeomParams P)
 {
     extern __shared__ __attribute__((aligned(16))) uint64_t lds_occ[];
     // the tile map arrives with one 64-byte scalar load (and one wait) before anything depends on it
     TileMap M = P.map;
-#ifdef VRT_EXP_STAMPS
-    const uint64_t t_begin = wall_clock64();                                 // (development build, tools/exp_timeline2.py: every wave's start / end stamp goes to the motion plane)
-#else
     const uint64_t t_begin = (M.flags & 2u) ? wall_clock64() : 0ull;         // diagnostic timeline (100 MHz)
-#endif
     int x0, y0, yp0, ty, tx;
     uint32_t frame;
     if (!block_to_tile<MAP>(M, frame, ty, tx)) return;                   // uniform per workgroup
@@ -844,7 +148,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(((MODE == 4
             // access below is a flat instruction with a 64-bit address in two vector registers)
             const uint32_t c8 = *gptr<const uint32_t>(sky8, (ty * k.w + tx) << 2);
             const uint32_t i32 = (uint32_t)py * (uint32_t)W + (uint32_t)px;
-#ifndef VRT_EXP_STAMPS
             // (span path: the planes of zeros as NON-TEMPORAL stores -- a whole 128-byte row per instruction has nothing left to merge
             // in the L2, which the 32-byte pieces of an 8x8 block do: those measured 4.88 against 3.2 ms this way)
             // (the primary-only kernels, where it was measured; in the megakernels a scalar that lives this long costs the bounce
@@ -867,13 +170,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(((MODE == 4
                 *gptr<uint32_t>(f.color8, i32 << 2) = c8;
                 return;
             }
-#endif
             if (f.position) *gptr<vrt_f4>(f.position, i32 << 4) = (vrt_f4){0.0f, 0.0f, 0.0f, 0.0f};
-#ifdef VRT_EXP_STAMPS
-            if (f.motion) *gptr<vrt_f2>(f.motion, i32 << 3) = (vrt_f2){__uint_as_float((uint32_t)t_begin), __uint_as_float((uint32_t)wall_clock64())};
-#else
             if (f.motion) *gptr<vrt_f2>(f.motion, i32 << 3) = (vrt_f2){0.0f, 0.0f};
-#endif
             if (f.depth) *gptr<float>(f.depth, i32 << 2) = 0.0f;
             if (f.normal8) *gptr<uint32_t>(f.normal8, i32 << 2) = 0u;
             if (f.mask8) *gptr<uint8_t>(f.mask8, i32) = (uint8_t)0;
@@ -903,12 +201,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(((MODE == 4
     // them from words and would otherwise get flat instructions with a 64-bit address each; the host admits frames below
     // 2^28 pixels)
     const uint32_t i32 = (uint32_t)i;
-#ifndef VRT_EXP_STAMPS
     // (the launch's flags once more from the kernel's own arguments: a scalar register held across the march would be the 77th)
     const bool six = (kernarg_words(offsetof(GeomParams, map) + offsetof(TileMap, flags))[0] & VRT_MAPFLAG_SIX) != 0u;
-#else
-    const bool six = false;
-#endif
     if (six) {                                                  // the reference's six targets and nothing else (the colour below)
         uint32_t n = 0u;
         if (hit) n = (uint32_t)(uint8_t)snorm8(h.normal.x) | ((uint32_t)(uint8_t)snorm8(h.normal.y) << 8) | ((uint32_t)(uint8_t)snorm8(h.normal.z) << 16);
@@ -919,9 +213,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(((MODE == 4
         *gptr<uint32_t>(f.normal8, i32 << 2) = n;
     } else {
     if (f.depth) *gptr<float>(f.depth, i32 << 2) = depth;
-#ifndef VRT_EXP_STAMPS
     if (f.motion) *gptr<vrt_f2>(f.motion, i32 << 3) = (vrt_f2){0.0f, 0.0f};
-#endif
     if (f.mask8) *gptr<uint8_t>(f.mask8, i32) = hit ? (uint8_t)230 : (uint8_t)0;          // unorm8(0.9f) = 230 (tests/test_oracle_kat.py), unorm8(0) = 0
     if (f.position) *gptr<vrt_f4>(f.position, i32 << 4) = (vrt_f4){h.pos.x, h.pos.y, h.pos.z, 0.0f};
     if (f.normal8) {
@@ -995,19 +287,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(((MODE == 4
         } else {
             col = sky_color(s, dir);
         }
-#ifdef VRT_EXP_LATE_INDEX
-        {   // the pixel's indices once more, from px and py alone: nothing but those two stays live across the secondary rays
-            int pxl = px, pyl = py;
-            asm volatile("" : "+v"(pxl), "+v"(pyl));
-            const size_t il = (size_t)pyl * (size_t)W + (size_t)pxl;
-            store_color(f, col, il, (uint32_t)il, ((uint32_t)(yp0 + (pyl - y0)) * (uint32_t)W + (uint32_t)pxl) << 2);
-        }
-#else
         store_color(f, col, i, i32, ((uint32_t)(yp0 + (py - y0)) * (uint32_t)W + (uint32_t)px) << 2);
-#endif
-#ifdef VRT_EXP_STAMPS
-        if (f.motion) *gptr<vrt_f2>(f.motion, i32 << 3) = (vrt_f2){__uint_as_float((uint32_t)t_begin), __uint_as_float((uint32_t)wall_clock64())};
-#endif
     } else if (hit) {
         // hit record for K2 (position bits + material | mask << 8 | (step+1) codes) and a slot in the compacted list of
         // hit pixels: K2 then runs one lane per HIT pixel instead of one per pixel (hipcc folds the per-lane
@@ -1119,7 +399,7 @@ hipError_t launch_primary_t(const GeomParams& p, hipStream_t s)
     else if (p.xcd_turn) grid = dim3((unsigned)p.tiles_x * 8u * (unsigned)((p.tiles_y_local * p.n_frames + 7) / 8));
     dim3 block(p.tile_h == 8 ? 64 : 256);
     size_t lds = (OCC_LDS && (TRAV == VRT_TRAVERSAL_BITMASK || TRAV == VRT_TRAVERSAL_JUMP)) ? p.occ2_bytes + p.occ3_bytes : 0;
-    // (the hand-written loop's AO batches: one slot of waiting rays per wave, df_ao_batch_loop)
+    // (the hand-written loop's AO batches: VRT_AO_SLOT bytes per wave, the contract at the head of vrt_shade.h)
     if ((TRAV == VRT_TRAVERSAL_DF_FAST || TRAV == VRT_TRAVERSAL_DF_FAST_CNT || TRAV == VRT_TRAVERSAL_BRICK || TRAV == VRT_TRAVERSAL_BRICK_CNT) && p.fused_shade != 1)
         lds = (size_t)(block.x / 64u) * (size_t)VRT_AO_SLOT;
     return p.table ? launch_k1<TRAV, OCC_LDS, true>(p, grid, block, lds, s) : launch_k1<TRAV, OCC_LDS, false>(p, grid, block, lds, s);

@@ -5,7 +5,7 @@
 // The record is traceRay's (voxel_volume.frag:176-196) with the normal before its normalisation:
 //   material  voxel id at the hit, 0 = miss (a ray that leaves the volume, or exhausts maxSteps)
 //   pos       RayHit.pos = boxIntersection's point + length(mask * (sideDist - deltaDist)) * dir -- the expression, in the
-//             order, of vrt_device.hip's trace_ray, so a primary ray's pos is the position plane's, bit for bit
+//             order, of vrt_shade.h's trace_ray, so a primary ray's pos is the position plane's, bit for bit
 //   voxel     mapPos at the hit
 //   normal    -mask * rayStep, every component in {-1, 0, 1}
 // and zeros in every field of a miss: the march ends a missing ray where nothing solid is left in its octant (open cells),

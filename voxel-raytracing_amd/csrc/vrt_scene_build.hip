@@ -95,7 +95,7 @@ __global__ __launch_bounds__(256) void k_df_pass(const uint8_t* __restrict__ vox
         best = best < m ? best : m;
     }
     size_t o = i;
-    if (padded) {                                            // final pass: into the zero-bordered field (vrt_traverse.h df_index)
+    if (padded) {                                            // final pass: into the zero-bordered field (vrt_volume.h df_index)
         o = (size_t)(x + 1) + ((size_t)(y + 1) + (size_t)(z + 1) * ((size_t)H + 2u)) * ((size_t)W + 2u);
     }
     dst[o] = (uint8_t)(best > cap ? cap : best);

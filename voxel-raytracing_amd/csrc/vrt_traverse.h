@@ -1,595 +1,31 @@
-// vrt_traverse.h -- the grid march of voxel_volume.frag:109-174 (boxIntersection + traceRayInt) in three
-// traversal strategies that all produce the SAME RayInt (hit cell, mask, sideDist, material) bit for bit:
+// vrt_traverse.h -- the grid march of voxel_volume.frag:109-174 (boxIntersection + traceRayInt) in traversal strategies
+// that all produce the SAME RayInt (hit cell, mask, sideDist, material) bit for bit:
 //
 //   DENSE    one R8 fetch per DDA iteration (the literal shader loop)
 //   BITMASK  same iterations; the solid test reads the 4^3 occupancy word cached in registers and the
 //            16^3 summary (LDS) before touching global memory; the R8 id is fetched once, at the hit
 //   DF       the wave agrees (one DPP min-reduction) on a number of iterations no lane needs a memory test for (distance
 //            field clearance) and runs them as pure ALU stepping; one gather per run instead of per iteration
+//   DF_FAST  DF through four hand-written gfx950 look-up loops (what AUTO / DF resolve to; _CNT: their counting twins)
+//   BRICK    DF over the two-level clearance of a brick scene (_CNT: with its counters)
 //   JUMP     BITMASK inside occupied 4^3 cells; across EMPTY pyramid cells (4^3 / 16^3 / 64^3) one iteration
-//            replaces all the DDA iterations up to the cell's exit -- exactly (see "exact jumps" below)
+//            replaces all the DDA iterations up to the cell's exit -- exactly (see "exact jumps" further down)
+//   DFJ      DF with its long runs in that closed form
 //
-// Compiled for the device by vrt_device.hip and for the host by tests/native/traverse_host.cpp (unit tests
+// Compiled for the device by vrt_device.hip and vrt_query.hip and for the host by tests/native/traverse_host.cpp (unit tests
 // of this very code against the oracle on millions of rays; the shipped library has no host render path).
 //
-// ---- exact jumps -------------------------------------------------------------------------------------
-// The shader advances sideDist by repeated fp32 addition (frag:167), so after k steps along an axis
-// sideDist = s (+) d (+) d ... (k roundings), which is not s + k*d.  Within one binade of s, however,
-// RN(s + d) = s + Q*ulp(s) for a constant integer Q (d rounded to the ulp of s; a half-ulp tie rounds to
-// even and, once the mantissa is even, keeps it even), and the bit pattern of a positive float is monotone
-// in its value.  Hence, on the bit patterns, k additions are ONE integer multiply-add, S(j) = bits + j*Q,
-// valid until the mantissa would overflow into the next binade.  The DDA's interleaving of the three
-// axes is a merge of three such arithmetic sequences by value, ties stepping together (frag:164), so the
-// state after any number of iterations is computable in closed form:
-//   n_a  = steps axis a may take before leaving the empty cell (or the binade), T_a = S_a(n_a - 1)
-//   T*   = min T_a: the sideDist value at which the last iteration of the jump happens
-//   c_a  = n_a for the axes with T_a == T*, else #{j : S_a(j) <= T*} = floor((T* - bits_a)/Q_a) + 1
-//   mask = axes whose last step was taken exactly at T*
-// The final addition of every axis that reaches T* is performed in fp32, so binade crossings are literal.
-// The iteration budget (MAX_RAY_STEPS) is tracked as bounds: every iteration steps 1..3 axes, so
-// max_a(steps_a) <= iterations <= sum_a(steps_a); a hit whose bounds straddle the budget (only possible
-// for rays with exact ties that run within a few steps of the budget) is re-traced literally.
+// The data types and the DDA are in vrt_volume.h and vrt_dda.h (no march, no assembly: what the C-ABI and the scene build
+// include).  This file holds, in this order: DF in plain C++ (trace_df), the hand-written loops (trace_df_fast, the AO pool),
+// the brick march, the literal strategies and the exact jumps, the host stubs of the device-only functions (ONE block), and
+// trace_int, the dispatch.  Cutting these into one header per march is the open part of the split: DESIGN.md 8.
 #pragma once
 
-#include "vrt_spec.h"
-
-#ifndef VRT_TRAVERSAL_DENSE
-#define VRT_TRAVERSAL_DENSE 1
-#define VRT_TRAVERSAL_BITMASK 2
-#define VRT_TRAVERSAL_JUMP 3
-#define VRT_TRAVERSAL_DF 4
-#define VRT_TRAVERSAL_DFJ 5
-#endif
-#define VRT_TRAVERSAL_BRICK 6     // brick scenes (vrt_scene_from_bricks): DF over a two-level clearance; chosen by AUTO
-#define VRT_TRAVERSAL_DF_FAST 7   // internal: DF through the hand-written look-up loop (trace_df_fast); chosen by the host
-#define VRT_TRAVERSAL_DF_FAST_CNT 8   // internal: the same through the loops' counting twins (VRT_FLAG_MARCHED_COUNTS / VRT_FLAG_LOOKUP_COUNTS)
-#define VRT_TRAVERSAL_BRICK_CNT 9     // internal: the brick march with its counters (the same flags, and every launch that fills iteration-count planes)
+#include "vrt_dda.h"     // (over vrt_volume.h: the data types and the DDA, for code that needs no march)
 
 namespace vrt {
 
-// Read-only view of a scene's voxel data (device pointers on the device, host pointers in the tests).
-struct VolumeView {
-    const uint8_t*  vox;     // W*H*D, x + y*W + z*W*H
-    const uint64_t* occ1;    // per 4^3 voxels, bit (x&3)|(y&3)<<2|(z&3)<<4
-    const uint64_t* occ2;    // per 16^3
-    const uint64_t* occ3;    // per 64^3
-    const uint8_t*  df;      // 8 octant clearance fields, each x-fastest with a one-voxel border of zeros (df_index): field o
-                             // (bit0: +x, bit1: +y, bit2: +z) holds per voxel 0 = solid, else min(63, side of the largest
-                             // empty cube that has this voxel as its corner and extends towards the octant's signs;
-                             // outside the volume counts as solid)
-    uint64_t        df_stride;  // bytes between octant fields
-    uint32_t        df_fast;    // 1: the allocation continues with a ninth field, the voxel ids in the same zero-bordered layout
-                                // (field 8), and one byte 0xFF at offset 9 * df_stride, and all of it is addressable with
-                                // 32-bit offsets (trace_df_fast)
-    uint32_t        count_lookups; // 1 (VRT_FLAG_LOOKUP_COUNTS): r.fetches holds the bytes a ray's march asked for instead of its iterations
-    uint32_t        count_marched; // 1 (VRT_FLAG_MARCHED_COUNTS): an any-hit ray that is decided a miss without stepping (its clearance covers
-                                // what is left of its budget) reports the iterations it TOOK, not the budget the reference's loop would
-                                // have spent -- the count planes then hold the product march's own work
-    // brick scenes (vrt_scene_from_bricks; vox / occ* / df are null): the volume in 8^3 bricks.  All grids are padded by one
-    // brick on every side (index (bx+1) + ((by+1) + (bz+1) * pby) * pbx), the border counting as outside the volume.
-    const uint32_t* bgrid;      // 0 = empty brick, 0xFFFFFFFF = border (outside the volume), else 1 + index into bpool / bfine
-    const uint8_t*  bcoarse;    // 8 octant fields over the padded grid: 0 = occupied brick or border, else min(16, side in BRICKS of
-                                // the largest cube of empty bricks cornered here and extending towards the octant's signs)
-    uint64_t        bcoarse_stride;
-    const uint8_t*  bpool;      // 512 voxel ids per occupied brick, voxel (x,y,z) of the brick at x + 8y + 64z
-    const uint8_t*  bfine;      // per occupied brick 8 octants x 512 voxels: 0 = solid, else min(16, side of the largest empty cube
-                                // of VOXELS cornered here ...), looking through the brick's 26 neighbours
-    int32_t         pbx, pby;
-    const uint64_t* bentry;     // what a look-up of the march reads: ONE 8-byte word per brick of the padded grid (brick_entry_pack):
-                                // bits 0..23 the pointer (0 empty, 0xFFFFFF border, else 1 + pool index), bits 24..31 "open" per octant,
-                                // bits 32..63 the coarse clearance of the eight octants, four bits each (0 = occupied or border, else
-                                // min(15, bricks)) -- bgrid and bcoarse folded into one load instead of two dependent ones
-    uint32_t        df_own;      // 1: AO rays through df_any_loop (development switch)
-    uint32_t        ao_batch;    // 1: the hand-written loop's kernels trace the AO rays of a wave from a pool in LDS every lane draws on (df_ao_pool_loop; context option "ao_batch")
-    uint32_t        df_prefetch; // 1: the secondary rays' look-ups through trace_df_fast prefetch the neighbouring rows (development switch)
-    uint32_t        df_thresh;   // 1: primary rays through df_prim_loop (long runs by threshold; launches that report no iteration counts)
-    uint32_t        brick_open;  // 1: bit 7 of a coarse byte (no occupied brick is left in the box between this brick and the volume's
-                                // corner in the octant's direction: a ray here is a miss) ends the march; 0: the bit is ignored   // padded grid dimensions in x and y
-    int32_t W, H, D;
-    int32_t n1x, n1y, n1z;
-    int32_t n2x, n2y, n2z;
-    int32_t n3x, n3y, n3z;
-};
-
-struct RayInt {            // RayHitInternal, voxel_volume.frag:33-41
-    f3 pos, side, delta;
-    int sx, sy, sz;        // rayStep
-    int mx, my, mz;        // mapPos at loop exit
-    uint32_t material;
-    uint32_t mask;         // bit0..2
-    uint32_t fetches;      // DENSE/BITMASK: iterations that sampled a voxel (frag:157); JUMP: upper bound
-    uint32_t dbg0, dbg1;   // traversal diagnostics (outer iterations / near-regime iterations of trace_skip)
-};
-
-struct TraceStats {        // host-side instrumentation (tests); a no-op type is used on the device
-    uint32_t literal = 0, jumps1 = 0, jumps2 = 0, jumps3 = 0, retrace = 0, lookups = 0;
-};
-struct NoStats {};
-VRT_HD void st_literal(TraceStats& s) { s.literal++; }
-VRT_HD void st_jump(TraceStats& s, int lvl) { if (lvl == 1) s.jumps1++; else if (lvl == 2) s.jumps2++; else s.jumps3++; }
-VRT_HD void st_retrace(TraceStats& s) { s.retrace++; }
-VRT_HD void st_lookup(TraceStats& s) { s.lookups++; }
-VRT_HD void st_literal(NoStats&) {}
-VRT_HD void st_jump(NoStats&, int) {}
-VRT_HD void st_retrace(NoStats&) {}
-VRT_HD void st_lookup(NoStats&) {}
-
-VRT_HD uint32_t f2u(float f)
-{
-#if defined(__HIP_DEVICE_COMPILE__)
-    return __float_as_uint(f);
-#else
-    union { float f; uint32_t u; } c; c.f = f; return c.u;
-#endif
-}
-VRT_HD float u2f(uint32_t u)
-{
-#if defined(__HIP_DEVICE_COMPILE__)
-    return __uint_as_float(u);
-#else
-    union { float f; uint32_t u; } c; c.u = u; return c.f;
-#endif
-}
-VRT_HD float rcp_approx(float x)
-{
-#if defined(__HIP_DEVICE_COMPILE__)
-    return __builtin_amdgcn_rcpf(x);
-#else
-    return 1.0f / x;
-#endif
-}
-
-// ---- occupancy lookups ------------------------------------------------------------------------------
-
-VRT_HD uint32_t cell_bit(int x, int y, int z) { return (uint32_t)(x & 3) | ((uint32_t)(y & 3) << 2) | ((uint32_t)(z & 3) << 4); }
-
-// occ1 word of 4^3 cell (cx,cy,cz); the 16^3 summary is consulted first so empty space costs no global access.
-template <class OP>
-VRT_HD uint64_t fetch_cell(const VolumeView& v, OP o2, int cx, int cy, int cz)
-{
-    uint64_t w2 = o2[(cx >> 2) + ((cy >> 2) + (cz >> 2) * v.n2y) * v.n2x];
-    if (!((w2 >> cell_bit(cx, cy, cz)) & 1ull)) return 0ull;
-    return v.occ1[cx + (cy + cz * v.n1y) * v.n1x];
-}
-
-// Emptiness level of the pyramid at voxel (mx,my,mz): 3 = its 64^3 cell is empty, 2 = its 16^3 cell, 1 = its
-// 4^3 cell, 0 = the 4^3 cell holds voxels (word = its occ1 bits).
-template <class OP>
-VRT_HD int lookup_level(const VolumeView& v, OP o2, OP o3, int mx, int my, int mz, uint64_t& word)
-{
-    int cx = mx >> 2, cy = my >> 2, cz = mz >> 2;
-    int qx = cx >> 2, qy = cy >> 2, qz = cz >> 2;
-    uint64_t w3 = o3[(qx >> 2) + ((qy >> 2) + (qz >> 2) * v.n3y) * v.n3x];
-    word = 0ull;
-    if (w3 == 0ull) return 3;
-    if (!((w3 >> cell_bit(qx, qy, qz)) & 1ull)) return 2;
-    uint64_t w2 = o2[qx + (qy + qz * v.n2y) * v.n2x];
-    if (!((w2 >> cell_bit(cx, cy, cz)) & 1ull)) return 1;
-    word = v.occ1[cx + (cy + cz * v.n1y) * v.n1x];
-    return 0;
-}
-
-// Each clearance field is a plain x-fastest volume with a one-voxel border of zeros on every side, (W+2)(H+2)(D+2)
-// bytes: voxel (x,y,z) lives at (x+1) + (y+1)*(W+2) + (z+1)*(W+2)*(H+2).  A run can carry a ray at most one voxel
-// past a wall (the fields count the outside as solid), so the traversal may read the field wherever a run ends
-// without a bounds test, and it keeps the index incrementally (two 24-bit multiply-adds per look-up).  An earlier
-// layout in 4x4x4 bricks touched fewer cache lines per gather but cost 12 VALU ops of index arithmetic plus the
-// bounds test per look-up; the kernel is bound by VALU issue, not by the vector-memory pipe.
-VRT_HD size_t df_index(const VolumeView& v, int x, int y, int z)
-{
-    const size_t pw = (size_t)v.W + 2u, ph = (size_t)v.H + 2u;
-    return (size_t)(x + 1) + ((size_t)(y + 1) + (size_t)(z + 1) * ph) * pw;
-}
-VRT_HD size_t df_field_bytes(int W, int H, int D)            // one padded field, rounded up to 256 B
-{
-    size_t n = ((size_t)W + 2u) * ((size_t)H + 2u) * ((size_t)D + 2u);
-    return (n + 255u) & ~(size_t)255u;
-}
-// 32-bit incremental indexing: all eight fields below 4 GiB and a padded z-slice that fits a signed 24-bit multiply
-VRT_HD bool df_small(const VolumeView& v)
-{
-    return 8ull * v.df_stride <= 0xFFFFFFFFull && ((uint64_t)v.W + 2u) * ((uint64_t)v.H + 2u) < (1ull << 23);
-}
-// trace_df_fast's layout (nine fields + the 0xFF byte, every offset 32 bits): the loop counts its offsets from `bias` =
-// (W+2)(H+2) bytes IN FRONT of field 0, so the largest offset it forms is bias + 9 * field (the 0xFF byte), a hit's id read
-// reaches bias + 8 * field + index, and a live lane's prefetch one slice (bias bytes) past its own index -- all of it must
-// stay below 2^32, and the padded slice must fit the signed 24-bit multiply of the index recovery.
-VRT_HD bool df_fast_layout_ok(int W, int H, int D)
-{
-    const uint64_t pwh = ((uint64_t)W + 2u) * ((uint64_t)H + 2u);
-    return 2ull * pwh + 9ull * (uint64_t)df_field_bytes(W, H, D) + 256ull <= 0xFFFFFFFFull && pwh < (1ull << 23);
-}
-template <bool SMALL> struct IndexT;
-template <> struct IndexT<true>  { typedef uint32_t type; typedef int32_t stype; };
-template <> struct IndexT<false> { typedef size_t type;   typedef long long stype; };
-// a * b for |a|, |b| < 2^23 (one v_mul_i32_i24 / v_mad_i32_i24 instead of the quarter-rate 32-bit multiply)
-VRT_HD int mul24(int a, int b)
-{
-#if defined(__HIP_DEVICE_COMPILE__)
-    return __mul24(a, b);
-#else
-    return a * b;
-#endif
-}
-
-// ---- boxIntersection + DDA setup (frag:109-144) -------------------------------------------------------
-
-struct DdaState {
-    f3 p;                     // boxIntersection() result
-    int mx, my, mz;           // mapPos
-    float sdx, sdy, sdz;      // sideDist
-    float dx, dy, dz;         // deltaDist
-    int sx, sy, sz;           // rayStep
-    uint32_t mask;            // rule A initial mask
-    float ivx, ivy, ivz;      // 1 / dir (dda_entry -> dda_rest)
-    float tspan;              // length of the ray inside the box, from where the march starts to where it leaves (0: never inside)
-};
-
-// boxIntersection (frag:109-125) and the first mapPos (frag:135): everything needed to know whether the march can
-// leave the volume in iteration 0.
-VRT_HD void dda_entry(const VolumeView& v, f3 start, f3 dir, DdaState& s)
-{
-    float ivx = 1.0f / dir.x, ivy = 1.0f / dir.y, ivz = 1.0f / dir.z;
-    float t1x = (-start.x) * ivx, t2x = ((float)v.W - start.x) * ivx;
-    float t1y = (-start.y) * ivy, t2y = ((float)v.H - start.y) * ivy;
-    float t1z = (-start.z) * ivz, t2z = ((float)v.D - start.z) * ivz;
-    float tnx = fminf(t1x, t2x), tny = fminf(t1y, t2y), tnz = fminf(t1z, t2z);
-    float txx = fmaxf(t1x, t2x), txy = fmaxf(t1y, t2y), txz = fmaxf(t1z, t2z);
-    float tmin = fmaxf(tnx, fmaxf(tny, tnz));
-    float tmax = fminf(txx, fminf(txy, txz));
-    s.p = start;
-    s.mask = 0;
-    if (tmin >= 0.0f && tmax >= tmin) {
-        float t = tmin + 0.1f;
-        s.p = mk3(start.x + t * dir.x, start.y + t * dir.y, start.z + t * dir.z);
-        s.mask = (uint32_t)(tnx == tmin) | ((uint32_t)(tny == tmin) << 1) | ((uint32_t)(tnz == tmin) << 2);
-    }
-    s.mx = (int)floorf(s.p.x); s.my = (int)floorf(s.p.y); s.mz = (int)floorf(s.p.z);
-    s.ivx = ivx; s.ivy = ivy; s.ivz = ivz;
-    const float t0 = fmaxf(tmin, 0.0f);
-    s.tspan = tmax >= t0 ? tmax - t0 : 0.0f;
-}
-
-// deltaDist, rayStep, sideDist (frag:136-144)
-VRT_HD void dda_rest(f3 dir, DdaState& s)
-{
-    s.dx = fabsf(s.ivx); s.dy = fabsf(s.ivy); s.dz = fabsf(s.ivz);
-    float gx = fsign(dir.x), gy = fsign(dir.y), gz = fsign(dir.z);
-    s.sx = (int)gx; s.sy = (int)gy; s.sz = (int)gz;
-    s.sdx = ((gx * ((float)s.mx - s.p.x) + gx * 0.5f) + 0.5f) * s.dx;
-    s.sdy = ((gy * ((float)s.my - s.p.y) + gy * 0.5f) + 0.5f) * s.dy;
-    s.sdz = ((gz * ((float)s.mz - s.p.z) + gz * 0.5f) + 0.5f) * s.dz;
-}
-
-VRT_HD void dda_setup(const VolumeView& v, f3 start, f3 dir, DdaState& s)
-{
-    dda_entry(v, start, dir, s);
-    dda_rest(dir, s);
-}
-
-VRT_HD bool oob(const VolumeView& v, int mx, int my, int mz)
-{
-    return (uint32_t)mx >= (uint32_t)v.W || (uint32_t)my >= (uint32_t)v.H || (uint32_t)mz >= (uint32_t)v.D;
-}
-
-VRT_HD uint32_t voxel_at(const VolumeView& v, int mx, int my, int mz)
-{
-    return v.vox[(size_t)mx + ((size_t)my + (size_t)mz * (size_t)v.H) * (size_t)v.W];
-}
-
-VRT_HD uint32_t umin3(uint32_t a, uint32_t b, uint32_t c) { uint32_t m = a < b ? a : b; return m < c ? m : c; }
-
-// One literal DDA iteration's advance (frag:164-170).  sideDist is never negative, so the order of the
-// floats is the order of their bit patterns: mask_a = (side_a <= min(side_b, side_c)) == (bits_a == min3(bits)).
-// (Integer min/compare need no NaN canonicalisation, which halves the instruction count of this block.)
-#define VRT_DDA_STEP(S, MASK)                                                         \
-    do {                                                                              \
-        uint32_t bx_ = f2u((S).sdx), by_ = f2u((S).sdy), bz_ = f2u((S).sdz);          \
-        uint32_t mn_ = umin3(bx_, by_, bz_);                                          \
-        bool m0_ = bx_ == mn_, m1_ = by_ == mn_, m2_ = bz_ == mn_;                    \
-        (MASK) = (uint32_t)m0_ | ((uint32_t)m1_ << 1) | ((uint32_t)m2_ << 2);         \
-        (S).sdx = m0_ ? (S).sdx + (S).dx : (S).sdx; (S).mx += m0_ ? (S).sx : 0;       \
-        (S).sdy = m1_ ? (S).sdy + (S).dy : (S).sdy; (S).my += m1_ ? (S).sy : 0;       \
-        (S).sdz = m2_ ? (S).sdz + (S).dz : (S).sdz; (S).mz += m2_ ? (S).sz : 0;       \
-    } while (0)
-
-VRT_HD void finish(const DdaState& s, uint32_t material, uint32_t mask, uint32_t fetches, RayInt& r)
-{
-    r.pos = s.p; r.side = mk3(s.sdx, s.sdy, s.sdz); r.delta = mk3(s.dx, s.dy, s.dz);
-    r.sx = s.sx; r.sy = s.sy; r.sz = s.sz; r.mx = s.mx; r.my = s.my; r.mz = s.mz;
-    r.material = material; r.mask = mask; r.fetches = fetches; r.dbg0 = 0; r.dbg1 = 0;
-}
-
-// rint(x) as an int; NaN -> 0 (what v_cvt_i32_f32 does; spelled out for the host build)
-VRT_HD int steps_taken(float x)
-{
-#if defined(__HIP_DEVICE_COMPILE__)
-    return (int)rintf(x);
-#else
-    return x == x ? (int)rintf(x) : 0;
-#endif
-}
-
-// Signed number of steps an axis took while its sideDist grew by dside: floor(dside * g + 1/2), g = +-1/delta (or 0 for
-// an axis that cannot step: its sideDist is +inf, inf - inf = NaN, and the DX9-rule multiply makes NaN * 0 = 0).
-// Two VALU ops: v_mul_legacy_f32 + v_cvt_rpi_i32_f32 (round to nearest by floor(x + 0.5) in one instruction).
-VRT_HD int steps_signed(float dside, float g)
-{
-#if defined(__HIP_DEVICE_COMPILE__)
-    int n;
-    float q;
-    asm("v_mul_legacy_f32 %0, %1, %2" : "=v"(q) : "v"(dside), "v"(g));
-    asm("v_cvt_rpi_i32_f32 %0, %1" : "=v"(n) : "v"(q));
-    return n;
-#else
-    return g == 0.0f ? 0 : (int)floorf(dside * g + 0.5f);
-#endif
-}
-
-// One DDA iteration that only advances sideDist (frag:164-170 without the mapPos / mask bookkeeping).
-// Device: 7 VALU ops -- one three-way integer min, then per axis a v_cmpx that narrows EXEC to the lanes whose axis holds the
-// minimum and a v_add_f32 that runs under it (the compiler's form is compare + select + add = 10).  EXEC is put back
-// from a scalar copy after each axis; the scalar moves issue beside other waves' vector work.
-VRT_HD void dda_advance(DdaState& s)
-{
-#if defined(__HIP_DEVICE_COMPILE__)
-    uint32_t mn;
-    uint64_t saved;
-    asm volatile("v_min3_u32 %[mn], %[x], %[y], %[z]\n\t"
-                 "s_mov_b64 %[sv], exec\n\t"
-                 "v_cmpx_eq_u32 %[mn], %[x]\n\t"
-                 "v_add_f32 %[x], %[x], %[dx]\n\t"
-                 "s_mov_b64 exec, %[sv]\n\t"
-                 "v_cmpx_eq_u32 %[mn], %[y]\n\t"
-                 "v_add_f32 %[y], %[y], %[dy]\n\t"
-                 "s_mov_b64 exec, %[sv]\n\t"
-                 "v_cmpx_eq_u32 %[mn], %[z]\n\t"
-                 "v_add_f32 %[z], %[z], %[dz]\n\t"
-                 "s_mov_b64 exec, %[sv]"
-                 : [x] "+v"(s.sdx), [y] "+v"(s.sdy), [z] "+v"(s.sdz), [mn] "=&v"(mn), [sv] "=&s"(saved)
-                 : [dx] "v"(s.dx), [dy] "v"(s.dy), [dz] "v"(s.dz)
-                 : "vcc");
-#else
-    uint32_t bx = f2u(s.sdx), by = f2u(s.sdy), bz = f2u(s.sdz);
-    uint32_t mn = umin3(bx, by, bz);
-    s.sdx = bx == mn ? s.sdx + s.dx : s.sdx;
-    s.sdy = by == mn ? s.sdy + s.dy : s.sdy;
-    s.sdz = bz == mn ? s.sdz + s.dz : s.sdz;
-#endif
-}
-
-#if defined(__HIP_DEVICE_COMPILE__)
-// The same iteration for use in wave-uniform control flow: only the lanes of `live` advance (EXEC is narrowed to
-// live & "this axis holds the minimum" per axis and put back to its value on entry at the end).
-__device__ __forceinline__ void dda_advance_live(DdaState& s, uint64_t live)
-{
-    uint32_t mn;
-    uint64_t entry;
-    asm volatile("v_min3_u32 %[mn], %[x], %[y], %[z]\n\t"
-                 "s_mov_b64 %[en], exec\n\t"
-                 "s_mov_b64 exec, %[lv]\n\t"
-                 "v_cmpx_eq_u32 %[mn], %[x]\n\t"
-                 "v_add_f32 %[x], %[x], %[dx]\n\t"
-                 "s_mov_b64 exec, %[lv]\n\t"
-                 "v_cmpx_eq_u32 %[mn], %[y]\n\t"
-                 "v_add_f32 %[y], %[y], %[dy]\n\t"
-                 "s_mov_b64 exec, %[lv]\n\t"
-                 "v_cmpx_eq_u32 %[mn], %[z]\n\t"
-                 "v_add_f32 %[z], %[z], %[dz]\n\t"
-                 "s_mov_b64 exec, %[en]"
-                 : [x] "+v"(s.sdx), [y] "+v"(s.sdy), [z] "+v"(s.sdz), [mn] "=&v"(mn), [en] "=&s"(entry)
-                 : [dx] "v"(s.dx), [dy] "v"(s.dy), [dz] "v"(s.dz), [lv] "s"(live)
-                 : "vcc");
-}
-// ... and handing out the EXEC mask each v_cmpx leaves behind: it IS that axis' mask bit for the live lanes.
-__device__ __forceinline__ void dda_advance_live_masks(DdaState& s, uint64_t live, uint64_t& kx, uint64_t& ky, uint64_t& kz)
-{
-    uint32_t mn;
-    uint64_t entry;
-    asm volatile("v_min3_u32 %[mn], %[x], %[y], %[z]\n\t"
-                 "s_mov_b64 %[en], exec\n\t"
-                 "s_mov_b64 exec, %[lv]\n\t"
-                 "v_cmpx_eq_u32 %[mn], %[x]\n\t"
-                 "s_mov_b64 %[kx], exec\n\t"
-                 "v_add_f32 %[x], %[x], %[dx]\n\t"
-                 "s_mov_b64 exec, %[lv]\n\t"
-                 "v_cmpx_eq_u32 %[mn], %[y]\n\t"
-                 "s_mov_b64 %[ky], exec\n\t"
-                 "v_add_f32 %[y], %[y], %[dy]\n\t"
-                 "s_mov_b64 exec, %[lv]\n\t"
-                 "v_cmpx_eq_u32 %[mn], %[z]\n\t"
-                 "s_mov_b64 %[kz], exec\n\t"
-                 "v_add_f32 %[z], %[z], %[dz]\n\t"
-                 "s_mov_b64 exec, %[en]"
-                 : [x] "+v"(s.sdx), [y] "+v"(s.sdy), [z] "+v"(s.sdz), [mn] "=&v"(mn), [en] "=&s"(entry),
-                   [kx] "=&s"(kx), [ky] "=&s"(ky), [kz] "=&s"(kz)
-                 : [dx] "v"(s.dx), [dy] "v"(s.dy), [dz] "v"(s.dz), [lv] "s"(live)
-                 : "vcc");
-}
-// A whole run of kw >= 1 iterations for the lanes of `live` in one block: kw - 1 iterations whose masks nobody reads, then
-// one that hands out its three EXEC masks.  EXEC is saved and put back once per run instead of once per iteration, and the
-// counter lives in the block: 5 scalar instructions per iteration (three EXEC reloads, decrement, branch) instead of 8.
-// The scalar unit matters: the kernel issues almost as many scalar as vector instructions.
-__device__ __forceinline__ void dda_run_live_masks(DdaState& s, uint64_t live, uint32_t kw, uint64_t& kx, uint64_t& ky, uint64_t& kz,
-                                                   float& ox, float& oy, float& oz)
-{
-    uint32_t mn, cnt;
-    uint64_t entry;
-#define VRT_DDA_ITER                                           \
-                 "s_mov_b64 exec, %[lv]\n\t"                    \
-                 "v_min3_u32 %[mn], %[x], %[y], %[z]\n\t"       \
-                 "v_cmpx_eq_u32 %[mn], %[x]\n\t"                \
-                 "v_add_f32 %[x], %[x], %[dx]\n\t"              \
-                 "s_mov_b64 exec, %[lv]\n\t"                    \
-                 "v_cmpx_eq_u32 %[mn], %[y]\n\t"                \
-                 "v_add_f32 %[y], %[y], %[dy]\n\t"              \
-                 "s_mov_b64 exec, %[lv]\n\t"                    \
-                 "v_cmpx_eq_u32 %[mn], %[z]\n\t"                \
-                 "v_add_f32 %[z], %[z], %[dz]\n\t"
-    // half of all runs are a single iteration: they take the first branch and nothing else; longer runs do their plain
-    // iterations four per loop trip (a taken branch stalls the wave's instruction stream), the odd one, two or three first
-    // (the block also keeps sideDist as it was on entry, ox/oy/oz: the compiler's own copies around an in/out operand are
-    // three before and two after)
-    asm volatile("s_mov_b64 %[en], exec\n\t"
-                 "v_mov_b32 %[ox], %[x]\n\t"
-                 "v_mov_b32 %[oy], %[y]\n\t"
-                 "v_mov_b32 %[oz], %[z]\n\t"
-                 "s_cmp_eq_u32 %[kw], 1\n\t"
-                 "s_cbranch_scc1 2f\n\t"
-                 "s_sub_u32 %[cnt], %[kw], 1\n\t"            // plain iterations, >= 1
-                 "s_bitcmp0_b32 %[cnt], 0\n\t"
-                 "s_cbranch_scc1 3f\n\t"
-                 VRT_DDA_ITER
-                 "3:\n\t"
-                 "s_bitcmp0_b32 %[cnt], 1\n\t"
-                 "s_cbranch_scc1 4f\n\t"
-                 VRT_DDA_ITER
-                 VRT_DDA_ITER
-                 "4:\n\t"
-                 "s_lshr_b32 %[cnt], %[cnt], 2\n\t"          // quads; SCC = (quads != 0)
-                 "s_cbranch_scc0 2f\n\t"
-                 "s_sub_u32 %[cnt], %[cnt], 1\n\t"
-                 "1:\n\t"
-                 VRT_DDA_ITER
-                 VRT_DDA_ITER
-                 VRT_DDA_ITER
-                 VRT_DDA_ITER
-                 "s_sub_u32 %[cnt], %[cnt], 1\n\t"
-                 "s_cbranch_scc0 1b\n\t"
-                 "2:\n\t"
-                 "s_mov_b64 exec, %[lv]\n\t"
-                 "v_min3_u32 %[mn], %[x], %[y], %[z]\n\t"
-                 "v_cmpx_eq_u32 %[mn], %[x]\n\t"
-                 "s_mov_b64 %[kx], exec\n\t"
-                 "v_add_f32 %[x], %[x], %[dx]\n\t"
-                 "s_mov_b64 exec, %[lv]\n\t"
-                 "v_cmpx_eq_u32 %[mn], %[y]\n\t"
-                 "s_mov_b64 %[ky], exec\n\t"
-                 "v_add_f32 %[y], %[y], %[dy]\n\t"
-                 "s_mov_b64 exec, %[lv]\n\t"
-                 "v_cmpx_eq_u32 %[mn], %[z]\n\t"
-                 "s_mov_b64 %[kz], exec\n\t"
-                 "v_add_f32 %[z], %[z], %[dz]\n\t"
-                 "s_mov_b64 exec, %[en]"
-                 : [x] "+v"(s.sdx), [y] "+v"(s.sdy), [z] "+v"(s.sdz), [mn] "=&v"(mn), [en] "=&s"(entry), [cnt] "=&s"(cnt),
-                   [kx] "=&s"(kx), [ky] "=&s"(ky), [kz] "=&s"(kz), [ox] "=&v"(ox), [oy] "=&v"(oy), [oz] "=&v"(oz)
-                 : [dx] "v"(s.dx), [dy] "v"(s.dy), [dz] "v"(s.dz), [lv] "s"(live), [kw] "s"(kw)
-                 : "vcc", "scc");
-#undef VRT_DDA_ITER
-}
-#endif
-
-#if defined(__HIP_DEVICE_COMPILE__)
-// this lane's bits of three wave-uniform lane masks as 1 | 2 | 4: v_cndmask with the mask as its condition operand
-__device__ __forceinline__ uint32_t lane_bits(uint64_t kx, uint64_t ky, uint64_t kz)
-{
-    uint32_t bx, by, bz;
-    asm("v_cndmask_b32_e64 %0, 0, 1, %1" : "=v"(bx) : "s"(kx));
-    asm("v_cndmask_b32_e64 %0, 0, 2, %1" : "=v"(by) : "s"(ky));
-    asm("v_cndmask_b32_e64 %0, 0, 4, %1" : "=v"(bz) : "s"(kz));
-    return bx | by | bz;
-}
-#endif
-
-// ---- wavefront votes (device: the 64 lanes of a gfx950 wave; host tests: a single lane) ------------------
-
-VRT_HD bool wave_all(bool p)
-{
-#if defined(__HIP_DEVICE_COMPILE__)
-    return __all(p) != 0;
-#else
-    return p;
-#endif
-}
-VRT_HD bool wave_any(bool p)
-{
-#if defined(__HIP_DEVICE_COMPILE__)
-    return __any(p) != 0;
-#else
-    return p;
-#endif
-}
-// min over the active lanes of k (k <= 63), by binary search over ballots: 6 votes, no cross-lane data movement.
-VRT_HD uint32_t wave_min_u6(uint32_t k)
-{
-#if defined(__HIP_DEVICE_COMPILE__)
-    if (__ballot(true) == ~0ull) {
-        // all 64 lanes live (the common case): DPP min-scan, total in lane 63.  row_shr:1,2,4,8 fold each row of 16,
-        // row_bcast:15 / :31 fold the rows; lanes without a source keep `old` = 63, the identity.
-        // v_min_u32 with the DPP modifier on its first source: one VALU op per stage (the builtin form costs three:
-        // mov, mov_dpp, min).  A lane whose DPP source does not exist is disabled for that op and keeps its value.
-        // s_nop 1 = the two wait states gfx9 needs between a VALU write of a VGPR and a DPP read of it.
-        uint32_t v = k, total;
-        asm volatile("s_nop 1\n\t"
-                     "v_min_u32_dpp %0, %0, %0 row_shr:1 row_mask:0xf bank_mask:0xf\n\t"
-                     "s_nop 1\n\t"
-                     "v_min_u32_dpp %0, %0, %0 row_shr:2 row_mask:0xf bank_mask:0xf\n\t"
-                     "s_nop 1\n\t"
-                     "v_min_u32_dpp %0, %0, %0 row_shr:4 row_mask:0xf bank_mask:0xf\n\t"
-                     "s_nop 1\n\t"
-                     "v_min_u32_dpp %0, %0, %0 row_shr:8 row_mask:0xf bank_mask:0xf\n\t"
-                     "s_nop 1\n\t"
-                     "v_min_u32_dpp %0, %0, %0 row_bcast:15 row_mask:0xa bank_mask:0xf\n\t"
-                     "s_nop 1\n\t"
-                     "v_min_u32_dpp %0, %0, %0 row_bcast:31 row_mask:0xc bank_mask:0xf\n\t"
-                     "s_nop 1\n\t"
-                     "v_readlane_b32 %1, %0, 63\n\t"
-                     "s_nop 3"
-                     : "+v"(v), "=s"(total));
-        return total;
-    }
-    uint32_t m = 0;                                           // partial waves: binary search over ballots
-#pragma unroll
-    for (uint32_t bit = 32u; bit != 0u; bit >>= 1)
-        if (__ballot(k < (m | bit)) == 0ull) m |= bit;
-    return m;
-#else
-    return k;
-#endif
-}
-
-// One vote for "is every lane finished" and "how far may the wave run": finished lanes vote VRT_VOTE_DONE, live lanes
-// their clearance (1..63); the minimum is VRT_VOTE_DONE exactly when nobody is live.
-#define VRT_VOTE_DONE 0xFFFFu
-VRT_HD uint32_t wave_min_vote(uint32_t k)
-{
-#if defined(__HIP_DEVICE_COMPILE__)
-    // Half of all look-ups end with a clearance of 1 somewhere in the wave, another quarter with 2 or 3: one compare
-    // each answers those before the 7-op reduction is needed (votes are >= 1; VRT_VOTE_DONE matches none of them).
-    if (__ballot(k == 1u) != 0ull) return 1u;
-    const bool full = __ballot(true) == ~0ull;
-    if (!full) {                                               // secondary rays of a partly hit wave: the reduction below is
-        if (__ballot(k == 2u) != 0ull) return 2u;              // the 6-vote binary search, worth two more shortcuts
-        if (__ballot(k == 3u) != 0ull) return 3u;
-    }
-    if (full) {
-        uint32_t v = k, total;
-        asm volatile("s_nop 1\n\t"
-                     "v_min_u32_dpp %0, %0, %0 row_shr:1 row_mask:0xf bank_mask:0xf\n\t"
-                     "s_nop 1\n\t"
-                     "v_min_u32_dpp %0, %0, %0 row_shr:2 row_mask:0xf bank_mask:0xf\n\t"
-                     "s_nop 1\n\t"
-                     "v_min_u32_dpp %0, %0, %0 row_shr:4 row_mask:0xf bank_mask:0xf\n\t"
-                     "s_nop 1\n\t"
-                     "v_min_u32_dpp %0, %0, %0 row_shr:8 row_mask:0xf bank_mask:0xf\n\t"
-                     "s_nop 1\n\t"
-                     "v_min_u32_dpp %0, %0, %0 row_bcast:15 row_mask:0xa bank_mask:0xf\n\t"
-                     "s_nop 1\n\t"
-                     "v_min_u32_dpp %0, %0, %0 row_bcast:31 row_mask:0xc bank_mask:0xf\n\t"
-                     "s_nop 1\n\t"
-                     "v_readlane_b32 %1, %0, 63\n\t"
-                     "s_nop 3"
-                     : "+v"(v), "=s"(total));
-        return total;
-    }
-    if (__ballot(k != VRT_VOTE_DONE) == 0ull) return VRT_VOTE_DONE;
-    return wave_min_u6(k < 63u ? k : 63u);
-#else
-    return k;
-#endif
-}
-
-// ---- literal traversals ---------------------------------------------------------------------------------
+// ---- DF in plain C++ -----------------------------------------------------------------------------------------
 
 // DF (clearance-field skip, wave-cooperative).  Profiling showed the per-iteration loops are bound by the
 // vector-memory pipe and by instruction issue, not by arithmetic: one 64-lane byte gather per DDA iteration
@@ -802,9 +238,11 @@ VRT_HD void trace_df_impl(const VolumeView& v, f3 start, f3 dir, uint32_t maxSte
 #undef VRT_DF_COUNT
 }
 
-// an AO ray as df_ao_pool_loop takes it up, and the LDS bytes of a wave's pool (11 dwords x 64 columns) + its two rows of counters
+// an AO ray as df_ao_pool_loop takes it up (11 dwords; with its tag a column of 12), and the LDS bytes of a wave's pool + its two rows of counters
 struct AoRay { float x, y, z, dx, dy, dz, gx, gy, gz; uint32_t idx0, voxoff; };
 #define VRT_AO_SLOT 3840   // (dense scenes: 12 rows of 256 B + two rows of counters; brick scenes: 13 + 2)
+// What a lane of the pool loop carries from one call to the next: the ray it is on (or the resting state it starts in)
+struct AoLane { float x, y, z, dx, dy, dz, gx, gy, gz, cx, cy, cz; uint32_t idx0, voxoff, state, owner; };
 
 #if defined(__HIP_DEVICE_COMPILE__)
 // ---- DF, hand-written look-up loop (primary rays of the primary-only kernel) ----------------------------------------------
@@ -893,15 +331,11 @@ __device__ __forceinline__ void df_fast_loop(const uint8_t* base, uint32_t maxSt
     // v53 = index of the byte to read next
     // the block starts on an instruction-cache line: where its loops fall relative to the lines is then a property of the block,
     // not of the code the compiler happens to put in front of it (6 % between two builds that differed elsewhere)
-#ifndef VRT_LOOP_PAD_N
-#define VRT_LOOP_PAD_N 0             // s_nop words after the alignment (development: scan of the block's phase)
-#endif
 #define VRT_STR2(x) #x
 #define VRT_STR(x) VRT_STR2(x)
 #define VRT_F_LOOP(CNT_LOOK, CNT_FIND, CNT_OPND) \
     asm volatile( \
         ".p2align 6\n\t" \
-        ".fill " VRT_STR(VRT_LOOP_PAD_N) ", 4, 0xBF800000\n\t" \
         "s_mov_b32 s60, 0\n\t" \
         "s_movk_i32 s63, 0xff\n\t" \
  /* the loop runs under the EXEC mask it is entered with (all 64 lanes for primary rays; the hit lanes of a wave for its */ \
@@ -1730,7 +1164,7 @@ __device__ __forceinline__ void trace_df_fast(const VolumeView& v, f3 start, f3 
     const uint32_t oct = (uint32_t)(s.sx > 0) | ((uint32_t)(s.sy > 0) << 1) | ((uint32_t)(s.sz > 0) << 2);
     const uint32_t stride = (uint32_t)v.df_stride;
     const int pw = v.W + 2, pwh = pw * (v.H + 2);
-    // offsets count from pwh bytes in front of field 0 (room for a prefetch one slice before it: vrt_api.hip df_guard)
+    // offsets count from pwh bytes in front of field 0 (room for a prefetch one slice before it: vrt_scene::df_guard, vrt_host.h)
     const uint32_t bias = (uint32_t)pwh, octoff = bias + oct * stride, sentinel = bias + 9u * stride;
     const float kInf = u2f(0x7F800000u);
     // a lane that never enters the volume is finished from the start: zero deltas, the 0xFF byte
@@ -1830,8 +1264,6 @@ __device__ __forceinline__ void ao_ray_store(uint32_t ldsw, uint32_t col, const 
     p[9 * 64] = a.idx0; p[10 * 64] = a.voxoff; p[11 * 64] = tag;
 }
 
-// What a lane of the pool loop carries from one call to the next: the ray it is on (or the resting state it starts in)
-struct AoLane { float x, y, z, dx, dy, dz, gx, gy, gz, cx, cy, cz; uint32_t idx0, voxoff, state, owner; };
 __device__ __forceinline__ void ao_lane_rest(const VolumeView& v, AoLane& l)
 {
     const uint32_t stride = (uint32_t)v.df_stride;
@@ -1861,15 +1293,6 @@ __device__ __forceinline__ void trace_ao_pool(const VolumeView& v, AoLane& l, ui
                          (uint32_t)__builtin_amdgcn_readfirstlane((int)v.count_marched), looks);
     next = nx;
 }
-#else
-// host pass of a .hip file / the host build of the unit tests: parsed, never run (the loop is gfx950 assembly)
-template <class STATS, bool ANYHIT = false, bool PF = false, bool OWN = false, bool CNT = false>
-VRT_HD void trace_df_fast(const VolumeView&, f3, f3, uint32_t, RayInt&, STATS&) {}
-VRT_HD void ao_ray_setup(const VolumeView&, f3, f3, AoRay&) {}
-VRT_HD void ao_ray_store(uint32_t, uint32_t, const AoRay&, uint32_t) {}
-struct AoLane { float x, y, z, dx, dy, dz, gx, gy, gz, cx, cy, cz; uint32_t idx0, voxoff, state, owner; };
-VRT_HD void ao_lane_rest(const VolumeView&, AoLane&) {}
-template <bool CNT> VRT_HD void trace_ao_pool(const VolumeView&, AoLane&, uint32_t, uint32_t, uint32_t, uint32_t&, uint32_t, uint32_t&) {}
 #endif
 
 template <class STATS, bool AHEAD = false>
@@ -1888,19 +1311,6 @@ VRT_HD void trace_df(const VolumeView& v, f3 start, f3 dir, uint32_t maxSteps, R
 // brick one byte per voxel and octant (looking through the neighbouring bricks, up to 16 voxels).  Any lower bound of the
 // true clearance gives the same hit (a run only ever skips voxels that are certainly empty), so the result is the dense
 // DF's and the oracle's bit for bit; empty space costs one byte per BRICK in memory and traffic.
-VRT_HD uint64_t brick_entry_pack(uint32_t ptr, const uint8_t coarse[8])
-{
-    // ptr: a padded-grid entry (0 empty, 0xFFFFFFFF border, else 1 + pool index < 0xFFFFFF); coarse[o]: the octant's coarse byte
-    // (low 7 bits: clearance in bricks, 0 = occupied or border; bit 7: open).  A clearance above 15 is stored as 15: any
-    // lower bound of the true clearance gives the same march.
-    uint32_t lo = ptr == 0xFFFFFFFFu ? 0xFFFFFFu : (ptr & 0xFFFFFFu), hi = 0u;
-    for (int o = 0; o < 8; o++) {
-        const uint32_t c = coarse[o] & 0x7Fu;
-        hi |= (c > 15u ? 15u : c) << (4 * o);
-        if (coarse[o] & 0x80u) lo |= 1u << (24 + o);
-    }
-    return (uint64_t)lo | ((uint64_t)hi << 32);
-}
 
 // One look-up of the brick march: the clearance at voxel (mx, my, mz) for a ray of octant `oct` (sx, sy, sz its steps), and the
 // voxel's id where that is 0 inside an occupied brick.  One 8-byte load answers for an empty brick, the border and an open
@@ -2156,6 +1566,8 @@ VRT_HD void trace_brick(const VolumeView& v, f3 start, f3 dir, uint32_t maxSteps
 #endif
 }
 
+// What a lane of the brick pool carries from one call of brick_ao_pool to the next: the ray it is on, or none (live = false)
+struct BrickAoLane { DdaState s; float gx, gy, gz; uint32_t i, owner; bool live; };
 #if defined(__HIP_DEVICE_COMPILE__)
 // The brick march for rays that point every way (AO): every lane spends its own clearance, up to VRT_OWN_CAP iterations per
 // look (df_any_loop's scheme in the generic loop: an iteration runs under the ballot of the lanes that have some left).
@@ -2210,7 +1622,6 @@ __device__ __forceinline__ void trace_brick_own(const VolumeView& v, f3 start, f
 // A ray of the pool: 13 dwords (sideDist, deltaDist, 1 / delta with its sign, mapPos, tag = column of its pixel | first clearance << 8), slot k
 // at row q: q * 256 + k * 4; the two rows of counters behind them (3328: rays of the column's pixel that found a solid voxel; 3584, CNT:
 // what the count planes report).
-struct BrickAoLane { DdaState s; float gx, gy, gz; uint32_t i, owner; bool live; };
 __device__ __forceinline__ void brick_ao_rest(BrickAoLane& l)
 {
     l.s.sdx = l.s.sdy = l.s.sdz = 0.0f; l.s.dx = l.s.dy = l.s.dz = 0.0f; l.s.mx = l.s.my = l.s.mz = 0; l.s.sx = l.s.sy = l.s.sz = 0;
@@ -2300,14 +1711,6 @@ __device__ __forceinline__ void brick_ao_pool(const VolumeView& v, BrickAoLane& 
         l.i += own;
     }
 }
-#else
-template <class STATS, bool CNT = false>
-VRT_HD void trace_brick_own(const VolumeView&, f3, f3, uint32_t, RayInt&, STATS&) {}
-struct BrickAoLane { DdaState s; float gx, gy, gz; uint32_t i, owner; bool live; };
-VRT_HD void brick_ao_rest(BrickAoLane&) {}
-VRT_HD void brick_ao_setup(const VolumeView&, f3, f3, DdaState&, float&, float&, float&) {}
-VRT_HD void brick_ao_store(uint32_t, uint32_t, const DdaState&, float, float, float, uint32_t) {}
-template <bool CNT> VRT_HD void brick_ao_pool(const VolumeView&, BrickAoLane&, uint32_t, uint32_t, bool, uint32_t&, uint32_t, uint32_t&) {}
 #endif
 
 // DENSE: one R8 fetch per iteration.  Straight-line body with a single exit (out of budget, out of bounds or
@@ -2421,6 +1824,22 @@ VRT_HD void trace_literal(const VolumeView& v, OP o2, f3 start, f3 dir, uint32_t
 }
 
 // ---- exact jumps ----------------------------------------------------------------------------------------
+// The shader advances sideDist by repeated fp32 addition (frag:167), so after k steps along an axis
+// sideDist = s (+) d (+) d ... (k roundings), which is not s + k*d.  Within one binade of s, however,
+// RN(s + d) = s + Q*ulp(s) for a constant integer Q (d rounded to the ulp of s; a half-ulp tie rounds to
+// even and, once the mantissa is even, keeps it even), and the bit pattern of a positive float is monotone
+// in its value.  Hence, on the bit patterns, k additions are ONE integer multiply-add, S(j) = bits + j*Q,
+// valid until the mantissa would overflow into the next binade.  The DDA's interleaving of the three
+// axes is a merge of three such arithmetic sequences by value, ties stepping together (frag:164), so the
+// state after any number of iterations is computable in closed form:
+//   n_a  = steps axis a may take before leaving the empty cell (or the binade), T_a = S_a(n_a - 1)
+//   T*   = min T_a: the sideDist value at which the last iteration of the jump happens
+//   c_a  = n_a for the axes with T_a == T*, else #{j : S_a(j) <= T*} = floor((T* - bits_a)/Q_a) + 1
+//   mask = axes whose last step was taken exactly at T*
+// The final addition of every axis that reaches T* is performed in fp32, so binade crossings are literal.
+// The iteration budget (MAX_RAY_STEPS) is tracked as bounds: every iteration steps 1..3 axes, so
+// max_a(steps_a) <= iterations <= sum_a(steps_a); a hit whose bounds straddle the budget (only possible
+// for rays with exact ties that run within a few steps of the budget) is re-traced literally.
 
 // Increment of the bit pattern per addition of d while the sum stays in the binade of `bits`, and how many
 // further additions are guaranteed to stay there (conservative).  false: no closed form here (zero/denormal/
@@ -2642,6 +2061,23 @@ VRT_HD void trace_dfj(const VolumeView& v, f3 start, f3 dir, uint32_t maxSteps, 
     }
     finish(s, material, mask, hit ? lo + slack + 1u : lo + slack, r);
 }
+
+#if !defined(__HIP_DEVICE_COMPILE__)
+// ---- HOST STUBS of the device-only functions (the one block of this file) ----------------------------------------
+// host pass of a .hip file / the host build of the unit tests: parsed, never run (the loop is gfx950 assembly)
+template <class STATS, bool ANYHIT = false, bool PF = false, bool OWN = false, bool CNT = false>
+VRT_HD void trace_df_fast(const VolumeView&, f3, f3, uint32_t, RayInt&, STATS&) {}
+VRT_HD void ao_ray_setup(const VolumeView&, f3, f3, AoRay&) {}
+VRT_HD void ao_ray_store(uint32_t, uint32_t, const AoRay&, uint32_t) {}
+VRT_HD void ao_lane_rest(const VolumeView&, AoLane&) {}
+template <bool CNT> VRT_HD void trace_ao_pool(const VolumeView&, AoLane&, uint32_t, uint32_t, uint32_t, uint32_t&, uint32_t, uint32_t&) {}
+template <class STATS, bool CNT = false>
+VRT_HD void trace_brick_own(const VolumeView&, f3, f3, uint32_t, RayInt&, STATS&) {}
+VRT_HD void brick_ao_rest(BrickAoLane&) {}
+VRT_HD void brick_ao_setup(const VolumeView&, f3, f3, DdaState&, float&, float&, float&) {}
+VRT_HD void brick_ao_store(uint32_t, uint32_t, const DdaState&, float, float, float, uint32_t) {}
+template <bool CNT> VRT_HD void brick_ao_pool(const VolumeView&, BrickAoLane&, uint32_t, uint32_t, bool, uint32_t&, uint32_t, uint32_t&) {}
+#endif
 
 // Dispatcher used by the kernels.
 // ANYHIT: the caller only uses r.material and r.fetches (traceRayHit, frag:198-202): a traversal may then stop stepping a ray

@@ -329,14 +329,24 @@ typedef struct vrt_ray_hits {
  * n < 0, n > 2^28 (268 435 456: the kernel indexes the dwords of a plane, three per ray, and their byte offsets in 32
  * bits -- split a larger batch), a NULL argument, no output plane, max_steps == 0: VRT_ERR_INVALID, before any device work.
  * For every ray with finite origin and direction the planes equal the reference's traceRay of the same volume, pos by bit
- * pattern, zero direction components included -- with one case left open: a zero direction component whose origin component
- * is exactly 0 or exactly the volume's size on that axis.  boxIntersection multiplies 0 by infinity there (frag:113-114);
- * this library's fminf / fmaxf drop the NaN, the axis' slab becomes empty (entry at +inf or exit at -inf), the box test
- * fails, and the ray is marched from its origin's own cell without boxIntersection's advance: a miss at once where that cell
- * lies outside the volume (origin component == size), else a march from the origin.  Never a fault, but pinned by nothing.
+ * pattern, zero direction components (+0 and -0), the direction (0, 0, 0) from inside the volume, subnormal components beside
+ * ordinary ones and origins up to 10^30 voxels away included -- with the set left open in which the GLSL itself is not defined.
+ * Call a direction component d "flat" when 1 / d overflows (d is +-0 or |d| <= 2^-128).  Left open:
+ *  (1) a flat component whose origin component is exactly 0 or exactly the volume's size on that axis.  boxIntersection
+ *      multiplies 0 by infinity there (frag:113-114); this library's fminf / fmaxf drop the NaN, the axis' slab becomes empty
+ *      (entry at +inf or exit at -inf), the box test fails, and the ray is marched from its origin's own cell without
+ *      boxIntersection's advance: a miss at once where that cell lies outside the volume, else a march from the origin;
+ *  (2) a flat, negative, non-zero component whose origin component is an integer: sideDist is 0 * inf (frag:144);
+ *  (3) a direction whose three components are all flat with an origin outside the volume -- (0, 0, 0) included:
+ *      boxIntersection's point is origin + inf * d -- and a direction whose three components are all zero or subnormal
+ *      (|d| < 2^-126) without all being zero: GLSL may flush them, and where it does not the three sideDist are infinite or
+ *      overflow within a few steps and the loop steps every axis on the tie.  The query reads such a direction as (0, 0, 0);
+ *  (4) a ray one of whose sideDist overflows within max_steps (every stepping |d| below about 2^-117 at 1024 steps).
+ * Never a fault, but pinned by nothing.  float -> int conversions saturate (NaN: 0), as the GPU's instruction does.
  * Traversal is what VRT_TRAVERSAL_AUTO resolves to: the hand-written look-up loop on dense scenes whose fields it can
- * address in 32 bits (for max_steps <= 1024, the budgets its position recovery is exact for; above, VRT_TRAVERSAL_DF),
- * VRT_TRAVERSAL_DF with 64-bit offsets on larger volumes, the brick march on brick scenes.  Of the context options only
+ * address in 32 bits (for max_steps <= 1024, the budgets its position recovery is exact for; above, VRT_TRAVERSAL_DF; a wave
+ * of 64 rays that holds a subnormal direction component takes VRT_TRAVERSAL_DF too), VRT_TRAVERSAL_DF with 64-bit offsets on
+ * larger volumes, the brick march on brick scenes.  Of the context options only
  * "thresh_runs" is looked at. */
 int  vrt_trace_rays(vrt_ctx* ctx, const vrt_scene* scene, int64_t n, const float* origins, const float* dirs,
                     uint32_t max_steps, const vrt_ray_hits* out);

@@ -236,6 +236,18 @@ static int box_intersection(const vo_scene* sc, const float s[3], const float d[
     return 0;
 }
 
+/* ivec3(floor(pos)), :135, with the conversion defined over all of float: saturating, NaN -> 0 (what the GPU's conversion
+ * instruction gives; in C a value outside the int range is undefined behaviour).  boxIntersection's point leaves the int range
+ * for far origins and for long directions (its +0.1 is in units of the direction). */
+static int floor_to_int(float x)
+{
+    float f = floorf(x);
+    if (f != f) return 0;
+    if (f >= 2147483648.0f) return 2147483647;
+    if (f <= -2147483648.0f) return -2147483647 - 1;
+    return (int)f;
+}
+
 /* traceRayInt, voxel_volume.frag:127-174. */
 static void trace_ray_int(const vo_scene* sc, const float start[3], const float dir[3],
                           uint32_t max_steps, ray_int* r)
@@ -243,7 +255,7 @@ static void trace_ray_int(const vo_scene* sc, const float start[3], const float 
     box_intersection(sc, start, dir, r->pos, r->mask);           /* :132, rule A mask init */
     float sg[3];
     for (int a = 0; a < 3; a++) {
-        r->map[a]   = (int)floorf(r->pos[a]);                     /* :135 */
+        r->map[a]   = floor_to_int(r->pos[a]);                    /* :135 */
         r->delta[a] = fabsf(1.0f / dir[a]);                       /* :138 */
         sg[a]       = f_sign(dir[a]);
         r->step[a]  = (int)sg[a];                                 /* :141 */

@@ -43,6 +43,27 @@ void qh_query(void* p, int bricks, int anyhit, int n, const float* starts, const
     }
 }
 
+// What query_recover_voxel rounds, for the dense volume: per ray and axis x = side * g + c as the look-up loop forms it (0 for an axis
+// that cannot step) and the ray's FIRST mapPos, from VRT_TRAVERSAL_DF's RayInt.  The steps the axis really took are the hit's
+// mapPos minus the first one, so |x - steps| is the recovery's error (tests/test_ray_query_cpu.py prints its maximum).
+void qh_recover_args(void* p, int n, const float* starts, const float* dirs, uint32_t maxSteps, float* x, int32_t* first)
+{
+    const VolumeView& v = ((HostVolume*)p)->v;
+    const float kInf = u2f(0x7F800000u);
+    for (int i = 0; i < n; i++) {
+        const f3 s = mk3(starts[i * 3], starts[i * 3 + 1], starts[i * 3 + 2]);
+        const f3 d = mk3(dirs[i * 3], dirs[i * 3 + 1], dirs[i * 3 + 2]);
+        RayInt r; NoStats ns;
+        trace_df(v, s, d, maxSteps, r, ns);
+        DdaState s0;
+        dda_setup(v, s, d, s0);
+        x[i * 3] = s0.dx < kInf ? r.side.x * d.x + (-(s0.sdx * d.x)) : 0.0f;
+        x[i * 3 + 1] = s0.dy < kInf ? r.side.y * d.y + (-(s0.sdy * d.y)) : 0.0f;
+        x[i * 3 + 2] = s0.dz < kInf ? r.side.z * d.z + (-(s0.sdz * d.z)) : 0.0f;
+        first[i * 3] = s0.mx; first[i * 3 + 1] = s0.my; first[i * 3 + 2] = s0.mz;
+    }
+}
+
 // the ray a lane without one is given: does the march end it in iteration 0, without a look-up?
 int qh_no_ray_ends_at_once(void* p, int bricks)
 {
@@ -55,5 +76,42 @@ int qh_no_ray_ends_at_once(void* p, int bricks)
 }
 
 size_t qh_sizeof_ray_hits() { return sizeof(vrt_ray_hits); }
+
+// ---- shared with query_edge_main.cpp (the stand-alone program of the sanitizer run) ----
+// the volume both sides trace: cell (x, y, z) of a W x H x D volume in [z][y][x] order; 1 in 200 cells solid, a slab, an empty corner
+void qe_fill(uint8_t* vol, int W, int H, int D)
+{
+    uint32_t x = 12345u;
+    for (int i = 0; i < W * H * D; i++) {
+        x = x * 1664525u + 1013904223u;
+        vol[i] = ((x >> 8) % 200u) == 0u ? (uint8_t)(1u + (x >> 20) % 255u) : (uint8_t)0;
+    }
+    for (int z = D / 2; z < D; z++)
+        for (int y = 0; y < (H / 8 > 1 ? H / 8 : 1); y++)
+            for (int xx = 0; xx < W; xx++) vol[xx + (y + z * H) * W] |= 7;
+    for (int z = 0; z < 8; z++)
+        for (int y = 0; y < 8; y++)
+            for (int xx = 0; xx < 8; xx++) vol[xx + (y + z * H) * W] = 0;
+}
+
+// one budget on one scene, appended to `out` in the order query_edge_main.cpp states; returns the number of bytes written
+size_t qe_records(void* scene, int bricks, int n, const float* rays, uint32_t maxSteps, uint8_t* out)
+{
+    std::vector<float> starts((size_t)n * 3), dirs((size_t)n * 3);
+    for (int i = 0; i < n; i++)
+        for (int a = 0; a < 3; a++) { starts[(size_t)i * 3 + a] = rays[(size_t)i * 6 + a]; dirs[(size_t)i * 3 + a] = rays[(size_t)i * 6 + 3 + a]; }
+    std::vector<uint8_t> mat(n), any(n);
+    std::vector<float> pos((size_t)n * 3);
+    std::vector<int32_t> vox((size_t)n * 3), rec((size_t)n * 3);
+    std::vector<int8_t> nrm((size_t)n * 3);
+    qh_query(scene, bricks, 0, n, starts.data(), dirs.data(), maxSteps, mat.data(), pos.data(), vox.data(), nrm.data(), bricks ? nullptr : rec.data());
+    qh_query(scene, bricks, 1, n, starts.data(), dirs.data(), maxSteps, any.data(), nullptr, nullptr, nullptr, nullptr);
+    uint8_t* o = out;
+    auto put = [&](const void* p, size_t bytes) { memcpy(o, p, bytes); o += bytes; };
+    put(mat.data(), (size_t)n); put(pos.data(), (size_t)n * 12); put(vox.data(), (size_t)n * 12); put(nrm.data(), (size_t)n * 3);
+    if (!bricks) put(rec.data(), (size_t)n * 12);
+    put(any.data(), (size_t)n);
+    return (size_t)(o - out);
+}
 
 } // extern "C"

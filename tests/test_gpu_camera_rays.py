@@ -84,15 +84,26 @@ def test_perspective_at_90_degrees_is_the_renderers_camera(vrt, oracle, engine):
 
 
 def test_other_cameras_trace_like_the_oracle(vrt, oracle, engine):
-    """Orthographic and panorama rays at 64x32 through vrt_trace_rays equal the oracle's vo_trace_ray of the same rays; both
-    views hit something and miss something."""
+    """Orthographic and panorama rays at 64x32 through vrt_trace_rays equal the oracle's vo_trace_ray of the same rays, the
+    orthographic view from an oblique pose and along +z exactly; every view hits something and misses something."""
     vol = _volume()
     pal = metallic_palette(vrt)
     sc = vrt.VoxelScene.from_dense(engine, vol, pal)
     osn = oracle.OracleScene(vol, pal)
     ctl = vrt.CameraController(position=POSE["pos"], yaw=POSE["yaw"], pitch=POSE["pitch"])      # (no direction component is exactly 0)
-    for name, cam in (("ortho", vrt.RayCamera.orthographic(ctl, 40.0)), ("panorama", vrt.RayCamera.panorama((32.5, 40.3, 20.2)))):
+    # ... and an orthographic view along +z exactly.  yaw = 90 does not give one (cos of the float nearest pi / 2 is -4.4e-8), so the
+    # controller's basis is set to the axes themselves: the rays then have two zero direction components and, with these numbers, no
+    # origin component on a face of the volume (the case include/vrt.h leaves open)
+    axial = vrt.CameraController(position=(32.3, 31.7, -20.0))
+    axial.normalDir = np.array([0.0, 0.0, 1.0], np.float32); axial.direction = axial.normalDir.copy()
+    axial.right = np.array([1.0, 0.0, 0.0], np.float32); axial.up = np.array([0.0, -1.0, 0.0], np.float32)
+    for name, cam in (("ortho", vrt.RayCamera.orthographic(ctl, 40.0)), ("panorama", vrt.RayCamera.panorama((32.5, 40.3, 20.2))),
+                      ("ortho along +z", vrt.RayCamera.orthographic(axial, 40.0))):
         o, d = cam.rays(engine, (64, 32))
+        if name == "ortho along +z":
+            dn, on = d.cpu().numpy(), o.cpu().numpy()
+            assert (dn[:, :2] == 0.0).all() and (dn[:, 2] > 0.0).all()
+            assert not ((on[:, :2] == 0.0) | (on[:, :2] == 64.0)).any()
         rec = sc.trace_rays(o, d, 512)
         engine.synchronize()
         rec = {k: v.cpu().numpy() for k, v in rec.items()}

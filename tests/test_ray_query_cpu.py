@@ -7,7 +7,8 @@ import subprocess
 import numpy as np
 import pytest
 
-from ray_query_common import oracle_records, planes_differ, query_rays
+from ray_query_common import (EDGE_CLASSES, EDGE_IMPOSSIBLE, LONG_BUDGETS, LONG_DIMS, edge_rays, long_rays, long_volume, open_set,
+                              oracle_records, planes_differ, query_rays)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NATIVE = os.path.join(ROOT, "tests", "native")
@@ -35,6 +36,11 @@ def qh():
     l.qh_query.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_uint32] + [C.c_void_p] * 5
     l.qh_no_ray_ends_at_once.argtypes = [C.c_void_p, C.c_int]
     l.qh_sizeof_ray_hits.restype = C.c_size_t
+    l.qh_recover_args.restype = None
+    l.qh_recover_args.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
+    l.qe_fill.restype = None; l.qe_fill.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
+    l.qe_records.restype = C.c_size_t
+    l.qe_records.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_uint32, C.c_void_p]
     return l
 
 
@@ -149,3 +155,184 @@ def test_c_abi_surface(qh, vrt):
     # the Python mirrors exist
     for m in ("trace_rays", "occluded", "pick"):
         assert callable(getattr(vrt.VoxelScene, m))
+
+
+# ---- the finite-ray contract at its edges (ray_query_common.edge_rays) ---------------------------------------------------------
+EDGE_BUDGETS = (1024, 512, 37, 1)
+# VOLUMES, a dense volume whose sizes are no multiples of 8 (no brick form), and a single solid voxel
+EDGE_VOLUMES = VOLUMES + [(15, (37, 5, 70), 0.01), (16, (1, 1, 1), 1.0)]
+
+
+def edge_volume(seed, dims, fill):
+    return np.full((1, 1, 1), 5, np.uint8) if dims == (1, 1, 1) else make_volume(seed, dims, fill)
+
+
+def edge_outcomes(cls, dims):
+    """The outcomes a class must hold at 5 % each at max_steps 512: hits and misses (a ray that leaves the volume or exhausts the
+    budget), but for what EDGE_IMPOSSIBLE lists with its reason.  On (1, 1, 1) every other class has both: a ray that never enters
+    the volume misses, one that does meets the one voxel."""
+    missing = EDGE_IMPOSSIBLE.get((cls, tuple(dims)), (None, ""))[0]
+    return [k for k in ("hit", "miss") if k != missing]
+
+
+def pick_edge_seed(oracle, osn, vol, dims, cls, first):
+    """A seed whose batch of the class holds every outcome of edge_outcomes at 5 % or more at max_steps 512 -- decided on the
+    oracle's results alone; returns the oracle's records at 512 too."""
+    for seed in range(first, first + 40):
+        starts, dirs = edge_rays(np.random.default_rng(seed), N_RAYS, dims, cls, vol)
+        exp, c = oracle_records(oracle, osn, starts, dirs, 512)
+        share = {"hit": float((c == 0).mean()), "left": float((c == 1).mean()), "exhausted": float((c == 2).mean())}
+        share["miss"] = share["left"] + share["exhausted"]
+        if min(share[k] for k in edge_outcomes(cls, dims)) >= 0.05:
+            return seed, starts, dirs, share, (exp, c)
+    raise AssertionError(f"no seed in {first} .. {first + 39} gives 5 % of {edge_outcomes(cls, dims)} for {cls} on {dims}: {share}")
+
+
+@pytest.mark.parametrize("cls", EDGE_CLASSES)
+@pytest.mark.parametrize("seed,dims,fill", EDGE_VOLUMES)
+def test_edge_classes_match_oracle(qh, oracle, seed, dims, fill, cls):
+    """Every class of edge_rays, N_RAYS rays each, at max_steps (1024, 512, 37, 1): the query's per-ray function -- VRT_TRAVERSAL_DF
+    on the dense volume and, where the sizes are multiples of 8, the brick march -- equals vo_trace_ray in every plane (pos by bit
+    pattern), a miss is 0 in every plane, the any-hit form equals material != 0, and query_recover_voxel finds the hit's mapPos."""
+    if EDGE_IMPOSSIBLE.get((cls, dims), ("",))[0] == "class":
+        with pytest.raises(AssertionError):
+            edge_rays(np.random.default_rng(0), 8, dims, cls)           # the class has no ray here (EDGE_IMPOSSIBLE says why)
+        return
+    W, H, D = dims
+    vol = edge_volume(seed, dims, fill)
+    osn = oracle.OracleScene(vol, np.zeros((256, 5), np.float32))
+    scenes = [(0, qh.th_create(vol.ctypes.data, W, H, D))]
+    if W % 8 == 0 and H % 8 == 0 and D % 8 == 0:
+        scenes.append((1, qh.thb_create(vol.ctypes.data, W, H, D)))
+    ray_seed, starts, dirs, share, at512 = pick_edge_seed(oracle, osn, vol, dims, cls, 1000 * seed)
+    print(f"\n{cls} on {dims}: ray seed {ray_seed}, at max_steps 512 hit / left / exhausted = "
+          f"{share['hit']:.3f} / {share['left']:.3f} / {share['exhausted']:.3f}")
+    assert len(starts) == N_RAYS
+    comp, rays = open_set(starts, dirs, dims)
+    assert not comp.any() and not rays.any()
+    for max_steps in EDGE_BUDGETS:
+        exp, c = at512 if max_steps == 512 else oracle_records(oracle, osn, starts, dirs, max_steps)
+        if max_steps == 512:
+            for k in edge_outcomes(cls, dims):
+                assert ((c == 0) if k == "hit" else (c != 0)).mean() >= 0.05, (cls, dims, k)
+        for bricks, h in scenes:
+            if bricks:
+                got = host_query(qh, h, 1, starts, dirs, max_steps)
+            else:
+                got, rec = host_query(qh, h, 0, starts, dirs, max_steps, recover=True)
+                hit = exp["material"] != 0
+                bad = np.flatnonzero((rec != exp["voxel"]).any(axis=1) & hit)
+                assert bad.size == 0, (cls, max_steps, bad[:5], rec[bad[:3]], exp["voxel"][bad[:3]], starts[bad[:3]], dirs[bad[:3]])
+            bad = planes_differ(got, exp)
+            assert bad.size == 0, (cls, bricks, max_steps, bad[:5], {k: v[bad[:3]] for k, v in got.items()}, {k: v[bad[:3]] for k, v in exp.items()},
+                                   starts[bad[:3]], dirs[bad[:3]])
+            miss = exp["material"] == 0
+            assert not got["pos"][miss].any() and not got["voxel"][miss].any() and not got["normal"][miss].any()
+            occ = host_query(qh, h, bricks, starts, dirs, max_steps, anyhit=True)["material"]
+            assert (occ == (exp["material"] != 0)).all(), (cls, bricks, max_steps)
+    for bricks, h in scenes:
+        (qh.thb_destroy if bricks else qh.th_destroy)(h)
+
+
+@pytest.mark.parametrize("mirrored", [False, True])
+def test_long_volume_recovery(qh, oracle, mirrored):
+    """The 1100 x 8 x 8 volume (its mirror image for rays along -x): 2 000 rays per direction that run 850 .. 1100 iterations before they hit.
+    At max_steps 1023, 1024, 1025 and 2000 VRT_TRAVERSAL_DF equals the oracle and query_recover_voxel, called on its RayInt whatever
+    the budget, finds the oracle's voxel for every hit.  What the recovery rounds, side * g + c, is within 1/2 of the steps really
+    taken at the budgets the look-up loop serves (<= 1024) -- the condition for rint to be right; the largest distance is printed.
+    Measured: 0.014526 along +x, 0.014465 along -x (the bound of csrc/vrt_query.h gives 0.063 for 1024 steps)."""
+    W, H, D = LONG_DIMS
+    vol = long_volume(mirrored)
+    starts, dirs = long_rays(2000, mirrored)
+    osn = oracle.OracleScene(vol, np.zeros((256, 5), np.float32))
+    h = qh.th_create(vol.ctypes.data, W, H, D)
+    worst = 0.0
+    hits = {}
+    for max_steps in LONG_BUDGETS:
+        exp, c, steps = oracle_records(oracle, osn, starts, dirs, max_steps, with_steps=True)
+        hit = exp["material"] != 0
+        hits[max_steps] = (hit, steps)
+        got, rec = host_query(qh, h, 0, starts, dirs, max_steps, recover=True)
+        bad = planes_differ(got, exp)
+        assert bad.size == 0, (max_steps, bad[:5], {k: v[bad[:3]] for k, v in got.items()}, {k: v[bad[:3]] for k, v in exp.items()})
+        bad = np.flatnonzero((rec != exp["voxel"]).any(axis=1) & hit)
+        assert bad.size == 0, (max_steps, bad[:5], rec[bad[:3]], exp["voxel"][bad[:3]])
+        if max_steps <= 1024:
+            x = np.zeros((len(starts), 3), np.float32); first = np.zeros((len(starts), 3), np.int32)
+            qh.qh_recover_args(h, len(starts), starts.ctypes.data, dirs.ctypes.data, max_steps, x.ctypes.data, first.ctypes.data)
+            err = np.abs(x.astype(np.float64) - (exp["voxel"] - first))[hit]
+            print(f"\nlong volume{' (mirrored)' if mirrored else ''}, max_steps {max_steps}: {int(hit.sum())} hits, "
+                  f"largest |side * g + c - n| = {err.max():.6f}")
+            worst = max(worst, float(err.max()))
+    print(f"long volume{' (mirrored)' if mirrored else ''}: largest recovery error at max_steps <= 1024: {worst:.6f}")
+    assert worst < 0.5
+    # composition, on the oracle alone: hits that need 850 .. 1100 iterations, rays that leave, and hits on either side of 1024
+    hit, steps = hits[2000]
+    assert (hit & (steps >= 850) & (steps <= 1100)).mean() >= 0.5 and (~hit).mean() >= 0.05
+    assert (hit & (steps <= 1023)).any() and (hit & (steps == 1024)).any() and (hit & (steps == 1025)).any() and (hit & (steps > 1025)).any()
+    for ms in (1023, 1024, 1025):
+        assert (hits[ms][0] == (hit & (steps <= ms))).all(), ms
+    qh.th_destroy(h)
+
+
+def test_edge_classes_standalone_under_sanitizers(qh, tmp_path):
+    """tests/native/query_edge_main.cpp built with AddressSanitizer + UBSan and run as a program of its own on rays of every class
+    (and of query_rays): exit status 0, and the records it writes equal the un-sanitised library's byte for byte."""
+    exe = os.path.join(NATIVE, "query_edge_main_san")
+    main = os.path.join(NATIVE, "query_edge_main.cpp")
+    if not os.path.exists(exe) or any(os.path.getmtime(exe) < os.path.getmtime(p) for p in DEPS + [main]):
+        # (the sanitizers' runtimes linked statically: the program then runs in whatever environment the suite is started in)
+        subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+                               "-ffp-contract=off", "-static-libasan", "-static-libubsan", "-o", exe, main])
+    dims = (40, 32, 56)
+    W, H, D = dims
+    vol = np.zeros((D, H, W), np.uint8)
+    qh.qe_fill(vol.ctypes.data, W, H, D)
+    assert 0.002 < (vol != 0).mean() < 0.10
+    batches = [query_rays(np.random.default_rng(5), 600, dims)] + [edge_rays(np.random.default_rng(50 + i), 600, dims, cls, vol) for i, cls in enumerate(EDGE_CLASSES)]
+    rays = np.ascontiguousarray(np.concatenate([np.concatenate([s, d], axis=1) for s, d in batches]), np.float32)
+    n = len(rays)
+    rays.tofile(tmp_path / "rays.f32")
+    r = subprocess.run([exe, str(tmp_path / "rays.f32"), str(tmp_path / "records.bin")] + [str(b) for b in EDGE_BUDGETS],
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-4000:]
+    got = np.fromfile(tmp_path / "records.bin", np.uint8)
+    hd, hb = qh.th_create(vol.ctypes.data, W, H, D), qh.thb_create(vol.ctypes.data, W, H, D)
+    want = []
+    for max_steps in EDGE_BUDGETS:
+        for bricks, h in ((0, hd), (1, hb)):
+            buf = np.zeros(n * 41, np.uint8)
+            w = qh.qe_records(h, bricks, n, rays.ctypes.data, max_steps, buf.ctypes.data)
+            assert w == n * (29 if bricks else 41)
+            want.append(buf[:w])
+    want = np.concatenate(want)
+    assert got.shape == want.shape and (got == want).all()
+    assert want[:n].any()                                                    # (the first plane: materials of the closest hits at 1024)
+    qh.th_destroy(hd); qh.thb_destroy(hb)
+
+
+def test_all_subnormal_direction_is_read_as_zero(qh, oracle):
+    """Outside the contract (include/vrt.h, (4)) but not left to chance: a direction whose three components are all zero or subnormal,
+    not all zero, is marched as (0, 0, 0) by query_ray itself, on the host as on the device -- the records are those of the
+    direction (0, 0, 0) from the same origin, for origins inside the volume (hit at once in a solid cell, else exhausted)."""
+    seed, dims, fill = VOLUMES[0]
+    W, H, D = dims
+    vol = make_volume(seed, dims, fill)
+    rng = np.random.default_rng(3)
+    n = 2000
+    starts = edge_rays(rng, n, dims, "zero", vol)[0]
+    inside = ((starts > 0) & (starts < np.array(dims, np.float32))).all(axis=1)
+    starts = np.ascontiguousarray(starts[inside])
+    bits = (rng.integers(0, 1 << 23, (len(starts), 3)) >> rng.integers(0, 23, (len(starts), 3))).astype(np.uint32)
+    bits[:, 0] |= 1
+    dirs = np.ascontiguousarray((bits | (rng.integers(0, 2, bits.shape).astype(np.uint32) << np.uint32(31))).view(np.float32))
+    assert (np.abs(dirs) < 2.0 ** -126).all() and (dirs != 0).any(axis=1).all()
+    zeros = np.zeros_like(dirs)
+    osn = oracle.OracleScene(vol, np.zeros((256, 5), np.float32))
+    exp, _ = oracle_records(oracle, osn, starts, zeros, 64)
+    assert (exp["material"] != 0).any() and (exp["material"] == 0).any()
+    for bricks, h in ((0, qh.th_create(vol.ctypes.data, W, H, D)), (1, qh.thb_create(vol.ctypes.data, W, H, D))):
+        got = host_query(qh, h, bricks, starts, dirs, 64)
+        assert planes_differ(got, exp).size == 0
+        assert planes_differ(host_query(qh, h, bricks, starts, zeros, 64), exp).size == 0
+        (qh.thb_destroy if bricks else qh.th_destroy)(h)

@@ -22,6 +22,18 @@ struct DdaState {
     float tspan;              // length of the ray inside the box, from where the march starts to where it leaves (0: never inside)
 };
 
+// float -> int as the device converts (v_cvt_i32_f32: saturating, NaN -> 0), spelled out for the host build, where a value
+// outside the int range is undefined behaviour: a far origin, or a direction 2^60 long (the +0.1 of boxIntersection is in units of
+// it), puts boxIntersection's point there
+VRT_HD int to_int_sat(float x)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    return (int)x;
+#else
+    return x != x ? 0 : x >= 2147483648.0f ? 2147483647 : x <= -2147483648.0f ? (-2147483647 - 1) : (int)x;
+#endif
+}
+
 // boxIntersection (frag:109-125) and the first mapPos (frag:135): everything needed to know whether the march can
 // leave the volume in iteration 0.
 VRT_HD void dda_entry(const VolumeView& v, f3 start, f3 dir, DdaState& s)
@@ -41,7 +53,7 @@ VRT_HD void dda_entry(const VolumeView& v, f3 start, f3 dir, DdaState& s)
         s.p = mk3(start.x + t * dir.x, start.y + t * dir.y, start.z + t * dir.z);
         s.mask = (uint32_t)(tnx == tmin) | ((uint32_t)(tny == tmin) << 1) | ((uint32_t)(tnz == tmin) << 2);
     }
-    s.mx = (int)floorf(s.p.x); s.my = (int)floorf(s.p.y); s.mz = (int)floorf(s.p.z);
+    s.mx = to_int_sat(floorf(s.p.x)); s.my = to_int_sat(floorf(s.p.y)); s.mz = to_int_sat(floorf(s.p.z));
     s.ivx = ivx; s.ivy = ivy; s.ivz = ivz;
     const float t0 = fmaxf(tmin, 0.0f);
     s.tspan = tmax >= t0 ? tmax - t0 : 0.0f;
@@ -85,13 +97,13 @@ VRT_HD void finish(const DdaState& s, uint32_t material, uint32_t mask, uint32_t
     r.material = material; r.mask = mask; r.fetches = fetches; r.dbg0 = 0; r.dbg1 = 0;
 }
 
-// rint(x) as an int; NaN -> 0 (what v_cvt_i32_f32 does; spelled out for the host build)
+// rint(x) as an int; saturating, NaN -> 0 (what v_cvt_i32_f32 does; spelled out for the host build: to_int_sat)
 VRT_HD int steps_taken(float x)
 {
 #if defined(__HIP_DEVICE_COMPILE__)
     return (int)rintf(x);
 #else
-    return x == x ? (int)rintf(x) : 0;
+    return to_int_sat(rintf(x));
 #endif
 }
 
@@ -107,7 +119,7 @@ VRT_HD int steps_signed(float dside, float g)
     asm("v_cvt_rpi_i32_f32 %0, %1" : "=v"(n) : "v"(q));
     return n;
 #else
-    return g == 0.0f ? 0 : (int)floorf(dside * g + 0.5f);
+    return g == 0.0f ? 0 : to_int_sat(floorf(dside * g + 0.5f));
 #endif
 }
 

@@ -58,6 +58,36 @@ VRT_HD void query_hit_record(const RayInt& r, f3 dir, int mx, int my, int mz, Qu
     h.vx = vx; h.vy = vy; h.vz = vz; h.nx = nx; h.ny = ny; h.nz = nz;
 }
 
+// Directions at the bottom of the float range.  A component is "small" when it is +-0 or subnormal (|d| < 2^-126).
+//  * All three small but not all zero: outside the contract (include/vrt.h: GLSL may flush subnormals to zero, and where it does
+//    not, the three sideDist are infinite or overflow within a few steps and the reference's loop steps every axis on the tie).
+//    query_ray takes the flushing reading, on the device and on the host: every component becomes a zero of its own sign, a direction whose march
+//    stands still.  Without it VRT_TRAVERSAL_DF would recover a position from an overflowed sideDist (inf * g, g subnormal, converts
+//    to INT_MAX) and index the fields with it.
+//  * One or two subnormal beside an ordinary one: in the contract.  query_subnormal_component says so; k_query sends the wave
+//    through VRT_TRAVERSAL_DF instead of the look-up loop.
+VRT_HD bool query_small(float d) { return (f2u(d) & 0x7F800000u) == 0u; }
+VRT_HD void query_flush_direction(f3& dir)
+{
+    if (query_small(dir.x) && query_small(dir.y) && query_small(dir.z))        // (each component keeps its sign: -0.0 stays -0.0)
+        dir = mk3(u2f(f2u(dir.x) & 0x80000000u), u2f(f2u(dir.y) & 0x80000000u), u2f(f2u(dir.z) & 0x80000000u));
+}
+VRT_HD bool query_subnormal_component(f3 dir)
+{
+    return (query_small(dir.x) && dir.x != 0.0f) || (query_small(dir.y) && dir.y != 0.0f) || (query_small(dir.z) && dir.z != 0.0f);
+}
+
+// Origins far from the volume.  The budget-free marches (df_prim_loop, brick_march_thresh) are entered by a wave none of whose rays
+// can reach max_steps, judged by tspan * (|dx| + |dy| + |dz|) * 1.001 + 8 (trace_df_fast).  tspan = tmax - t0 is a difference of two
+// t = (plane - origin) / d, each wrong by up to two ulps of its own size: in steps, up to about 2^-22 * 3 * |origin| along the
+// longest axis.  For |origin| <= 2^20 that is below one step, well inside the margin of 8; beyond, it can exceed it, and an
+// under-bounded ray would march past its budget.  k_query therefore clears df_thresh for a wave that holds such an origin.
+VRT_HD bool query_far_origin(f3 start)
+{
+    const float lim = 1048576.0f;
+    return !(fabsf(start.x) <= lim && fabsf(start.y) <= lim && fabsf(start.z) <= lim);
+}
+
 // One ray of a query.  TRAV: what VRT_TRAVERSAL_AUTO resolves to for the scene (VRT_TRAVERSAL_DF_FAST, _DF or _BRICK);
 // ANYHIT: traceRayHit (frag:198-202), only h.material is defined.  Wave-cooperative on the device like the march itself:
 // every lane of a wave calls it, a lane without a ray with one that ends before it starts (query_no_ray).
@@ -65,6 +95,7 @@ template <int TRAV, bool ANYHIT>
 VRT_HD void query_ray(const VolumeView& v, f3 start, f3 dir, uint32_t maxSteps, QueryHit& h)
 {
     RayInt r;
+    query_flush_direction(dir);
     trace_int<TRAV, const uint64_t*, false, ANYHIT>(v, v.occ2, v.occ3, start, dir, maxSteps, r);
     if (ANYHIT) { h.material = r.material; return; }
     int mx = r.mx, my = r.my, mz = r.mz;

@@ -94,7 +94,18 @@ __global__ __launch_bounds__(64) void k_query(const QueryParams P)
     // no lane leaves before the march: its loops vote over the whole wave (vrt_query.h, query_no_ray)
     if (!on) query_no_ray(start, dir);
     QueryHit h;
-    query_ray<TRAV, ANYHIT>(P.vol, start, dir, P.max_steps, h);
+    // The look-up loop recovers positions as side * g + c with g = dir: for a subnormal component that is a product of a huge
+    // and a subnormal factor in an instruction (v_mul_legacy_f32) whose treatment of subnormals the loop's bounds do not cover,
+    // so a wave that holds such a ray takes VRT_TRAVERSAL_DF, which only ever multiplies the sideDist travelled in a run -- exactly
+    // 0 for an axis that did not step (vrt_query.h, query_subnormal_component).  Wave-uniform: the march's loops vote.
+    // ... and a wave that holds an origin too far away for the bound that admits a wave to the budget-free march does not take it
+    // (vrt_query.h, query_far_origin)
+    VolumeView vol = P.vol;
+    if (__any(query_far_origin(start)) != 0) vol.df_thresh = 0u;
+    if (TRAV == VRT_TRAVERSAL_DF_FAST && __any(query_subnormal_component(dir)) != 0)
+        query_ray<VRT_TRAVERSAL_DF, ANYHIT>(vol, start, dir, P.max_steps, h);
+    else
+        query_ray<TRAV, ANYHIT>(vol, start, dir, P.max_steps, h);
     if (!on) { h.material = 0u; h.pos = mk3(0.0f, 0.0f, 0.0f); h.vx = h.vy = h.vz = 0; h.nx = h.ny = h.nz = 0; }
 
     if (ANYHIT) {

@@ -1,6 +1,6 @@
 // Host build of csrc/vrt_brick_edit.h for tests/test_brick_edit_cpu.py: the statements the brick-scene edits rest on, checked
 // against a brute-force build.  brick_edit_sweep() draws brick lattices, voxel contents and boxes, builds by the definitions
-// (vrt_traverse.h, VolumeView::bcoarse / bfine / bentry; k_brick_fine) the occupancy, the per-voxel clearances of the occupied
+// (vrt_march_brick.h brick_clear, VolumeView::bcoarse / bfine / bentry; k_brick_fine) the occupancy, the per-voxel clearances of the occupied
 // bricks, the eight coarse fields with their open bits and the packed entries before and after the edit, and checks that
 //   * the fine bytes of every brick outside F are the same, and the ids and the occupancy of every brick outside T;
 //   * an edit that changes no brick's occupancy changes no coarse byte, no open bit and no entry;

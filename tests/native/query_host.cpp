@@ -1,4 +1,4 @@
-// query_host.cpp -- TEST HELPER: the ray queries' per-ray code (csrc/vrt_query.h over csrc/vrt_traverse.h) compiled for the host,
+// query_host.cpp -- TEST HELPER: the ray queries' per-ray code (csrc/vrt_query.h over csrc/vrt_traverse.h and the marches, csrc/vrt_march_*.h) compiled for the host,
 // so that the record a query returns can be compared with the oracle's vo_trace_ray without a GPU.  The volumes are built by
 // traverse_host.cpp's builders (th_create: dense fields, thb_create: bricks).  Built on demand by tests/test_ray_query_cpu.py.
 #include "../../include/vrt.h"

@@ -1,4 +1,4 @@
-// traverse_host.cpp -- TEST HELPER: compiles the product's traversal header (csrc/vrt_traverse.h) for the
+// traverse_host.cpp -- TEST HELPER: compiles the product's traversal header (csrc/vrt_traverse.h over csrc/vrt_march_*.h) for the
 // host so that its three strategies can be compared with the oracle on millions of rays without a GPU.
 // Built on demand by tests/test_traverse_host.py with g++; never linked into libvrt_hip.so.
 #include <cstdint>
@@ -44,7 +44,7 @@ void* th_create(const uint8_t* vox, int W, int H, int D)
     // clearance fields: per octant three one-sided 1-D min-max passes (same definition as k_df_pass, written independently)
     {
         const int CAP = 127;
-        size_t stride = df_field_bytes(W, H, D);                 // padded x-fastest fields (vrt_traverse.h df_index)
+        size_t stride = df_field_bytes(W, H, D);                 // padded x-fastest fields (vrt_volume.h df_index)
         h->df.assign(8 * stride, 0);
         std::vector<uint8_t> a((size_t)W * H * D), b((size_t)W * H * D);
         for (int o = 0; o < 8; o++) {

@@ -167,7 +167,7 @@ def test_config5_sparse_bricks_long_budget(vrt, oracle, engine):
 
 def test_volume_past_the_32bit_field_limit(vrt, oracle, engine):
     """Eight clearance fields of an 832^3 volume total 4.6 GiB: the traversal switches to 64-bit field indexing
-    (vrt_traverse.h df_small).  Same planes as the dense traversal; bands against the oracle."""
+    (vrt_volume.h df_small).  Same planes as the dense traversal; bands against the oracle."""
     N = 832
     vol = vrt.synthetic.sparse_bricks(N, 8, 0.004, seed=9)
     pal = metallic_palette(vrt)

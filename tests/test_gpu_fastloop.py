@@ -1,4 +1,4 @@
-"""The hand-written look-up loop (vrt_traverse.h trace_df_fast; chosen by the host for AUTO / DF when the budgets are <= 1024
+"""The hand-written look-up loop (vrt_march_fast.h trace_df_fast; chosen by the host for AUTO / DF when the budgets are <= 1024
 and no hit_voxel plane is asked for) against the oracle and against the general loop (context option fast_loop = 0): primary rays and the
 secondary rays of the megakernel / split kernels (partly filled waves), ties, axis-parallel rays, cameras inside the volume
 and on lattice points, rays that miss the box, budgets of 1 ... 1024, ragged frame sizes, batches, and a randomised sweep."""

@@ -3,7 +3,7 @@ long volume on either side of VRT_TRAVERSAL_AUTO's switch at max_steps 1024 / 10
 statement in numpy, and a pick from a lattice camera position.  tests/test_ray_query_cpu.py holds the same classes against the
 oracle on the host build first; this file is what the host build cannot reach -- the hand-written look-up loops.
 
-What the look-up loops (csrc/vrt_traverse.h: trace_df_fast over df_fast_loop / df_prim_loop) index, class by class.  The set-up forms
+What the look-up loops (csrc/vrt_march_fast.h: trace_df_fast over df_fast_loop / df_prim_loop) index, class by class.  The set-up forms
 ONE first index, idx0 = bias + oct * stride + df_index(first mapPos) when the first mapPos is inside the volume, else the sentinel
 (the 0xFF byte behind the ninth field: the lane is finished before it starts, its deltas and increments are 0).  Every later index is
 either the previous one moved by incx = +-1, incy = +-pw, incz = +-pwh per step of a short run (integers, exact), or idx0 + nx +

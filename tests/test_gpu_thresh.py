@@ -1,4 +1,4 @@
-"""Long runs by threshold (vrt_traverse.h df_prim_loop / brick_march_thresh; context option thresh_runs): every axis steps on its
+"""Long runs by threshold (vrt_march_fast.h df_prim_loop / vrt_march_brick.h brick_march_thresh; context option thresh_runs): every axis steps on its
 own while its sideDist is below the lane's threshold -- the same fp32 additions per lane as the shader's merged loop, so every
 plane a caller of the product gets must come out bit for bit as with thresh_runs = 0 and as the oracle computes it.
 The loop keeps no iteration count and is entered only by waves whose rays provably cannot reach the budget: the cases below sit

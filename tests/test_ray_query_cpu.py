@@ -16,7 +16,8 @@ SRC = os.path.join(NATIVE, "query_host.cpp")
 LIB = os.path.join(NATIVE, "libquery_host.so")
 DEPS = [SRC, os.path.join(NATIVE, "traverse_host.cpp"), os.path.join(ROOT, "include", "vrt.h")] + \
        [os.path.join(ROOT, "voxel-raytracing_amd", "csrc", h) for h in
-        ("vrt_query.h", "vrt_traverse.h", "vrt_volume.h", "vrt_dda.h", "vrt_spec.h")]
+        ("vrt_query.h", "vrt_traverse.h", "vrt_march_df.h", "vrt_march_fast.h", "vrt_march_brick.h", "vrt_march_literal.h",
+         "vrt_volume.h", "vrt_dda.h", "vrt_spec.h")]
 
 N_RAYS = 5000
 BUDGETS = (512, 64, 37, 1)

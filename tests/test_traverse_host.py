@@ -12,7 +12,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "tests", "native", "traverse_host.cpp")
 LIB = os.path.join(ROOT, "tests", "native", "libtraverse_host.so")
 HDRS = [os.path.join(ROOT, "voxel-raytracing_amd", "csrc", h) for h in
-        ("vrt_traverse.h", "vrt_volume.h", "vrt_dda.h", "vrt_spec.h")]
+        ("vrt_traverse.h", "vrt_march_df.h", "vrt_march_fast.h", "vrt_march_brick.h", "vrt_march_literal.h",
+         "vrt_volume.h", "vrt_dda.h", "vrt_spec.h")]
 
 
 @pytest.fixture(scope="module")

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Lint of the hand-written gfx950 assembly blocks (csrc/vrt_traverse.h: the four look-up loops and axis_run; csrc/vrt_dda.h: the DDA
+"""Lint of the hand-written gfx950 assembly blocks (csrc/vrt_march_fast.h: the four look-up loops; csrc/vrt_march_brick.h: axis_run; csrc/vrt_dda.h: the DDA
 iterations and the wave votes; and whatever else the device objects include), on the
 PREPROCESSED source of every device object (each distinct statement once), so that every macro-built variant of a block (the counting twins, the prefetching form ...) is seen
 as the compiler sees it.  The compiler keeps its own values out of the registers a block declares clobbered and out of its

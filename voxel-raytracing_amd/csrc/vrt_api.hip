@@ -465,7 +465,7 @@ static int launch_plan(const DevOptions& opt, const vrt_scene* s, const Launch& 
     // 3.46 against 3.25 ms on config 5 -- and 1 % faster on the Mandelbulb; context option packed_bounces = 2 forces it everywhere)
     p.packed_chain = (opt.packed_bounces && st->ao_samples <= 0xFFFFu && (!s->bricks || opt.packed_bounces >= 2)) ? 1 : 0;
     // default traversal and budgets the recovery of positions from sideDist is exact for: the hand-written look-up loop
-    // (vrt_traverse.h trace_df_fast) for every ray of the frame
+    // (vrt_march_fast.h trace_df_fast) for every ray of the frame
     {
         const bool want = opt.fast_loop != 0;                             // development switch
         const bool df = st->traversal == VRT_TRAVERSAL_AUTO || st->traversal == VRT_TRAVERSAL_DF;

@@ -8,7 +8,7 @@
 // vrt_post.hip.)  Compiled in four parts, -DVRT_K1_PART=0..3: the list behind launch_shade_t.
 // This file is the kernels and their launch code.  What they are made of: vrt_shade.h (traceRay, the secondary rays, colorHit,
 // colorMainRay -- and, at its head, what a kernel that calls them owes them), vrt_frame_slot.h (the frame slot from the kernel
-// arguments or the table, the workgroup -> tile map, the colour store), vrt_traverse.h (the march).
+// arguments or the table, the workgroup -> tile map, the colour store), vrt_traverse.h (the dispatch over the marches, vrt_march_*.h).
 //
 // A wave owns an 8x8 pixel block so that its 64 rays stay spatially coherent; the default (clearance-field)
 // traversal runs one wave per workgroup, the LDS-staged ones 16x16 tiles of four waves.  Rays are generated in-kernel

@@ -6,7 +6,7 @@
 #include <stdint.h>
 
 #include "../../include/vrt.h"
-#include "vrt_volume.h"     // VolumeView and the traversal constants; the march itself (vrt_traverse.h) is included by the kernels that run it
+#include "vrt_volume.h"     // VolumeView and the traversal constants; the march itself (vrt_traverse.h over vrt_march_*.h) is included by the kernels that run it
 #include "vrt_sky.h"
 #include "vrt_tags.h"
 #include "vrt_span.h"

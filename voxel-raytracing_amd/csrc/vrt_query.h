@@ -27,7 +27,7 @@ struct QueryHit {
 // the loop itself computes for every look-up: per axis n = rint(side * g + c) steps since the start of the ray, g = dir
 // (1 / +-deltaDist to within an ulp; 0 for an axis the ray cannot step along) and c = -side0 * g, side0 the first sideDist
 // (frag:142-144, recomputed here from the first mapPos as dda_rest does).  |error of n| <= (n^2 + 3n) 2^-24, below 1/16
-// for the budgets that loop accepts (maxSteps <= 1024; vrt_traverse.h, df_fast_loop).
+// for the budgets that loop accepts (maxSteps <= 1024; vrt_march_fast.h, df_fast_loop).
 VRT_HD void query_recover_voxel(const RayInt& r, f3 dir, int& mx, int& my, int& mz)
 {
     const float kInf = u2f(0x7F800000u);

@@ -1,4 +1,4 @@
-// vrt_query.hip -- ray queries: the march of vrt_traverse.h fed from a ray buffer (vrt_trace_rays, vrt_occluded_rays) or
+// vrt_query.hip -- ray queries: the marches behind vrt_traverse.h (vrt_march_*.h) fed from a ray buffer (vrt_trace_rays, vrt_occluded_rays) or
 // from pixel coordinates (vrt_pick_pixels) instead of a frame's pixels.  An object of its own: the render stage's kernels
 // (vrt_device.hip) do not see this file.
 //

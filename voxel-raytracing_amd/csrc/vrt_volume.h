@@ -2,7 +2,7 @@
 // data: ids, occupancy pyramid, clearance fields, bricks), RayInt, the statistics hooks, the bit casts, the occupancy look-ups
 // and the layout of the clearance fields (df_index and the conditions of 32-bit indexing).  No march and no assembly: this is
 // the header for code that builds or hands over a VolumeView without tracing through it (vrt_internal.h, the scene build,
-// the C-ABI objects).  The marches: vrt_traverse.h.
+// the C-ABI objects).  The marches: vrt_march_*.h, behind vrt_traverse.h.
 #pragma once
 
 #include "vrt_spec.h"

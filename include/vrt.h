@@ -397,7 +397,9 @@ int  vrt_camera_rays(vrt_ctx* ctx, const vrt_ray_camera* camera, int32_t W, int3
                                    * edge-stopping weights as ONE hardware exponential, exp2(-(dc2*kc + dn2*kn + dp2*kp)), and divide
                                    * by multiplying with the hardware reciprocal -- the shader's own freedom (GLSL exp / division are
                                    * not correctly rounded either).  Stated bound against the exact mode and the oracle: at most ONE
-                                   * RGBA8 code per channel per pass (tests/test_gpu_denoise.py); the exact mode stays the default. */
+                                   * RGBA8 code per channel per pass (tests/test_gpu_denoise.py), non-finite positions included: a NaN
+                                   * position distance weighs 1 here as in the exact mode (tests/test_gpu_denoise_shard.py); the exact
+                                   * mode stays the default. */
 
 /* DenoiserSettings, voxel_render_settings.hpp:21-29. */
 typedef struct vrt_denoiser_settings {
@@ -415,7 +417,14 @@ void vrt_denoiser_settings_default(vrt_denoiser_settings* s);
  * denoiser_stage.cpp:143-154.  target0/target1 are the two RGBA8 ping-pong images (_colorTargets);
  * *result receives the one holding the final image (color_in itself when iterations == 0).
  * With a shard, only the rank's own rows of the final image are valid; the guide planes must already
- * hold `vrt_denoise_halo_rows()` valid rows either side of every owned strip. */
+ * hold `vrt_denoise_halo_rows()` valid rows either side of every owned strip.  A sharded call READS the rank's
+ * own rows +- vrt_denoise_halo_rows(), clipped to the frame, of the three input planes and nothing beyond (what
+ * the other rows hold never reaches an own row of the result); it WRITES, in both targets, own rows +- the halo
+ * at most (pass i: own rows +- the reaches of the later passes) and no other row.  A rank without a strip
+ * launches nothing.  The halo may exceed strip_rows (16-row strips, five passes at step width 2: 25 rows): the
+ * extended regions of a rank's own strips then overlap, the overlap is written twice with equal values and the
+ * result is the same -- only vrt_pack_halo, which sends rows of ONE neighbouring strip, refuses such a halo, so
+ * the caller must bring those rows in another way. */
 int  vrt_denoise(vrt_ctx* ctx, int32_t W, int32_t H, const vrt_denoiser_settings* ds,
                  const uint8_t* color_in, const int8_t* normal8, const float* position,
                  uint8_t* target0, uint8_t* target1, const vrt_shard* shard, const uint8_t** result);

@@ -3,6 +3,8 @@ range the guard admits, step widths, modes, pass counts, and G-buffers of severa
 noise, flat patches, hard edges, hostile random codes, non-finite positions).  Every case must be bit-identical.
 
     python tests/fuzz_denoise.py [cases] [seed]        (on a GPU box; tests/test_gpu_denoise.py runs a short sweep of it)
+    python tests/fuzz_denoise.py --sharded [cases] [seed]     the same draws through vrt_denoise with a vrt_shard, every rank on a frame
+                                                              poisoned beyond its halo (tests/test_gpu_denoise_shard.py runs 30)
 """
 import os
 import sys
@@ -74,10 +76,52 @@ def run(vrt, oracle, engine, cases, seed, verbose=False):
     return verified, redone
 
 
+def run_sharded(vrt, oracle, engine, cases, seed, verbose=False):
+    """The sharded denoiser: the draws of run(), then a shard (2 .. 5 ranks, strips of 16 .. 64 rows) and a poison.  Every rank gets
+    the frame poisoned beyond its halo (tests/denoise_shard_common.py); its own rows must be the oracle's image of the TRUE frame,
+    and no row beyond the halo may be written.  No draw is left out: a halo larger than a strip is served like any other.
+    Returns the number of ranks checked."""
+    import denoise_shard_common as dsc
+    rng = np.random.default_rng(seed)
+    ranks = 0
+    for case in range(cases):
+        W, H = int(rng.integers(1, 300)), int(rng.integers(1, 200))
+        kind = int(rng.integers(0, 3))
+        truth = make_gbuffer(rng, W, H, kind)
+        iterations = int(rng.integers(1, 5))
+        step = float(rng.choice([0.0, 1.0, 1.0, 2.0, 2.0, 2.0, 4.0, 1.5]))
+        mode = int(rng.integers(0, 2))
+        phis = tuple(float(10.0 ** rng.uniform(-3.5, 3.5)) for _ in range(3)) if rng.random() < 0.7 else (20.4, 0.01, 0.1)
+        nranks, strip_rows = int(rng.integers(2, 6)), int(rng.choice([16, 32, 48, 64]))
+        poison = dsc.POISONS[int(rng.integers(0, 2))]
+        st = vrt.VoxelRenderSettings(targetResolution=(W, H))
+        d = st.denoiserSettings
+        d.iterations, d.stepWidth, d.mode = iterations, step, mode
+        d.phiColor0, d.phiNormal0, d.phiPos0 = phis
+        halo = dsc.halo_rows(iterations, step)
+        exp = oracle.denoise(*truth, iterations=iterations, phi_color0=phis[0], phi_normal0=phis[1], phi_pos0=phis[2], step_width0=step, mode=mode)
+        what = f"case {case} (seed {seed}): {W}x{H} kind {kind} iterations {iterations} step {step} mode {mode} phis {phis} shard ({nranks}, {strip_rows}) poison {poison}"
+        if verbose and case % 100 == 0:
+            print(what, flush=True)
+        for rank in range(nranks):
+            own = dsc.owned_rows(H, rank, nranks, strip_rows)
+            got = dsc.run_rank(vrt, engine, st, dsc.poisoned(truth, H, rank, nranks, strip_rows, halo, poison, rng), rank, nranks, strip_rows, halo, rng)
+            bad = int((got[own] != exp[own]).sum())
+            assert bad == 0, f"{what}: rank {rank}: {bad} bytes differ on own rows"
+            ranks += 1
+    return ranks
+
+
 if __name__ == "__main__":
     import voxel_raytracing_amd as vrt
     from oracle import oracle
-    cases = int(sys.argv[1]) if len(sys.argv) > 1 else 300
-    seed = int(sys.argv[2]) if len(sys.argv) > 2 else 1
+    sharded = "--sharded" in sys.argv
+    args = [a for a in sys.argv[1:] if a != "--sharded"]
+    cases = int(args[0]) if len(args) > 0 else 300
+    seed = int(args[1]) if len(args) > 1 else 1
+    if sharded:
+        n = run_sharded(vrt, oracle, vrt.Engine(0), cases, seed, verbose=True)
+        print(f"{cases} sharded cases, {n} ranks: own rows bit-identical to the oracle, nothing written beyond the halo")
+        sys.exit(0)
     v, r = run(vrt, oracle, vrt.Engine(0), cases, seed, verbose=True)
     print(f"{cases} cases bit-identical; {v} passes took the verified form, {r} pixels were evaluated twice")

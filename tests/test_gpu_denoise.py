@@ -2,6 +2,7 @@
 import numpy as np
 import pytest
 
+from denoise_shard_common import _hostile_gbuffer
 from helpers import camera_push, metallic_palette
 
 pytestmark = pytest.mark.gpu
@@ -120,25 +121,6 @@ def test_fast_denoise_single_weighted_pass_bound(vrt, oracle, engine):
 # ---- the verified pass: exact output from a cheap evaluation + a literal one where the cheap one cannot vouch ----------------
 # (csrc/vrt_denoise_bound.h).  The default for whole-frame weighted passes with an integral tap offset; "denoise_verified" = 0 has
 # the exact kernels compute every pixel.
-
-def _hostile_gbuffer(rng, W, H):
-    """Random codes in every channel (alpha and w included, SNORM -128 too), positions clustered so that the weights are
-    neither 0 nor 1, a sprinkling of equal neighbours, huge, infinite and NaN positions."""
-    color = rng.integers(0, 256, (H, W, 4), dtype=np.uint8)
-    flat = rng.random((H, W, 1)) < 0.3
-    color = np.where(flat, color // 64 * 64, color).astype(np.uint8)             # flat patches: sums whose mean is a code exactly
-    nrm = rng.choice(np.array([-128, -127, -90, -73, -1, 0, 1, 73, 90, 127], np.int8), (H, W, 4))
-    nrm = np.where(rng.random((H, W, 1)) < 0.5, np.array([0, 127, 0, 0], np.int8), nrm).astype(np.int8)
-    pos = rng.uniform(0, 64, (H, W, 4)).astype(np.float32)
-    pos = (np.round(pos * 4) / 4 + rng.normal(0, 0.05, (H, W, 4))).astype(np.float32)
-    pos[..., 3] = np.where(rng.random((H, W)) < 0.9, 0.0, pos[..., 3])
-    odd = rng.random((H, W))
-    pos[odd < 0.002] = np.float32(np.nan)
-    pos[(odd >= 0.002) & (odd < 0.004)] = np.float32(np.inf)
-    pos[(odd >= 0.004) & (odd < 0.006)] = np.float32(-3e19)
-    pos[(odd >= 0.006) & (odd < 0.3)] = 0.0                                       # sky
-    return color, nrm, pos
-
 
 @pytest.mark.parametrize("mode", [0, 1])
 @pytest.mark.parametrize("size", [(200, 120), (333, 61), (64, 8), (70, 13), (1, 1), (5, 3), (130, 2)])

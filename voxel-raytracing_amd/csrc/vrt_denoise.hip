@@ -147,6 +147,9 @@ __global__ __launch_bounds__(256) void k_denoise(const DenoiseParams P)
 {
     int px = blockIdx.x * 64 + (threadIdx.x & 63);
     int r = blockIdx.y * 4 + (threadIdx.x >> 6);
+    // (the launch rounds the rows up to blocks of 4: a row past the last local strip's is no row of this rank, though strip_row, which
+    // does not know the strip count, may find the extension of the next strip of its stride inside the frame)
+    if (r >= P.sh.n_local_strips * (P.sh.strip_rows + 2 * P.extend)) return;
     int py = strip_row(P.sh, P.extend, r, P.H);
     if (py < 0 || px >= P.W) return;
     reinterpret_cast<uchar4*>(P.color_out)[(size_t)py * (size_t)P.W + (size_t)px] = denoise_pixel<PHI_INF>(P, px, py);
@@ -344,7 +347,8 @@ __global__ __launch_bounds__(256) void k_denoise_lds(const DenoiseParams P, int 
             // three polynomial exponentials
             const float4 op = lp[ci], on = ln[ci];
             const float o_p[4] = {op.x, op.y, op.z, op.w}, o_n[4] = {on.x, on.y, on.z, on.w};
-            const float e = __builtin_fmaf(dist2_4(s_p, o_p), P.kp, __builtin_fmaf(dist2_4(s_c, o_c), P.kc, fmaxf(dist2_4(s_n, o_n), 0.0f) * P.kn));
+            // (a NaN position distance -- NaN or inf - inf -- weighs 1 in the shader, fminf(exp(NaN), 1): its term of the one exponent is 0)
+            const float e = __builtin_fmaf(fmaxf(dist2_4(s_p, o_p), 0.0f), P.kp, __builtin_fmaf(dist2_4(s_c, o_c), P.kc, fmaxf(dist2_4(s_n, o_n), 0.0f) * P.kn));
             w = __builtin_amdgcn_exp2f(-e);
         } else if (!PHI_INF) {
             const float4 op = lp[ci];
@@ -465,7 +469,8 @@ __global__ __launch_bounds__(256) void k_denoise_fast(const DenoiseParams P, int
             const float4 oc = lc[ci], op = lp[ci], on = ln[ci];
             // the kernel weight rides in the exponent: w * kern = exp2(-(e - log2 kern))
             const float lk = r2_of(tx, ty) == 0 ? 0.0f : (r2_of(tx, ty) == 1 ? 0.18033688011112042f : 0.36067376022224085f);   // -log2(G1), -log2(G2)
-            const float e = __builtin_fmaf(dist2_pk(sp, op), P.kp, __builtin_fmaf(dist2_pk(sc, oc), kc, __builtin_fmaf(dist2_pk(sn, on), kn, SHIPPED ? shipped_lk(i) : lk)));
+            // (a NaN position distance -- NaN or inf - inf -- weighs 1 in the shader, fminf(exp(NaN), 1): its term of the one exponent is 0)
+            const float e = __builtin_fmaf(fmaxf(dist2_pk(sp, op), 0.0f), P.kp, __builtin_fmaf(dist2_pk(sc, oc), kc, __builtin_fmaf(dist2_pk(sn, on), kn, SHIPPED ? shipped_lk(i) : lk)));
             const float wk = __builtin_amdgcn_exp2f(-e);
             const v2f w2 = {wk, wk};
             s01 = __builtin_elementwise_fma((v2f){oc.x, oc.y}, w2, s01);
@@ -689,6 +694,7 @@ __global__ __launch_bounds__(256) void k_denoise_ver(const DenoiseParams P, int 
             const float dx = sp.x - op.x, dy = sp.y - op.y, dz = sp.z - op.z;
             float dp = __builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx));
             if (W4) { const float dw = sp.w - op.w; dp = __builtin_fmaf(dw, dw, dp); }
+            if (!FLAG) dp = fmaxf(dp, 0.0f);                 // VRT_DENOISE_FAST, nothing redone: a NaN distance weighs 1, as in the shader's fminf(exp(NaN), 1)
             // the kernel weight rides in the exponent: w * kern = exp2(-(e + -log2 kern))
             const float lk = SHIPPED ? shipped_lk(i) : (r2_of(tx, ty) == 1 ? 0.18033688011112042f : 0.36067376022224085f);
             const float e = __builtin_fmaf(dp, kp, __builtin_fmaf((float)dc, kc, __builtin_fmaf((float)dn, kn, lk)));
@@ -901,6 +907,7 @@ __global__ __launch_bounds__(64 * R) void k_denoise_pair(const DenoiseParams P, 
             const float dx = s4.x - o4.x, dy = s4.y - o4.y, dz = s4.z - o4.z;
             float dp = __builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx));
             if (W4) { const float dw = sw - lw[ci]; dp = __builtin_fmaf(dw, dw, dp); }
+            if (!FLAG) dp = fmaxf(dp, 0.0f);                 // VRT_DENOISE_FAST, nothing redone: a NaN distance weighs 1, as in the shader's fminf(exp(NaN), 1)
             const float lk = (k == 0 || k == 2) ? 0.18033688011112042f : 0.36067376022224085f;      // -log2(G1), -log2(G2)
             const float e = __builtin_fmaf(dp, kp, __builtin_fmaf(dc, kc, __builtin_fmaf((float)dn, kn, lk)));
             wf[k] = __builtin_amdgcn_exp2f(-e);

@@ -162,6 +162,7 @@ int  vrt_ctx_synchronize(vrt_ctx* ctx);                     /* device.waitIdle()
  *                                     k_denoise_pair launch), "denoise_th16" (0: the tolerance kernel's 64 x 16 tiles
  *                                     are an experiment), and the tests' handles on the verified pass "denoise_guard_div8" (0), "denoise_count" (0)
  *   vrt_trace_rays / vrt_occluded_rays / vrt_pick_pixels:  "thresh_runs" (1) and nothing else
+ *   vrt_render_rays:                  "thresh_runs" (1), "ao_batch" (1) and nothing else
  *   scene creation:                   "open_cells" (1), "df_prefetch" (1), "df_own" (1)
  * The environment seeds them ONCE, at vrt_ctx_create (VRT_TILE_TAGS=0, VRT_SKY_FAST=0, ...); nothing on the render path calls
  * getenv.  Values are non-negative integers (the switches: 0 / 1; a negative value is stored as 0).  Unknown name: VRT_ERR_INVALID. */
@@ -368,8 +369,8 @@ int  vrt_pick_pixels(vrt_ctx* ctx, const vrt_scene* scene, const vrt_push* push,
  * vrt_camera_rays writes the primary rays of a W x H frame under one of three camera models into the two planes of 3 packed
  * floats per ray that vrt_trace_rays and vrt_occluded_rays take: which voxel every pixel of a wide-angle, an orthographic or a
  * panoramic view sees, or whether it sees one, is then one more call.  csrc/vrt_raygen.h defines the three models step by step in
- * fp32; the GPU result equals it bit for bit.  (The rays are traced, not shaded: the geometry stage's G-buffer is still drawn by
- * the built-in camera only.) */
+ * fp32; the GPU result equals it bit for bit.  vrt_render_rays (below) shades such rays: the geometry stage's full G-buffer for any
+ * camera. */
 #define VRT_CAMERA_PERSPECTIVE  0   /* main()'s pinhole with a field of view: tan_half = tan(horizontal FOV / 2); 1.0f is the reference's camera bit for bit */
 #define VRT_CAMERA_ORTHOGRAPHIC 1   /* parallel rays along cam_dir; half_width: half the view's width in voxels */
 #define VRT_CAMERA_PANORAMA     2   /* equirectangular around cam_pos, the inverse of skyColor's mapping (frag:98-105); the basis is not used */
@@ -389,6 +390,37 @@ typedef struct vrt_ray_camera {
  * pointer, an unknown model, a tan_half (perspective) or half_width (orthographic) that is not finite and positive, a
  * degenerate basis (non-finite position or jitter; perspective and orthographic: a zero or non-finite determinant). */
 int  vrt_camera_rays(vrt_ctx* ctx, const vrt_ray_camera* camera, int32_t W, int32_t H, float* origins, float* dirs);
+
+/* ---- the G-buffer of caller-supplied rays (no reference analogue: the reference draws main()'s pinhole only) -------------------
+ * The G-buffer of a W x H frame whose primary rays the caller supplies: ray py * W + px is pixel (px, py)'s.  origins, dirs: DEVICE
+ * pointers to W * H x 3 packed floats (what vrt_camera_rays writes and vrt_trace_rays takes), 4-byte aligned, overlapping no
+ * output plane.  Every plane of `out` holds what main() (voxel_volume.frag:312-346) writes for pixel (px, py) of frame index
+ * `frame` if that pixel's primary ray is (origin, dir):
+ *   the primary record  vrt_trace_rays' record of the ray with settings->max_steps, bit for bit: the same open set, the same
+ *                       reading of an all-small direction as (0, 0, 0), the same traversal (the rule for budgets above 1024 included)
+ *   position            (pos, 0);  depth = length(pos - origin), 0 on a miss;  mask8 = 230 on a hit, 0 on a miss;  motion = 0
+ *   normal8             the SNORM8 codes of normalize(-mask * rayStep), 0 on a miss
+ *   hit_id, hit_voxel, hit_mask   material id, hit cell and final DDA mask of the primary hit (0 on a miss)
+ *   color8 / color_f    a hit: colorMainRay (frag:267-307) with RayHit.dir = the direction as given -- AO, shadow and bounce rays
+ *                       as vrt_render_geometry traces them; the blue-noise texel is pixel (px, py)'s (its coordinate does not
+ *                       depend on W or H), the sample offset is frame % 32.  A miss: skyColor(dir).
+ * Directions are used as given.  vrt_camera_rays delivers unit vectors; a direction that is not one is traced exactly as
+ * vrt_trace_rays traces it, and its sky texel, its reflection and its AO are whatever the formulas give for it.  Only FINITE
+ * directions are in the contract.  The sky look-up of a miss cannot fault on any value (a NaN coordinate reaches texel 0), but a
+ * metallic hit reflects the direction into a bounce ray, and a bounce ray made from a NaN, an infinity or a subnormal component
+ * is one vrt_trace_rays' contract does not cover either: what such a pixel holds is pinned by nothing, and the path it takes
+ * through the shading kernel has not been examined.
+ * VRT_ERR_UNSUPPORTED: a non-NULL steps_primary, steps_total, rays_total or color8_strips; any bit of settings->flags; a
+ * settings->traversal other than VRT_TRAVERSAL_AUTO.
+ * VRT_ERR_INVALID, before any device work: a NULL argument, W or H < 1 or beyond vrt_render_geometry's frame limits (2^28 pixels
+ * and more included), max_steps == 0, max_bounces > VRT_MAX_BOUNCES, no output plane at all, a misaligned ray plane, a ray plane
+ * that overlaps an output plane.
+ * Asynchronous on the context's stream.  There is no vrt_shard: a rank of a multi-GPU frame passes the rays of its own rows as a
+ * frame of that many rows.  Two kernels, the split form of the geometry stage over a ray buffer: the primary march of
+ * vrt_trace_rays writes the planes, the misses' colour and one 16-byte record per hit; the shading kernel runs one lane per hit.
+ * Of the context options "thresh_runs" and "ao_batch" are honoured and nothing else. */
+int  vrt_render_rays(vrt_ctx* ctx, const vrt_scene* scene, int32_t W, int32_t H, const float* origins, const float* dirs,
+                     uint32_t frame, const vrt_settings* settings, const vrt_frame* out);
 
 /* ---- denoiser stage -------------------------------------------------------------------------- */
 #define VRT_DENOISE_CANONICAL  0  /* the intended 9-tap a-trous filter                               */

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Register budget of the hand-scheduled kernels (csrc: the parts of vrt_device.hip, vrt_denoise.hip, vrt_scene_edit.hip, vrt_query.hip, vrt_reproject.hip, vrt_upsample.hip, vrt_rays.hip), checked
+"""Register budget of the hand-scheduled kernels (csrc: the parts of vrt_device.hip, vrt_denoise.hip, vrt_scene_edit.hip, vrt_query.hip, vrt_reproject.hip, vrt_upsample.hip, vrt_rays.hip, vrt_render_rays.hip), checked
 at build time.
 
 K1's look-up loop pins physical registers and the kernel sits at two occupancy cliffs that the compiler's own remark does
@@ -72,12 +72,22 @@ BUDGET = {
     "k_upsampleENS_14UpsampleParamsE": ("temporal upsampling", 64, 80, 0),
     # ray generation for caller-side cameras (vrt_rays.hip): a stream of 24 B per pixel; eight waves per SIMD, no scratch (15 VGPRs, 35 SGPRs)
     "k_camera_raysENS_12RayCamConstsE": ("ray generation, three camera models", 32, 48, 0),
+    # the G-buffer of caller-supplied rays (vrt_render_rays.hip).  k_rays_primary<TRAV> is k_query's closest-hit form plus the plane
+    # stores: the same budgets, no scratch (69 / 48 / 59 VGPRs).  k_shade_rays<TRAV> is k_shade's body: four waves per SIMD (at most 128
+    # VGPRs; 108 / 89 / 108) and k_shade's 368 B of scratch per lane, the stack of hits of the bounce loop -- nothing beyond it
+    "k_rays_primaryILi7EE": ("rays' G-buffer, primary march, look-up loop", 72, 80, 0),
+    "k_rays_primaryILi4EE": ("rays' G-buffer, primary march, DF", 64, 80, 0),
+    "k_rays_primaryILi6EE": ("rays' G-buffer, primary march, brick march", 64, 80, 0),
+    "k_shade_raysILi7EE": ("rays' G-buffer, shading of the hit list, look-up loop", 128, 112, 368),
+    "k_shade_raysILi4EE": ("rays' G-buffer, shading of the hit list, DF", 128, 112, 368),
+    "k_shade_raysILi6EE": ("rays' G-buffer, shading of the hit list, brick march", 128, 112, 368),
 }
 
 
 # the objects that hold budgeted kernels, as the Makefile builds them: (source, extra flags); slowest first
 OBJECTS = [("vrt_device.hip", ["-DVRT_K1_PART=%d" % n]) for n in (3, 0, 1, 2)] + [("vrt_denoise.hip", []), ("vrt_scene_edit.hip", []), ("vrt_query.hip", []),
-                                                                                     ("vrt_reproject.hip", []), ("vrt_upsample.hip", []), ("vrt_rays.hip", [])]
+                                                                                     ("vrt_reproject.hip", []), ("vrt_upsample.hip", []), ("vrt_rays.hip", []),
+                                                                                     ("vrt_render_rays.hip", [])]
 
 
 def remarks(obj):

@@ -139,6 +139,7 @@ SYMBOLS = {
     "vrt_occluded_rays": (C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_uint32, _P]),
     "vrt_pick_pixels": (C.c_int, [_P, _P, C.POINTER(Push), C.c_uint32, C.c_int64, _P, C.POINTER(RayHits)]),
     "vrt_camera_rays": (C.c_int, [_P, C.POINTER(RayCamera), C.c_int32, C.c_int32, _P, _P]),
+    "vrt_render_rays": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P, C.c_uint32, C.POINTER(Settings), C.POINTER(Frame)]),
     "vrt_denoiser_settings_default": (None, [C.POINTER(DenoiserSettings)]),
     "vrt_denoise": (C.c_int, [_P, C.c_int32, C.c_int32, C.POINTER(DenoiserSettings), _P, _P, _P, _P, _P,
                               C.POINTER(Shard), C.POINTER(_P)]),

@@ -1,5 +1,5 @@
 // vrt_api.hip -- the C-ABI of libvrt_hip.so (include/vrt.h): the error string, contexts and their options, device memory, the
-// host-only calls (settings defaults, images, .vox flattening, jitter), the geometry stage and the instrumentation.  Scenes are in
+// host-only calls (settings defaults, images, .vox flattening, jitter), the geometry stage (vrt_render_rays included) and the instrumentation.  Scenes are in
 // vrt_api_scene.hip, the denoiser / strip packing / presentation / reprojection in vrt_api_post.hip, the ray queries in
 // vrt_api_query.hip, ray generation in vrt_api_rays.hip, RCCL in vrt_api_comm.hip; vrt_host.h is what they share.  Host code only; kernels live in the other .hip files.
 //
@@ -95,7 +95,7 @@ int vrt_ctx_set_stream(vrt_ctx* c, void* hip_stream)
     c->stream = (hipStream_t)hip_stream;      // NULL is a valid handle: the HIP null (legacy default) stream
     c->own_stream = false;
     c->have_geo = c->have_den = false;
-    c->checked_ptrs[0] = c->checked_ptrs[1] = c->checked_ptrs[3] = 0;
+    c->checked_ptrs[0] = c->checked_ptrs[1] = c->checked_ptrs[3] = c->checked_ptrs[4] = 0;
     return VRT_OK;
 }
 
@@ -154,7 +154,7 @@ int vrt_device_free(vrt_ctx* c, void* p)
     HIPCHK(hipSetDevice(c->device));
     HIPCHK(hipStreamSynchronize(c->stream));
     if (p) HIPCHK(hipFree(p));
-    c->checked_ptrs[0] = c->checked_ptrs[1] = c->checked_ptrs[3] = 0;     // a freed address may come back as something else: verify again
+    c->checked_ptrs[0] = c->checked_ptrs[1] = c->checked_ptrs[3] = c->checked_ptrs[4] = 0;     // a freed address may come back as something else: verify again
     return VRT_OK;
 }
 
@@ -691,6 +691,93 @@ int vrt_render_geometry_slots(vrt_ctx* c, const vrt_scene* s, int32_t n, const v
     if (!c || !s || !pushes || !st || !frames || !shards) return fail(VRT_ERR_INVALID, "vrt_render_geometry_slots: NULL argument");
     if (n < 0) return fail(VRT_ERR_INVALID, "vrt_render_geometry_slots: n < 0");
     return render_many(c, s, n, pushes, st, frames, shards, 1);
+}
+
+// The G-buffer of caller-supplied rays (kernels: vrt_render_rays.hip): the split form over a ray buffer.  Here, beside the launch
+// it borrows from: the GeomParams of the shading kernel comes from launch_plan and launch_records, as a split
+// vrt_render_geometry launch of one frame builds it.
+int vrt_render_rays(vrt_ctx* c, const vrt_scene* s, int32_t W, int32_t H, const float* origins, const float* dirs, uint32_t frame,
+                    const vrt_settings* st, const vrt_frame* out)
+{
+    // every argument error is reported before the context or a device is looked at
+    if (!c || !s || !origins || !dirs || !st || !out) return fail(VRT_ERR_INVALID, "vrt_render_rays: NULL argument");
+    if (W < 1 || H < 1 || W > 32768 || H > 32768) return fail(VRT_ERR_INVALID, "vrt_render_rays: bad frame size");
+    if ((int64_t)W * (int64_t)H >= ((int64_t)1 << 28))
+        return fail(VRT_ERR_INVALID, "vrt_render_rays: 2^28 pixels or more per frame (the limit of vrt_render_geometry: pass the image as several rectangles of rays)");
+    if (st->max_steps == 0u) return fail(VRT_ERR_INVALID, "vrt_render_rays: max_steps == 0");
+    if (st->max_bounces > VRT_MAX_BOUNCES) return fail(VRT_ERR_INVALID, "vrt_render_rays: max_bounces > VRT_MAX_BOUNCES");
+    if (out->steps_primary || out->steps_total || out->rays_total || out->color8_strips)
+        return fail(VRT_ERR_UNSUPPORTED, "vrt_render_rays: the count planes and color8_strips are not filled for caller-supplied rays");
+    if (st->flags != 0u) return fail(VRT_ERR_UNSUPPORTED, "vrt_render_rays: settings->flags must be 0");
+    if (st->traversal != VRT_TRAVERSAL_AUTO) return fail(VRT_ERR_UNSUPPORTED, "vrt_render_rays: VRT_TRAVERSAL_AUTO only");
+    const size_t n = (size_t)W * (size_t)H;
+    const struct { const void* p; size_t bpp; } planes[10] = {
+        {out->color8, 4}, {out->depth, 4}, {out->motion, 8}, {out->mask8, 1}, {out->position, 16}, {out->normal8, 4},
+        {out->color_f, 12}, {out->hit_id, 1}, {out->hit_voxel, 6}, {out->hit_mask, 1}};
+    bool any = false;
+    for (const auto& q : planes) any = any || q.p != nullptr;
+    if (!any) return fail(VRT_ERR_INVALID, "vrt_render_rays: no output plane");
+    if ((((uintptr_t)origins | (uintptr_t)dirs) & 3u) != 0u) return fail(VRT_ERR_INVALID, "vrt_render_rays: origins and dirs must be 4-byte aligned");
+    for (const auto& q : planes) {
+        if (!q.p) continue;
+        const uintptr_t a = (uintptr_t)q.p, na = n * q.bpp;
+        for (const float* r : {origins, dirs})
+            if (a < (uintptr_t)r + n * 12u && (uintptr_t)r < a + na) return fail(VRT_ERR_INVALID, "vrt_render_rays: a ray plane overlaps an output plane");
+    }
+    HIPCHK(hipSetDevice(c->device));
+    {
+        const void* ptrs[12] = {origins, dirs};
+        for (int q = 0; q < 10; q++) ptrs[2 + q] = planes[q].p;
+        int rc = check_device_ptrs(c, 4, ptrs, 12, "vrt_render_rays");      // (a slot of its own: alternating with vrt_render_geometry keeps both digests)
+        if (rc != VRT_OK) return rc;
+    }
+    // the synthetic push block: the shading path reads `frame` (the sample offset) and nothing else of it
+    vrt_push push;
+    memset(&push, 0, sizeof push);
+    push.volume_bounds[0] = (uint32_t)s->d.vol.W; push.volume_bounds[1] = (uint32_t)s->d.vol.H; push.volume_bounds[2] = (uint32_t)s->d.vol.D;
+    push.screen_size[0] = W; push.screen_size[1] = H; push.frame = frame;
+    // the plan of a split launch of that one frame.  Of the context options "thresh_runs" and "ao_batch" are honoured, the others
+    // take their defaults; hit_voxel does not choose the march here (query_recover_voxel recovers the cell on the look-up loop)
+    DevOptions opt;
+    opt.thresh_runs = c->opt.thresh_runs; opt.ao_batch = c->opt.ao_batch;
+    vrt_settings split = *st;
+    split.flags = VRT_FLAG_SPLIT_KERNELS;
+    vrt_frame plan_frame = *out;
+    plan_frame.hit_voxel = nullptr;
+    const Launch l = {1, &push, &split, &plan_frame, nullptr, 0, W, H};
+    GeomParams p;
+    int rc = launch_plan(opt, s, l, false, nullptr, 0, p);
+    if (rc != VRT_OK) return rc;
+    p.fused_shade = 0; p.st.flags = 0u;
+    p.slot[0].pc = push; p.slot[0].fr = *out; p.slot[0].rg = raygen_consts(push); p.slot[0].shard_rank = 0;
+    p.slot[0].box[0] = p.slot[0].box[2] = 0; p.slot[0].box[1] = p.slot[0].box[3] = 255;
+    rc = launch_records(c, n, p);
+    if (rc != VRT_OK) return rc;
+    // The primary march is vrt_trace_rays' (vrt_api_query.hip, query_launch): what VRT_TRAVERSAL_AUTO resolves to for the scene and
+    // the budget.  The shading kernel takes the hand-written loops where the plan admits them for the secondary rays too
+    // (launch_plan: the AO budget), else VRT_TRAVERSAL_DF.
+    RaysParams rp;
+    memset(&rp, 0, sizeof rp);
+    rp.sc = p.sc; rp.origins = origins; rp.dirs = dirs; rp.fr = *out; rp.n = (uint32_t)n; rp.max_steps = st->max_steps;
+    rp.records = p.records; rp.hit_list = p.hit_list; rp.hit_count = p.hit_count;
+    int prim, shade;
+    if (s->bricks) {
+        prim = shade = VRT_TRAVERSAL_BRICK;
+        rp.sc.vol.df_thresh = (c->opt.thresh_runs && st->max_steps >= 32u) ? 1u : 0u;
+    } else {
+        const bool fast = s->d.vol.df_fast != 0u && st->max_steps <= 1024u;
+        prim = fast ? VRT_TRAVERSAL_DF_FAST : VRT_TRAVERSAL_DF;
+        shade = (fast && p.fast_loop == 1) ? VRT_TRAVERSAL_DF_FAST : VRT_TRAVERSAL_DF;
+        const int vw = s->d.vol.W, vh = s->d.vol.H, vd = s->d.vol.D;
+        const int dmax = vw > vh ? (vw > vd ? vw : vd) : (vh > vd ? vh : vd);
+        rp.sc.vol.df_thresh = (fast && c->opt.thresh_runs && dmax <= 1022 && st->max_steps >= 32u) ? 1u : 0u;
+    }
+    if (c->timing) HIPCHK(hipEventRecord(c->ev_geo0, c->stream));
+    HIPCHK(launch_rays_primary(rp, prim, c->stream));
+    if (c->timing) HIPCHK(hipEventRecord(c->ev_prim1, c->stream));
+    HIPCHK(launch_rays_shade(p, dirs, rp.n, shade, c->stream));
+    if (c->timing) { HIPCHK(hipEventRecord(c->ev_geo1, c->stream)); c->have_geo = true; }
+    return VRT_OK;
 }
 
 

@@ -98,7 +98,7 @@ struct vrt_ctx {
     vrt::DevBuf<uint32_t> hit_list;   // [records_px] + 1 counter word at the end
     size_t records_px = 0;
     int div_w = 0, div_h = 0, div_ok = 0;   // screen size last examined by screen_div_ok, and its verdict
-    uint64_t checked_ptrs[4] = {0, 0, 0, 0};   // digests of the image pointers last verified to be device memory (geometry, denoiser, ray queries, vrt_camera_rays)
+    uint64_t checked_ptrs[5] = {0, 0, 0, 0, 0};   // digests of the image pointers last verified to be device memory (geometry, denoiser, ray queries, vrt_camera_rays, vrt_render_rays)
     // frame-slot tables of launches with more than VRT_MAX_BATCH frames: a ring of device tables, each with a pinned host
     // image that is uploaded on a stream of its own (the copy runs while the previous launch is still tracing)
     static constexpr int kTabRing = 4;

@@ -278,6 +278,20 @@ struct QueryParams {
     int32_t        fast_screen_div, W, H;
 };
 
+// vrt_render_rays, the primary kernel (vrt_render_rays.hip): W * H rays from two planes of 3 floats each, the planes of the frame
+// they fill (NULL: not written) and the hit records handed to the shading kernel.  sc.vol: the scene's view with the march
+// variants set as a ray query sets them (vrt_api_query.hip).
+struct RaysParams {
+    DevScene       sc;
+    const float*   origins;   // 3n (device)
+    const float*   dirs;
+    vrt_frame      fr;
+    uint4*         records;   // GeomParams::records, hit_list, hit_count of the shading launch that follows
+    uint32_t*      hit_list;
+    uint32_t*      hit_count;
+    uint32_t       n, max_steps;
+};
+
 // Temporal reprojection (vrt_reproject.hip): the call's constants (vrt_reproject.h), the current planes, the previous history
 // (both nullptr: a new sequence) and the outputs; resolved8 and motion may be nullptr (not written).  W * H texels each.
 struct ReprojectParams {
@@ -310,7 +324,7 @@ struct UpsampleParams {
 
 // launchers: scene build (vrt_scene_build.hip), scene edits (vrt_scene_edit.hip), render (vrt_device.hip: sky, tile tags, hit
 // colours, K1, K2), K3 (vrt_denoise.hip), rows / blit / accumulate / resolve (vrt_post.hip), reprojection (vrt_reproject.hip),
-// upsampling (vrt_upsample.hip), ray generation (vrt_rays.hip)
+// upsampling (vrt_upsample.hip), ray generation (vrt_rays.hip), shading of caller-supplied rays (vrt_render_rays.hip)
 hipError_t launch_build_pyramid(const uint8_t* vox, int W, int H, int D, uint64_t* occ1, uint64_t* occ2,
                                 uint64_t* occ3, hipStream_t s);
 hipError_t launch_build_df(const uint8_t* vox, int W, int H, int D, uint8_t* df, size_t stride, uint8_t* tmp0, uint8_t* tmp1, hipStream_t s, int cap = 0 /* 0: the dense scene's cap */);
@@ -350,6 +364,8 @@ hipError_t launch_bedit_coarse(const BrickEdit& b, const uint8_t* occ, uint8_t* 
 hipError_t launch_primary(const GeomParams& p, hipStream_t s);
 hipError_t launch_shade(const GeomParams& p, hipStream_t s);
 hipError_t launch_query(const QueryParams& p, int traversal /* VRT_TRAVERSAL_DF_FAST, _DF or _BRICK */, int anyhit, int pick, hipStream_t s);
+hipError_t launch_rays_primary(const RaysParams& rp, int traversal /* VRT_TRAVERSAL_DF_FAST, _DF or _BRICK */, hipStream_t s);
+hipError_t launch_rays_shade(const GeomParams& p, const float* dirs, uint32_t n, int traversal, hipStream_t s);
 hipError_t launch_denoise_pass(const DenoiseParams& p, hipStream_t s);
 hipError_t launch_rows(const RowsParams& p, int rows_total, hipStream_t s);
 hipError_t launch_rows_batch(const RowsBatchParams& p, int rows_total, int images, hipStream_t s);

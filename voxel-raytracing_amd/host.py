@@ -775,6 +775,25 @@ class GeometryStage:
                                                 C.byref(shard) if shard is not None else None))
         return gb
 
+    def record_rays(self, origins, dirs, resolution, frame=0) -> GeometryBuffer:
+        """The G-buffer of a frame whose primary rays the caller supplies (vrt_render_rays): origins, dirs are float32 device
+        tensors (W * H, 3), ray py * W + px for pixel (px, py) -- what RayCamera.rays returns.  The stage's own planes; of the
+        debug planes color_f, hit_id, hit_voxel and hit_mask are filled; the count planes are not attached and are left untouched
+        (zeros on a fresh stage, the last record()'s values on one that has drawn the built-in camera)."""
+        torch = _torch()
+        W, H = int(resolution[0]), int(resolution[1])
+        if (W, H) != tuple(self._settings.renderResolution()):
+            raise ValueError("record_rays: resolution must be the settings' renderResolution()")
+        for t, what in ((origins, "origins"), (dirs, "dirs")):
+            if not (torch.is_tensor(t) and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == (W * H, 3)):
+                raise ValueError(f"record_rays: {what} must be a contiguous float32 tensor of shape (W * H, 3)")
+        gb = self._targets()
+        st = self._settings.to_c()
+        fr = gb.to_c(without=("steps_primary", "steps_total", "rays_total", "color8_strips"))
+        check(lib().vrt_render_rays(self.engine.ctx, self._scene.handle, W, H, C.c_void_p(origins.data_ptr()), C.c_void_p(dirs.data_ptr()),
+                                    int(frame) & 0xFFFFFFFF, C.byref(st), C.byref(fr)))
+        return gb
+
     def prepare(self, shard: Optional[_capi.Shard] = None):
         """Frame loops whose settings do not change between frames: marshal the settings / target structs once and
         return launch(push) -> GeometryBuffer (a Python-side economy only; the same C-ABI call is made)."""
@@ -1024,16 +1043,21 @@ class VoxelRenderer:
     the temporal pass is UpscalerStage.record_reprojected instead of the pixel-by-pixel accumulation, and gBuffer.motion holds
     the motion vectors; reproject=False is the accumulation exactly.  upsample=True (with reproject=True) keeps that history at
     targetResolution instead (UpscalerStage.record_upsampled: no blit, display-resolution motion in upscaler.motion);
-    upsample=False is the render-resolution path exactly."""
+    upsample=False is the render-resolution path exactly.  camera=RayCamera(...): the G-buffer is drawn from that camera's rays
+    (RayCamera.rays + GeometryStage.record_rays) instead of the built-in pinhole; the denoiser and the writers run unchanged.
+    Not with temporal=True: the reprojection projects through the pinhole."""
 
     def __init__(self, engine: Engine, settings: Optional[VoxelRenderSettings] = None, scene: Optional[VoxelScene] = None,
                  noise=None, debug_planes: bool = False, temporal: bool = False, windowSize=None, reproject: bool = False,
-                 upsample: bool = False):
+                 upsample: bool = False, camera: Optional["RayCamera"] = None):
+        if camera is not None and temporal:
+            raise ValueError("VoxelRenderer: temporal=True with a RayCamera is not supported (the reprojection projects through the built-in pinhole)")
         if upsample and not reproject:
             raise ValueError("VoxelRenderer: upsample=True needs reproject=True (the display-resolution history is a reprojected one)")
         self.engine = engine
         self._settings = settings or VoxelRenderSettings()
         self._camera = CameraController()
+        self.rayCamera = camera
         self._scene = scene if scene is not None else VoxelScene(engine, self._settings.voxPath)
         self._geometryStage = GeometryStage(engine, self._settings, self._scene, noise, debug_planes)
         self._denoiserStage = DenoiserStage(engine, self._settings)
@@ -1091,7 +1115,14 @@ class VoxelRenderer:
         if self.upsample and shard is not None:
             raise ValueError("VoxelRenderer: upsampling across strips is not supported (include/vrt.h, vrt_upsample)")
         push = self.push_constants()
-        gBuffer = self._geometryStage.record(push, shard)
+        if self.rayCamera is not None:
+            if shard is not None:
+                raise ValueError("VoxelRenderer: a RayCamera renders whole frames (vrt_render_rays has no vrt_shard)")
+            res = self._settings.renderResolution()
+            origins, dirs = self.rayCamera.rays(self.engine, res, self.jitter)
+            gBuffer = self._geometryStage.record_rays(origins, dirs, res, self.frameCount)
+        else:
+            gBuffer = self._geometryStage.record(push, shard)
         if self._settings.denoiserSettings.enable:
             color = self._denoiserStage.record(gBuffer.color, gBuffer.normal, gBuffer.position, shard)
         else:

@@ -3,6 +3,8 @@
 // --rays IN --hits OUT [--ray-steps N]: no frame; the rays of IN (raw little-endian float32, n x 6: origin then direction) are
 // traced through the loaded scene (VoxelScene::traceRays) and OUT receives per ray material (u8), pos (3 x f32), voxel (3 x i32),
 // normal (3 x i8), packed in that order: 28 bytes.
+// --projection perspective:FOV | ortho:HALFWIDTH | panorama: the frame is drawn under that camera model (vrt_camera_rays over the
+// --pos / --yaw / --pitch basis, then vrt_render_rays) instead of the built-in 90-degree pinhole; not with --temporal or --devices.
 // Errors propagate as exceptions to run(), are printed, and the process exits with EXIT_FAILURE.
 #include <cstdio>
 #include <cstdlib>
@@ -53,7 +55,7 @@ int run(int argc, char** argv)
         vec3 pos{8, 8, -50}; float yaw = 90, pitch = 0; bool havePos = false; int device = 0;
         std::vector<int> devices;                                          // --devices a,b,...: one process drives several GPUs
         int frames = 1; uint32_t windowW = 0, windowH = 0; float flyForward = 0, flyStrafe = 0, flyMouseX = 0; bool temporal = false, reproject = false, upsample = false;
-        std::string dumpPushes; std::vector<vrt_push> allPushes;
+        std::string dumpPushes, projection; std::vector<vrt_push> allPushes;
         for (int i = 1; i < argc; i++) {
             std::string a = argv[i];
             auto next = [&]() { if (i + 1 >= argc) throw std::runtime_error("missing value for " + a); return std::string(argv[++i]); };
@@ -80,9 +82,11 @@ int run(int argc, char** argv)
             else if (a == "--upsample") upsample = true;                                       // with --temporal --reproject: the history at display resolution (vrt_upsample)
             else if (a == "--dump-pushes") dumpPushes = next();                                // every frame's push block, 96 bytes each
             else if (a == "--window") { windowW = (uint32_t)std::stoul(next()); windowH = (uint32_t)std::stoul(next()); }
+            else if (a == "--projection") projection = next();
             else if (a == "--fly") { flyForward = std::stof(next()); flyStrafe = std::stof(next()); flyMouseX = std::stof(next()); }
             else throw std::runtime_error("unknown argument " + a);
         }
+        if (!devices.empty() && !projection.empty()) throw std::runtime_error("--projection renders on one device (vrt_render_rays has no strips)");
         if (!devices.empty()) {
             // screen strips over the listed GPUs, RCCL gather to the first one (ShardedRenderer); the scene is loaded on each
             std::vector<std::shared_ptr<Engine>> engines; std::vector<std::shared_ptr<VoxelScene>> scenes;
@@ -134,6 +138,15 @@ int run(int argc, char** argv)
         if (!havePos) pos = {scene->width / 2.0f, scene->height / 2.0f, -0.8f * scene->depth};
         renderer.camera().position = pos; renderer.camera().yaw = yaw; renderer.camera().pitch = pitch;
         renderer.camera().updateDirectionVectors();
+        if (!projection.empty()) {
+            if (temporal) throw std::runtime_error("--projection does not go with --temporal (the reprojection projects through the built-in pinhole)");
+            const size_t c = projection.find(':');
+            const std::string kind = projection.substr(0, c), value = c == std::string::npos ? "" : projection.substr(c + 1);
+            if (kind == "perspective" && !value.empty()) { renderer.projection = VRT_CAMERA_PERSPECTIVE; renderer.tanHalf = std::tan(std::stof(value) * 3.14159265358979323846f / 360.0f); }
+            else if (kind == "ortho" && !value.empty()) { renderer.projection = VRT_CAMERA_ORTHOGRAPHIC; renderer.halfWidth = std::stof(value); }
+            else if (kind == "panorama" && value.empty()) renderer.projection = VRT_CAMERA_PANORAMA;
+            else throw std::runtime_error("--projection perspective:FOV | ortho:HALFWIDTH | panorama");
+        }
         renderer.temporal = temporal; renderer.reproject = reproject; renderer.upsample = upsample; renderer.windowW = windowW; renderer.windowH = windowH;
         std::vector<uint8_t> img; uint32_t res[2] = {0, 0};
         const bool moving = flyForward != 0 || flyStrafe != 0 || flyMouseX != 0;

@@ -224,18 +224,18 @@ public:
         : engine(engine), settings(settings), scene(scene) {}
     GeometryBuffer record(const vrt_push& push, const vrt_shard* shard = nullptr)     // geometry_stage.cpp:106
     {
-        auto res = settings->renderResolution();
-        if (gb.width != res[0] || gb.height != res[1]) {                              // RENDER_RESIZE recreation (:19-45)
-            size_t n = (size_t)res[0] * res[1];
-            gb.color = std::make_shared<DeviceBuffer<uint8_t>>(engine, n * 4); gb.mask = std::make_shared<DeviceBuffer<uint8_t>>(engine, n);
-            gb.depth = std::make_shared<DeviceBuffer<float>>(engine, n); gb.motion = std::make_shared<DeviceBuffer<float>>(engine, n * 2);
-            gb.position = std::make_shared<DeviceBuffer<float>>(engine, n * 4); gb.normal = std::make_shared<DeviceBuffer<int8_t>>(engine, n * 4);
-            gb.width = res[0]; gb.height = res[1];
-        }
-        vrt_frame f{}; f.color8 = gb.color->ptr; f.depth = gb.depth->ptr; f.motion = gb.motion->ptr; f.mask8 = gb.mask->ptr;
-        f.position = gb.position->ptr; f.normal8 = gb.normal->ptr;
+        vrt_frame f = targets();
         vrt_settings st = settings->toC();
         check(vrt_render_geometry(engine->ctx, scene->handle, &push, &st, &f, shard));
+        return gb;
+    }
+    // The G-buffer of a frame whose primary rays the caller supplies (no reference analogue; vrt_render_rays): origins, dirs are DEVICE
+    // pointers to renderResolution() rays of 3 packed floats, ray py * W + px for pixel (px, py) -- what vrt_camera_rays writes
+    GeometryBuffer recordRays(const float* origins, const float* dirs, uint32_t frame = 0)
+    {
+        vrt_frame f = targets();
+        vrt_settings st = settings->toC();
+        check(vrt_render_rays(engine->ctx, scene->handle, (int32_t)gb.width, (int32_t)gb.height, origins, dirs, frame, &st, &f));
         return gb;
     }
     // n camera poses in one launch per 8 frames (vrt_render_geometry_batch); every frame gets its own planes, kept in `batch`
@@ -262,6 +262,20 @@ public:
         return batch;
     }
 private:
+    vrt_frame targets()
+    {
+        auto res = settings->renderResolution();
+        if (gb.width != res[0] || gb.height != res[1]) {                              // RENDER_RESIZE recreation (:19-45)
+            size_t n = (size_t)res[0] * res[1];
+            gb.color = std::make_shared<DeviceBuffer<uint8_t>>(engine, n * 4); gb.mask = std::make_shared<DeviceBuffer<uint8_t>>(engine, n);
+            gb.depth = std::make_shared<DeviceBuffer<float>>(engine, n); gb.motion = std::make_shared<DeviceBuffer<float>>(engine, n * 2);
+            gb.position = std::make_shared<DeviceBuffer<float>>(engine, n * 4); gb.normal = std::make_shared<DeviceBuffer<int8_t>>(engine, n * 4);
+            gb.width = res[0]; gb.height = res[1];
+        }
+        vrt_frame f{}; f.color8 = gb.color->ptr; f.depth = gb.depth->ptr; f.motion = gb.motion->ptr; f.mask8 = gb.mask->ptr;
+        f.position = gb.position->ptr; f.normal8 = gb.normal->ptr;
+        return f;
+    }
     std::shared_ptr<Engine> engine; std::shared_ptr<VoxelRenderSettings> settings; std::shared_ptr<VoxelScene> scene; GeometryBuffer gb;
     std::vector<GeometryBuffer> batch;
 };
@@ -421,7 +435,16 @@ public:
     std::vector<uint8_t> render(uint32_t* outW = nullptr, uint32_t* outH = nullptr)
     {
         vrt_push push = pushConstants();
-        GeometryBuffer g = _geometryStage->record(push);
+        GeometryBuffer g;
+        if (projection >= 0) {
+            // another camera model: its rays (vrt_camera_rays over this renderer's camera basis and jitter), then their G-buffer
+            if (temporal) throw std::runtime_error("VoxelRenderer: temporal with a projection is not supported (the reprojection projects through the built-in pinhole)");
+            vrt_ray_camera cam{}; cam.model = projection; cam.basis = push; cam.tan_half = tanHalf; cam.half_width = halfWidth;
+            const size_t n = (size_t)push.screen_size[0] * (size_t)push.screen_size[1];
+            if (!_rayOrigins || _rayOrigins->count != 3 * n) { _rayOrigins = std::make_unique<DeviceBuffer<float>>(engine, 3 * n); _rayDirs = std::make_unique<DeviceBuffer<float>>(engine, 3 * n); }
+            check(vrt_camera_rays(engine->ctx, &cam, push.screen_size[0], push.screen_size[1], _rayOrigins->ptr, _rayDirs->ptr));
+            g = _geometryStage->recordRays(_rayOrigins->ptr, _rayDirs->ptr, push.frame);
+        } else g = _geometryStage->record(push);
         const uint8_t* img = _settings->denoiserSettings.enable ? _denoiserStage->record(g) : g.color->ptr;
         uint32_t w = g.width, h = g.height;
         if (temporal && _settings->fsrSetttings.enable) { if (upsample && !reproject) throw std::runtime_error("VoxelRenderer: upsample needs reproject"); img = !reproject ? _upscalerStage->record(img, w, h) : upsample ? _upscalerStage->recordUpsampled(img, g, push) : _upscalerStage->recordReprojected(img, g, push); w = _settings->targetResolution[0]; h = _settings->targetResolution[1]; }
@@ -434,7 +457,10 @@ public:
         return host;
     }
     bool temporal = false, reproject = false, upsample = false; uint32_t windowW = 0, windowH = 0; GeometryBuffer gBuffer;
+    // projection >= 0: a VRT_CAMERA_* model drawn through vrt_camera_rays + vrt_render_rays instead of the built-in 90-degree pinhole
+    int projection = -1; float tanHalf = 1.0f, halfWidth = 1.0f;
 private:
+    std::unique_ptr<DeviceBuffer<float>> _rayOrigins, _rayDirs;
     std::shared_ptr<Engine> engine; std::shared_ptr<VoxelRenderSettings> _settings; std::shared_ptr<VoxelScene> _scene;
     std::unique_ptr<CameraController> _camera; std::unique_ptr<GeometryStage> _geometryStage; std::unique_ptr<DenoiserStage> _denoiserStage;
     std::unique_ptr<UpscalerStage> _upscalerStage; std::unique_ptr<BlitStage> _blitStage;

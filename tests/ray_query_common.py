@@ -323,15 +323,25 @@ def long_volume(mirrored=False):
     return np.ascontiguousarray(vol[:, :, ::-1]) if mirrored else vol
 
 
-def long_rays(n, mirrored=False):
+def long_rays(n, mirrored=False, dims=LONG_DIMS, axis=0, sign=None, along=((-3.0, 3.0),), margin=2.5, slopes=(0.002, 0.05), seed=1101):
     """n rays that start within three voxels of the x = 0 face, inside the volume or just outside it, and run along +x: seven in ten
     from the middle of the section with a slope of at most 0.002 against the axis (they stay inside the 8 x 8 section all the way), the others up to 3 degrees
-    (they leave through a side).  mirrored: the same rays reflected to start at the far end and run along -x."""
-    rng = np.random.default_rng(1101)
-    W, H, D = LONG_DIMS
-    o = np.stack([rng.uniform(-3.0, 3.0, n), rng.uniform(2.5, H - 2.5, n), rng.uniform(2.5, D - 2.5, n)], axis=1)
-    slope = np.where(rng.random(n) < 0.7, 0.002, 0.05)[:, None] * rng.uniform(-1, 1, (n, 2))
-    d = np.concatenate([np.ones((n, 1)), slope], axis=1) * rng.uniform(0.5, 2.0, n)[:, None]
+    (they leave through a side).  mirrored: the same rays reflected to start at the far end and run along -x.
+    Generalised (tests/extents_common.py): the volume `dims`, its long `axis`, `sign` of travel (-1 = mirrored), the ranges `along`
+    the axis that ray i % len(along) starts in, measured from the face the rays leave behind, the `margin` the origins keep from
+    the section's sides, and the two slope classes.  `sign`, where given (not None), decides the direction and `mirrored` is not
+    looked at; the callers of the 1100 x 8 x 8 volume pass `mirrored` alone."""
+    rng = np.random.default_rng(seed)
+    if sign is not None:
+        mirrored = sign < 0
+    u, v = [b for b in range(3) if b != axis]
+    lo, hi = (np.array([along[i % len(along)][k] for i in range(n)]) for k in (0, 1))
+    o = np.empty((n, 3))
+    o[:, axis], o[:, u], o[:, v] = rng.uniform(lo, hi, n), rng.uniform(margin, dims[u] - margin, n), rng.uniform(margin, dims[v] - margin, n)
+    slope = np.where(rng.random(n) < 0.7, slopes[0], slopes[1])[:, None] * rng.uniform(-1, 1, (n, 2))
+    d = np.empty((n, 3))
+    d[:, axis], d[:, u], d[:, v] = 1.0, slope[:, 0], slope[:, 1]
+    d *= rng.uniform(0.5, 2.0, n)[:, None]
     if mirrored:
-        o[:, 0] = W - o[:, 0]; d[:, 0] = -d[:, 0]
+        o[:, axis] = dims[axis] - o[:, axis]; d[:, axis] = -d[:, axis]
     return np.ascontiguousarray(o, np.float32), np.ascontiguousarray(d, np.float32)

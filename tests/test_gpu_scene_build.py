@@ -10,6 +10,7 @@ import time
 import numpy as np
 import pytest
 
+import extents_common
 import scene_reference as R
 from helpers import metallic_palette
 from test_gpu_scene_edit import apply_edit
@@ -28,8 +29,11 @@ def count(case_bytes):
 
 DIMS = [(1, 1, 1), (1, 1, 200), (200, 1, 1), (3, 5, 7), (4, 4, 4), (5, 4, 4), (63, 9, 10), (64, 8, 8), (65, 8, 8), (255, 3, 5), (256, 4, 4),
         (257, 6, 3), (300, 40, 20), (17, 70, 66), (130, 129, 131)]
-CORNERS = [(3, 5, 7), (5, 4, 4), (65, 8, 8), (257, 6, 3), (17, 70, 66), (130, 129, 131)]
-DENSITIES = [(1, 1, 200), (200, 1, 1), (63, 9, 10), (64, 8, 8), (255, 3, 5), (256, 4, 4), (300, 40, 20), (17, 70, 66), (130, 129, 131)]
+# the longest axis a scene may have (tests/extents_common.py): cells 0 .. 1023 of the cell list, rows of 4098 bytes
+NEEDLES = extents_common.NEEDLES + extents_common.RAGGED
+DIMS += NEEDLES + extents_common.LINES
+CORNERS = [(3, 5, 7), (5, 4, 4), (65, 8, 8), (257, 6, 3), (17, 70, 66), (130, 129, 131)] + NEEDLES
+DENSITIES = [(1, 1, 200), (200, 1, 1), (63, 9, 10), (64, 8, 8), (255, 3, 5), (256, 4, 4), (300, 40, 20), (17, 70, 66), (130, 129, 131)] + NEEDLES
 SLABS = [(3, 5, 7), (63, 9, 10), (65, 8, 8), (257, 6, 3), (300, 40, 20), (130, 129, 131)]
 
 
@@ -48,6 +52,8 @@ def dense_contents(dims):
             out.append((f"one voxel in corner {k}", v))
     if dims in DENSITIES:
         out += [("random 0.002", rand(0.002)), ("random 0.5", rand(0.5))]
+    if dims in NEEDLES:
+        out.append(("the needle of extents_common", extents_common.needle_volume(dims)))
     if dims in SLABS:
         for axis, name in ((2, "x"), (1, "y"), (0, "z")):
             v = np.zeros((D, H, W), np.uint8)
@@ -172,6 +178,7 @@ def test_the_dense_cases_exercise_the_classes():
 # ---- brick scenes -----------------------------------------------------------------------------------------------------------------
 
 GRIDS = [(1, 1, 1), (1, 1, 20), (20, 1, 1), (3, 4, 5), (12, 8, 11), (17, 16, 18)]          # bricks: nbx, nby, nbz
+GRIDS += extents_common.BRICK_NEEDLES                             # the longest axis, 512 bricks: brick coordinates 0 .. 511
 
 
 def sparse_brick(rng, p=0.05):
@@ -212,6 +219,8 @@ def brick_contents(nb):
                 v[bz * 8 + 7 * (k >> 2 & 1), by * 8 + 7 * (k >> 1 & 1), bx * 8 + 7 * (k & 1)] = 1 + k % 255
                 k += 1
     out.append(("one corner voxel per brick", v))
+    if nb in extents_common.BRICK_NEEDLES:
+        out.append(("the needle of extents_common", extents_common.brick_needle_volume(nb)))
     if nb == (1, 1, 1):
         for k in range(1, 8):
             v = np.zeros((D, H, W), np.uint8)

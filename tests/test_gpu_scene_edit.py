@@ -90,7 +90,7 @@ def apply_edit(sc, vol, lo, what):
     return [w, h, d]
 
 
-@pytest.mark.parametrize("dims", [(100, 60, 90), (300, 40, 150)])
+@pytest.mark.parametrize("dims", [(100, 60, 90), (300, 40, 150), (4096, 9, 12), (9, 12, 4096)])
 def test_state_after_every_edit_equals_a_fresh_build(vrt, engine, dims):
     W, H, D = dims
     rng = np.random.default_rng(W)

@@ -13,6 +13,7 @@ import itertools
 import numpy as np
 import pytest
 
+import extents_common
 import scene_reference as R
 from test_traverse_host import th                                 # noqa: F401  (the fixture that builds and loads the library)
 
@@ -286,3 +287,59 @@ def test_the_host_builder_gives_the_same_clearance(th):             # noqa: F811
                 th.thb_octant_clearance(np.ascontiguousarray(vol).ctypes.data, W, H, D, o, cap, out.ctypes.data)
                 exp = R.clearance(vol, o, cap)
                 assert (out == exp).all(), (vol.shape, cap, o, np.argwhere(out != exp)[:3].tolist())
+
+
+# ---- the definition at the longest axis a scene may have ------------------------------------------------------------------------
+
+NEEDLES = extents_common.NEEDLES + extents_common.RAGGED + extents_common.LINES      # the needle rows of tests/test_gpu_scene_build.py's DIMS
+
+
+@pytest.mark.parametrize("dims", NEEDLES, ids=lambda d: "x".join(str(v) for v in d))
+def test_the_definition_at_a_4096_axis(dims):
+    """the needles of tests/test_gpu_scene_build.py (content of tests/extents_common.py; on the lines sparse voxels and both ends): clearance
+    and open cells against the literal cube and box at the corners, along both ends of the long axis, at the clearance's cap and at
+    random points; the pyramid and the cell list against a literal loop over the solid voxels -- cell coordinates 0 and 1023 occur,
+    and 1023 is the largest"""
+    W, H, D = dims
+    a = int(np.argmax(dims))
+    L = dims[a]
+    rng = np.random.default_rng(L + a)
+    if min(dims) > 1:
+        vol = extents_common.needle_volume(dims)
+    else:
+        vol = ((rng.random((D, H, W)) < 0.004) * rng.integers(1, 256, (D, H, W))).astype(np.uint8)
+        vol.reshape(-1)[[0, L - 1]] = 7
+    solid = vol != 0
+    pts = [((W - 1) * (k & 1), (H - 1) * (k >> 1 & 1), (D - 1) * (k >> 2)) for k in range(8)]
+    for along in list(range(0, 8)) + list(range(L - 8, L)) + [100, 130, 227, 228, L - 130, L // 2 + 599, L // 2 + 602] + [int(v) for v in rng.integers(0, L, 40)]:
+        p = [int(rng.integers(0, n)) for n in dims]
+        p[a] = along
+        pts.append(tuple(p))
+    capped = False
+    for o in range(8):
+        sx, sy, sz = R.signs(o)
+        clear, op = R.clearance(vol, o, R.DF_CAP), R.open_cells(vol, o)
+        capped |= bool((clear == R.DF_CAP).any())
+        for x, y, z in pts:
+            k = 0
+            while k < R.DF_CAP:                                   # the cube of side k + 1 from (x, y, z) towards the octant
+                x0, x1 = (x, x + k + 1) if sx > 0 else (x - k, x + 1)
+                y0, y1 = (y, y + k + 1) if sy > 0 else (y - k, y + 1)
+                z0, z1 = (z, z + k + 1) if sz > 0 else (z - k, z + 1)
+                if min(x0, y0, z0) < 0 or x1 > W or y1 > H or z1 > D or solid[z0:z1, y0:y1, x0:x1].any():
+                    break
+                k += 1
+            assert clear[z, y, x] == k, (o, x, y, z, int(clear[z, y, x]), k)
+            box = solid[slice(z, D) if sz > 0 else slice(0, z + 1), slice(y, H) if sy > 0 else slice(0, y + 1), slice(x, W) if sx > 0 else slice(0, x + 1)]
+            assert bool(op[z, y, x]) == (not box.any()), (o, x, y, z)
+    assert capped == (min(dims) >= R.DF_CAP)                      # a cube's side is the needle's width at most
+    zs, ys, xs = np.nonzero(solid)
+    keys = sorted({(int(x) >> 2) | (int(y) >> 2) << 10 | (int(z) >> 2) << 20 for x, y, z in zip(xs, ys, zs)})
+    assert R.cells(vol).tolist() == keys
+    coord = [k >> (10 * a) & 1023 for k in keys]
+    assert min(coord) == 0 and max(coord) == 1023
+    n1 = R.level_dims(dims, 1)
+    exp1 = np.zeros(n1[0] * n1[1] * n1[2], np.uint64)
+    for x, y, z in zip(xs.tolist(), ys.tolist(), zs.tolist()):
+        exp1[(x >> 2) + n1[0] * ((y >> 2) + n1[1] * (z >> 2))] |= np.uint64(1) << np.uint64((x & 3) | (y & 3) << 2 | (z & 3) << 4)
+    assert (R.pyramid(vol)[0] == exp1).all()

@@ -582,6 +582,37 @@ int  vrt_reproject(vrt_ctx* ctx, int32_t W, int32_t H, const vrt_push* cur, cons
                    const vrt_reproject_settings* settings, const uint8_t* color8, const float* position, const int8_t* normal8,
                    const vrt_history* history_in, const vrt_history* history_out, uint8_t* resolved8, float* motion);
 
+/* ---- temporal reprojection for ray cameras: vrt_reproject under the three models of vrt_camera_rays -------------------------------
+ * vrt_reproject projects a hit point onto the previous screen through the push blocks' pinhole.  vrt_reproject_camera does it
+ * through a vrt_ray_camera, so that frames drawn with vrt_camera_rays + vrt_render_rays keep a history; everything else -- the
+ * history's format and vrt_history_bytes, the four taps and their exact surface test, the blend, the optional outputs, the
+ * ping-pong of history_in / history_out, asynchrony, the frame-size limits -- is vrt_reproject's.  csrc/vrt_reproject_cam.h is
+ * the definition, step by step in fp32; the GPU result equals it bit for bit.
+ * The previous-screen position of a hit point P, d = P - prev->basis.cam_pos: PERSPECTIVE is vrt_reproject's projection over the
+ * basis U = cam_right * tan_half, V = cam_up * tan_half * H / W, C = normalize(cam_dir) + jitter (with tan_half == 1.0f every
+ * plane equals vrt_reproject's under the two bases, bit for bit); ORTHOGRAPHIC solves d = sx U + sy V + l cam_dir with U, V
+ * scaled by half_width (no jitter) and keeps P if l > 0, the previous camera having seen only what lies in front of its plane;
+ * PANORAMA is skyColor's mapping, u = atan(d.z, d.x) * 0.1591 + 0.5 and t = asin(-normalize(d).y) * 0.3183 + 0.5, at pixel
+ * (u W - 0.5, t H - 0.5), for every finite d != 0.  The tap tolerance is tol_abs + tol_rel * |P - cur position| (perspective,
+ * panorama) or tol_abs + tol_rel (orthographic: a parallel view's footprint does not grow with depth).
+ * The panorama is periodic in x: a history tap at column -1 reads column W - 1, one at column W reads column 0 (and is dropped,
+ * like any tap, if it shows another surface); rows are clipped.  Its motion is the plain difference of the two screen positions,
+ * not taken the short way round: a surface that crossed the seam moves by almost +-W.
+ * cur / prev: the cameras this frame and the previous one were drawn with, as given to vrt_camera_rays (the perspective model's
+ * jitter included).  settings NULL: vrt_reproject_camera_settings_default(cur, W, ...).
+ * VRT_ERR_INVALID, before any device work: every case of vrt_reproject; cur->model != prev->model; a camera vrt_camera_rays
+ * would refuse (unknown model, a tan_half or half_width that is not finite and positive, a degenerate basis, a non-finite
+ * position or jitter), current or previous.
+ * There is no vrt_shard here, for the reason vrt_reproject gives.  vrt_upsample has no such counterpart. */
+int  vrt_reproject_camera(vrt_ctx* ctx, int32_t W, int32_t H, const vrt_ray_camera* cur, const vrt_ray_camera* prev,
+                          const vrt_reproject_settings* settings, const uint8_t* color8, const float* position,
+                          const int8_t* normal8, const vrt_history* history_in, const vrt_history* history_out,
+                          uint8_t* resolved8, float* motion);
+/* The defaults for camera `cur` and a frame W pixels wide: max_history 32, tol_abs 0.5, tol_rel two pixel footprints -- perspective
+ * 4 |cam_right| tan_half / W per unit of depth, orthographic 4 |cam_right| half_width / W voxels, panorama 2 / (0.1591 W) per unit
+ * of depth; 0 for a camera vrt_camera_rays would refuse.  Needs no device. */
+void vrt_reproject_camera_settings_default(const vrt_ray_camera* cur, int32_t W, vrt_reproject_settings* s);
+
 /* ---- temporal upsampling: a DISPLAY-resolution history from jittered render-resolution frames (the part of the FSR2 dispatch,
  * upscaler_stage.cpp:72-161, that the jitter sequence exists for; the library itself stays out of scope) -----------------------
  * vrt_reproject keeps its history at render resolution, and the step to the display is one bilinear vrt_blit of it.  vrt_upsample

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Register budget of the hand-scheduled kernels (csrc: the parts of vrt_device.hip, vrt_denoise.hip, vrt_scene_edit.hip, vrt_query.hip, vrt_reproject.hip, vrt_upsample.hip, vrt_rays.hip, vrt_render_rays.hip), checked
+"""Register budget of the hand-scheduled kernels (csrc: the parts of vrt_device.hip, vrt_denoise.hip, vrt_scene_edit.hip, vrt_query.hip, vrt_reproject.hip, vrt_reproject_cam.hip, vrt_upsample.hip, vrt_rays.hip, vrt_render_rays.hip), checked
 at build time.
 
 K1's look-up loop pins physical registers and the kernel sits at two occupancy cliffs that the compiler's own remark does
@@ -67,6 +67,11 @@ BUDGET = {
     "k_queryILi6ELb0ELb1EE": ("pixel pick, brick march", 64, 80, 0),
     # temporal reprojection (vrt_reproject.hip): a streaming kernel with a four-tap gather; eight waves per SIMD, no scratch (40 VGPRs, 58 SGPRs)
     "k_reprojectENS_15ReprojectParamsE": ("temporal reprojection", 64, 80, 0),
+    # temporal reprojection for ray cameras (vrt_reproject_cam.hip): k_reproject's memory side, one instantiation per camera model
+    # (40 VGPRs each; 58 / 50 / 48 SGPRs); eight waves per SIMD, no scratch, no LDS
+    "k_reproject_camILi0EE": ("temporal reprojection, perspective camera", 64, 80, 0),
+    "k_reproject_camILi1EE": ("temporal reprojection, orthographic camera", 64, 80, 0),
+    "k_reproject_camILi2EE": ("temporal reprojection, panorama", 64, 80, 0),
     # temporal upsampling (vrt_upsample.hip): one thread per display pixel, two projections and the same four-tap gather; eight
     # waves per SIMD, no scratch (40 VGPRs, 62 SGPRs)
     "k_upsampleENS_14UpsampleParamsE": ("temporal upsampling", 64, 80, 0),
@@ -86,7 +91,7 @@ BUDGET = {
 
 # the objects that hold budgeted kernels, as the Makefile builds them: (source, extra flags); slowest first
 OBJECTS = [("vrt_device.hip", ["-DVRT_K1_PART=%d" % n]) for n in (3, 0, 1, 2)] + [("vrt_denoise.hip", []), ("vrt_scene_edit.hip", []), ("vrt_query.hip", []),
-                                                                                     ("vrt_reproject.hip", []), ("vrt_upsample.hip", []), ("vrt_rays.hip", []),
+                                                                                     ("vrt_reproject.hip", []), ("vrt_reproject_cam.hip", []), ("vrt_upsample.hip", []), ("vrt_rays.hip", []),
                                                                                      ("vrt_render_rays.hip", [])]
 
 

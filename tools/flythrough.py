@@ -1,9 +1,11 @@
 """Scripted fly-through: replays keyboard / mouse input through CameraController (camera_controller.cpp:30-68)
 and renders every frame through the whole frame graph of voxel_renderer.cpp:55-94 -- geometry (reference defaults: AO 4,
 shadow, <= 5 bounces), 2 denoiser passes, jittered accumulation stand-in for FSR2 at the BALANCED render scale, window blit.
-   python tools/flythrough.py [--frames N] [--png-dir DIR] [--vox FILE] [--reproject [--upsample]]
+   python tools/flythrough.py [--frames N] [--png-dir DIR] [--vox FILE] [--reproject [--upsample | --projection perspective:FOV|ortho:HW|panorama]]
 --reproject keeps the history across the moving frames by temporal reprojection (vrt_reproject) instead of dropping it every frame;
 --upsample (with --reproject) keeps that history at the target resolution (vrt_upsample) instead of blitting a render-resolution one.
+--projection (with --reproject) draws the frames through that ray camera, which follows the scripted controller, and keeps the history by
+vrt_reproject_camera.
 Prints frame-time statistics measured with HIP events over the whole run (no per-frame synchronisation)."""
 import argparse, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -17,6 +19,7 @@ ap.add_argument("--vox", default=None)
 ap.add_argument("--target", default="1920x1080")
 ap.add_argument("--reproject", action="store_true")
 ap.add_argument("--upsample", action="store_true")
+ap.add_argument("--projection", default=None, help="perspective:FOV | ortho:HALFWIDTH | panorama (needs --reproject)")
 args = ap.parse_args()
 TW, TH = (int(v) for v in args.target.split("x"))
 eng = vrt.Engine(0)
@@ -27,8 +30,18 @@ else:
     sc = vrt.VoxelScene.from_dense(eng, vrt.synthetic.treehouse(N, seed=2), vrt.synthetic.default_palette(metallic_ids=range(200, 256)),
                                    sky=vrt.synthetic.sky_gradient(512, 256), noise=vrt.synthetic.blue_noise_standin(512))
 st = vrt.VoxelRenderSettings(targetResolution=(TW, TH))                      # reference defaults incl. FSR BALANCED render scale
-r = vrt.VoxelRenderer(eng, st, sc, temporal=True, windowSize=(TW, TH), reproject=args.reproject, upsample=args.upsample)
 pos, yaw, pitch = vrt.synthetic.default_camera_for(sc.width, sc.height, sc.depth)
+cam = None
+if args.projection:
+    kind, _, value = args.projection.partition(":")
+    ctrl = vrt.CameraController(position=pos, yaw=yaw, pitch=pitch)
+    if kind == "perspective" and value: cam = vrt.RayCamera.perspective(ctrl, float(value))
+    elif kind == "ortho" and value: cam = vrt.RayCamera.orthographic(ctrl, float(value))
+    elif kind == "panorama" and not value: cam = vrt.RayCamera.panorama(pos)
+    else: sys.exit("--projection perspective:FOV | ortho:HALFWIDTH | panorama")
+r = vrt.VoxelRenderer(eng, st, sc, temporal=True, windowSize=(TW, TH), reproject=args.reproject, upsample=args.upsample, camera=cam)
+if cam is not None:
+    r._camera = cam.camera                                                   # the scripted input drives the ray camera's controller
 r.camera.position = np.array(pos, np.float32); r.camera.yaw, r.camera.pitch = yaw, pitch; r.camera.updateDirectionVectors()
 third = max(1, args.frames // 3)
 keys = [vrt.CameraKey(frames=third, forward=1.0),                            # W

@@ -163,6 +163,9 @@ SYMBOLS = {
     "vrt_history_bytes": (C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
     "vrt_reproject": (C.c_int, [_P, C.c_int32, C.c_int32, C.POINTER(Push), C.POINTER(Push), C.POINTER(ReprojectSettings), _P, _P, _P,
                                 C.POINTER(History), C.POINTER(History), _P, _P]),
+    "vrt_reproject_camera_settings_default": (None, [C.POINTER(RayCamera), C.c_int32, C.POINTER(ReprojectSettings)]),
+    "vrt_reproject_camera": (C.c_int, [_P, C.c_int32, C.c_int32, C.POINTER(RayCamera), C.POINTER(RayCamera), C.POINTER(ReprojectSettings),
+                                       _P, _P, _P, C.POINTER(History), C.POINTER(History), _P, _P]),
     "vrt_upsample": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(Push), C.POINTER(Push), C.POINTER(ReprojectSettings),
                                _P, _P, _P, C.POINTER(History), C.POINTER(History), _P, _P]),
     "vrt_jitter_phase_count": (C.c_int32, [C.c_int32, C.c_int32]),

@@ -1,6 +1,6 @@
 // vrt_api_post.hip -- what the C-ABI does with rendered images: the denoiser stage, strip packing, presentation (blit, accumulate,
-// resolve), temporal reprojection and temporal upsampling.  Host code only; the kernels are vrt_denoise.hip, vrt_post.hip,
-// vrt_reproject.hip and vrt_upsample.hip.
+// resolve), temporal reprojection (push blocks and ray cameras) and temporal upsampling.  Host code only; the kernels are
+// vrt_denoise.hip, vrt_post.hip, vrt_reproject.hip, vrt_reproject_cam.hip and vrt_upsample.hip.
 //
 // Call surface mirrored from the reference (paths relative to its root):
 //   DenoiserStage::record      source/voxels/stages/denoiser_stage.cpp:143-154,156-258
@@ -9,6 +9,7 @@
 
 #include "vrt_host.h"
 #include "vrt_denoise_bound.h"
+#include "vrt_reproject_cam.h"
 
 using namespace vrt;
 
@@ -356,6 +357,76 @@ int vrt_reproject(vrt_ctx* c, int32_t W, int32_t H, const vrt_push* cur, const v
     p.resolved8 = (uint32_t*)resolved8; p.motion = motion;
     HIPCHK(hipSetDevice(c->device));
     HIPCHK(launch_reproject(p, c->stream));
+    return VRT_OK;
+}
+
+// ---- temporal reprojection for ray cameras (csrc/vrt_reproject_cam.h is the definition, vrt_reproject_cam.hip the kernel) ----
+
+static void reproject_camera_defaults(const vrt_ray_camera* cur, int W, vrt_reproject_settings* s)
+{
+    s->max_history = 32;
+    s->tol_abs = 0.5f;
+    s->tol_rel = cur ? reproject_cam_default_tol_rel(*cur, W) : 0.0f;
+}
+
+void vrt_reproject_camera_settings_default(const vrt_ray_camera* cur, int32_t W, vrt_reproject_settings* s)
+{
+    if (s) reproject_camera_defaults(cur, W, s);
+}
+
+int vrt_reproject_camera(vrt_ctx* c, int32_t W, int32_t H, const vrt_ray_camera* cur, const vrt_ray_camera* prev,
+                         const vrt_reproject_settings* settings, const uint8_t* color8, const float* position,
+                         const int8_t* normal8, const vrt_history* history_in, const vrt_history* history_out, uint8_t* resolved8,
+                         float* motion)
+{
+    // every argument error is reported before the context or a device is looked at
+    if (!c || !cur || !prev || !color8 || !position || !normal8 || !history_out || !history_out->color16 || !history_out->surface ||
+        (history_in && (!history_in->color16 || !history_in->surface)))
+        return fail(VRT_ERR_INVALID, "vrt_reproject_camera: NULL argument");
+    if (W <= 0 || H <= 0 || W > 32768 || H > 32768) return fail(VRT_ERR_INVALID, "vrt_reproject_camera: bad frame size");
+    if ((int64_t)W * (int64_t)H >= ((int64_t)1 << 28))
+        return fail(VRT_ERR_UNSUPPORTED, "vrt_reproject_camera: 2^28 pixels or more per frame (the limit of vrt_render_geometry)");
+    vrt_reproject_settings st;
+    if (settings) st = *settings;
+    else reproject_camera_defaults(cur, W, &st);
+    if (st.max_history < 1u || st.max_history > 255u) return fail(VRT_ERR_INVALID, "vrt_reproject_camera: max_history must be in 1..255");
+    if (!(st.tol_abs >= 0.0f) || !(st.tol_rel >= 0.0f) || !rp_finite(st.tol_abs) || !rp_finite(st.tol_rel))
+        return fail(VRT_ERR_INVALID, "vrt_reproject_camera: a tolerance is negative or not finite");
+    ReprojectCamConsts ck;
+    switch (reproject_cam_consts(W, H, *cur, *prev, st.tol_abs, st.tol_rel, st.max_history, ck)) {
+    case 0: break;
+    case 1: return fail(VRT_ERR_INVALID, "vrt_reproject_camera: the current and the previous camera are of different models");
+    case 2: return fail(VRT_ERR_INVALID, "vrt_reproject_camera: the current camera is not one vrt_camera_rays accepts (unknown model, bad tan_half / half_width, degenerate basis, non-finite position or jitter)");
+    case 3: return fail(VRT_ERR_INVALID, "vrt_reproject_camera: the previous camera is not one vrt_camera_rays accepts (unknown model, bad tan_half / half_width, degenerate basis, non-finite position or jitter)");
+    default: return fail(VRT_ERR_INVALID, "vrt_reproject_camera: the previous camera's basis is degenerate (zero or non-finite determinant)");
+    }
+    const size_t n = (size_t)W * (size_t)H;
+    struct Range { const char* lo; size_t bytes; bool out; };
+    const Range rg[9] = {
+        {(const char*)color8, n * 4, false}, {(const char*)position, n * 16, false}, {(const char*)normal8, n * 4, false},
+        {history_in ? (const char*)history_in->color16 : nullptr, n * 8, false},
+        {history_in ? (const char*)history_in->surface : nullptr, n * 16, false},
+        {(const char*)history_out->color16, n * 8, true}, {(const char*)history_out->surface, n * 16, true},
+        {(const char*)resolved8, n * 4, true}, {(const char*)motion, n * 8, true}};
+    for (int a = 0; a < 9; a++)
+        for (int b = a + 1; b < 9; b++) {
+            if (!rg[a].lo || !rg[b].lo || (!rg[a].out && !rg[b].out)) continue;
+            if ((uintptr_t)rg[a].lo < (uintptr_t)rg[b].lo + rg[b].bytes && (uintptr_t)rg[b].lo < (uintptr_t)rg[a].lo + rg[a].bytes)
+                return fail(VRT_ERR_INVALID, "vrt_reproject_camera: an output overlaps another buffer (the history is gathered: in and out must differ)");
+        }
+    if ((((uintptr_t)position | (uintptr_t)history_out->surface | (uintptr_t)(history_in ? history_in->surface : nullptr)) & 15u) != 0u ||
+        (((uintptr_t)history_out->color16 | (uintptr_t)(history_in ? history_in->color16 : nullptr) | (uintptr_t)motion) & 7u) != 0u ||
+        (((uintptr_t)color8 | (uintptr_t)normal8 | (uintptr_t)resolved8) & 3u) != 0u)
+        return fail(VRT_ERR_INVALID, "vrt_reproject_camera: a plane is not aligned to its texel size");
+    ReprojectParams p;
+    p.k = ck.k;
+    p.color8 = (const uint32_t*)color8; p.position = (const rp_u4*)position; p.normal8 = (const uint32_t*)normal8;
+    p.hist_color = history_in ? (const rp_u2*)history_in->color16 : nullptr;
+    p.hist_surface = history_in ? (const rp_u4*)history_in->surface : nullptr;
+    p.out_color = (rp_u2*)history_out->color16; p.out_surface = (rp_u4*)history_out->surface;
+    p.resolved8 = (uint32_t*)resolved8; p.motion = motion;
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(launch_reproject_cam(ck.model, p, c->stream));
     return VRT_OK;
 }
 

@@ -324,7 +324,7 @@ struct UpsampleParams {
 
 // launchers: scene build (vrt_scene_build.hip), scene edits (vrt_scene_edit.hip), render (vrt_device.hip: sky, tile tags, hit
 // colours, K1, K2), K3 (vrt_denoise.hip), rows / blit / accumulate / resolve (vrt_post.hip), reprojection (vrt_reproject.hip),
-// upsampling (vrt_upsample.hip), ray generation (vrt_rays.hip), shading of caller-supplied rays (vrt_render_rays.hip)
+// upsampling (vrt_upsample.hip), reprojection for ray cameras (vrt_reproject_cam.hip), ray generation (vrt_rays.hip), shading of caller-supplied rays (vrt_render_rays.hip)
 hipError_t launch_build_pyramid(const uint8_t* vox, int W, int H, int D, uint64_t* occ1, uint64_t* occ2,
                                 uint64_t* occ3, hipStream_t s);
 hipError_t launch_build_df(const uint8_t* vox, int W, int H, int D, uint8_t* df, size_t stride, uint8_t* tmp0, uint8_t* tmp1, hipStream_t s, int cap = 0 /* 0: the dense scene's cap */);
@@ -374,6 +374,8 @@ hipError_t launch_accumulate(const void* color_rgba8, void* accum_u32x4, size_t 
 hipError_t launch_resolve(const void* accum_u32x4, void* out_rgba8, size_t n, uint32_t frames, hipStream_t s);
 hipError_t launch_reproject(const ReprojectParams& p, hipStream_t s);
 hipError_t launch_upsample(const UpsampleParams& p, hipStream_t s);
+// (vrt_reproject_cam.hip: k_reproject_cam<model> takes k_reproject's parameters; model: VRT_CAMERA_*)
+hipError_t launch_reproject_cam(int model, const ReprojectParams& p, hipStream_t s);
 hipError_t launch_camera_rays(const RayCamConsts& k, const float* col, const float* row, float* origins, float* dirs, hipStream_t s);
 const char* primary_kernel_name(int traversal, int fused, int occ2_lds);
 

@@ -904,6 +904,7 @@ class UpscalerStage:
         self._hist = None              # two (color16, surface) pairs, written in turn
         self._hist_cur = -1            # the pair the latest frame wrote; -1: no history
         self._prev_push = None
+        self._prev_camera = None       # record_reprojected_camera: the previous frame's vrt_ray_camera
         self.jitterX = 0.0
         self.jitterY = 0.0
         self.frameCount = 0
@@ -956,6 +957,43 @@ class UpscalerStage:
                                   C.byref(hout), self._resolved.data_ptr(), motion.data_ptr() if motion is not None else None))
         self._hist_cur = nxt
         self._prev_push = _capi.Push.from_buffer_copy(push)
+        self.accumulated += 1
+        check(lib().vrt_blit(self.engine.ctx, self._resolved.data_ptr(), W, H, self._target.data_ptr(), TW, TH))
+        return self._target
+
+    def record_reprojected_camera(self, color, gbuffer: "GeometryBuffer", ray_camera_c: _capi.RayCamera):
+        """record_reprojected() for a frame drawn through a RayCamera (vrt_reproject_camera): ray_camera_c is the vrt_ray_camera
+        block the frame's rays were made with (RayCamera.to_c(resolution, jitter)); the previous frame's is kept here, as
+        record_reprojected() keeps the previous push.  One stage records through one of the two: their histories are the same
+        buffers.  reprojectSettings.tolRel None is the camera model's default."""
+        torch = _torch()
+        H, W = color.shape[0], color.shape[1]
+        TW, TH = self._settings.targetResolution
+        if self._hist is None or self._hist[0][0].shape[:2] != (H, W) or self._resolved is None or self._resolved.shape[:2] != (H, W):
+            self._hist = [(torch.zeros((H, W, 4), dtype=torch.int16, device=color.device),
+                           torch.zeros((H, W, 4), dtype=torch.int32, device=color.device)) for _ in range(2)]
+            self._resolved = torch.zeros((H, W, 4), dtype=torch.uint8, device=color.device)
+            self._accum = None
+            self._hist_cur = -1
+        if self._target is None or self._target.shape[:2] != (TH, TW):
+            self._target = torch.zeros((TH, TW, 4), dtype=torch.uint8, device=color.device)
+        if self._hist_cur >= 0 and (self._prev_camera is None or self._prev_camera.model != ray_camera_c.model):
+            self._hist_cur = -1                                    # another camera model: a new sequence
+        prev = self._prev_camera if self._hist_cur >= 0 else ray_camera_c
+        nxt = 1 - self._hist_cur if self._hist_cur >= 0 else 0
+        hin = _capi.History(self._hist[self._hist_cur][0].data_ptr(), self._hist[self._hist_cur][1].data_ptr()) if self._hist_cur >= 0 else None
+        hout = _capi.History(self._hist[nxt][0].data_ptr(), self._hist[nxt][1].data_ptr())
+        st = _capi.ReprojectSettings()
+        lib().vrt_reproject_camera_settings_default(C.byref(ray_camera_c), W, C.byref(st))
+        st.max_history, st.tol_abs = int(self.reprojectSettings.maxHistory), float(self.reprojectSettings.tolAbs)
+        if self.reprojectSettings.tolRel is not None:
+            st.tol_rel = float(self.reprojectSettings.tolRel)
+        motion = gbuffer.planes.get("motion")
+        check(lib().vrt_reproject_camera(self.engine.ctx, W, H, C.byref(ray_camera_c), C.byref(prev), C.byref(st), color.data_ptr(),
+                                         gbuffer.position.data_ptr(), gbuffer.normal.data_ptr(), C.byref(hin) if hin is not None else None,
+                                         C.byref(hout), self._resolved.data_ptr(), motion.data_ptr() if motion is not None else None))
+        self._hist_cur = nxt
+        self._prev_camera = _capi.RayCamera.from_buffer_copy(ray_camera_c)
         self.accumulated += 1
         check(lib().vrt_blit(self.engine.ctx, self._resolved.data_ptr(), W, H, self._target.data_ptr(), TW, TH))
         return self._target
@@ -1045,13 +1083,18 @@ class VoxelRenderer:
     targetResolution instead (UpscalerStage.record_upsampled: no blit, display-resolution motion in upscaler.motion);
     upsample=False is the render-resolution path exactly.  camera=RayCamera(...): the G-buffer is drawn from that camera's rays
     (RayCamera.rays + GeometryStage.record_rays) instead of the built-in pinhole; the denoiser and the writers run unchanged.
-    Not with temporal=True: the reprojection projects through the pinhole."""
+    With temporal=True it needs reproject=True: the temporal pass is then UpscalerStage.record_reprojected_camera
+    (vrt_reproject_camera) over the camera's to_c(resolution, jitter) of the frame, and gBuffer.motion holds its vectors.  The
+    accumulation (a moving ray camera has no pixel-wise history) and upsample=True (vrt_upsample projects through the pinhole)
+    are refused."""
 
     def __init__(self, engine: Engine, settings: Optional[VoxelRenderSettings] = None, scene: Optional[VoxelScene] = None,
                  noise=None, debug_planes: bool = False, temporal: bool = False, windowSize=None, reproject: bool = False,
                  upsample: bool = False, camera: Optional["RayCamera"] = None):
-        if camera is not None and temporal:
-            raise ValueError("VoxelRenderer: temporal=True with a RayCamera is not supported (the reprojection projects through the built-in pinhole)")
+        if camera is not None and temporal and not reproject:
+            raise ValueError("VoxelRenderer: temporal=True with a RayCamera needs reproject=True (the pixel-by-pixel accumulation is wrong for a moving ray camera)")
+        if camera is not None and upsample:
+            raise ValueError("VoxelRenderer: upsample=True with a RayCamera is not supported (vrt_upsample projects through the built-in pinhole)")
         if upsample and not reproject:
             raise ValueError("VoxelRenderer: upsample=True needs reproject=True (the display-resolution history is a reprojected one)")
         self.engine = engine
@@ -1120,6 +1163,7 @@ class VoxelRenderer:
                 raise ValueError("VoxelRenderer: a RayCamera renders whole frames (vrt_render_rays has no vrt_shard)")
             res = self._settings.renderResolution()
             origins, dirs = self.rayCamera.rays(self.engine, res, self.jitter)
+            ray_camera_c = self.rayCamera.to_c(res, self.jitter)
             gBuffer = self._geometryStage.record_rays(origins, dirs, res, self.frameCount)
         else:
             gBuffer = self._geometryStage.record(push, shard)
@@ -1132,7 +1176,9 @@ class VoxelRenderer:
             if self.reproject:
                 if shard is not None:
                     raise ValueError("VoxelRenderer: reprojection across strips is not supported (include/vrt.h, vrt_reproject)")
-                if self.upsample:
+                if self.rayCamera is not None:
+                    color = self._upscalerStage.record_reprojected_camera(color, gBuffer, ray_camera_c)
+                elif self.upsample:
                     color = self._upscalerStage.record_upsampled(color, gBuffer, push)
                 else:
                     color = self._upscalerStage.record_reprojected(color, gBuffer, push)

@@ -344,6 +344,33 @@ public:
         check(vrt_blit(engine->ctx, resolved->ptr, (int32_t)w, (int32_t)h, target->ptr, (int32_t)settings->targetResolution[0], (int32_t)settings->targetResolution[1]));
         return target->ptr;
     }
+    // recordReprojected() for a frame drawn through a vrt_ray_camera (vrt_reproject_camera): cam is the block the frame's rays were
+    // made with; the previous frame's is kept here.  The histories are recordReprojected()'s buffers.
+    const uint8_t* recordReprojectedCamera(const uint8_t* color, const GeometryBuffer& g, const vrt_ray_camera& cam)
+    {
+        const uint32_t w = g.width, h = g.height;
+        size_t n = (size_t)w * h;
+        if (!histColor[0] || histColor[0]->count != n * 4) {
+            for (int k = 0; k < 2; k++) { histColor[k] = std::make_shared<DeviceBuffer<uint16_t>>(engine, n * 4); histSurface[k] = std::make_shared<DeviceBuffer<uint32_t>>(engine, n * 4); }
+            histCur = -1;
+        }
+        if (!resolved || resolved->count != n * 4) { resolved = std::make_shared<DeviceBuffer<uint8_t>>(engine, n * 4); accum.reset(); }
+        size_t tn = (size_t)settings->targetResolution[0] * settings->targetResolution[1] * 4;
+        if (!target || target->count != tn) target = std::make_shared<DeviceBuffer<uint8_t>>(engine, tn);
+        if (histCur >= 0 && prevCamera.model != cam.model) histCur = -1;               // another camera model: a new sequence
+        vrt_reproject_settings st; vrt_reproject_camera_settings_default(&cam, (int32_t)w, &st);
+        if (reprojectSettings.max_history != 0) st.max_history = reprojectSettings.max_history;
+        st.tol_abs = reprojectSettings.tol_abs;
+        if (reprojectSettings.tol_rel >= 0) st.tol_rel = reprojectSettings.tol_rel;
+        const int nxt = histCur >= 0 ? 1 - histCur : 0;
+        vrt_history in{}, out{histColor[nxt]->ptr, histSurface[nxt]->ptr};
+        if (histCur >= 0) { in.color16 = histColor[histCur]->ptr; in.surface = histSurface[histCur]->ptr; }
+        check(vrt_reproject_camera(engine->ctx, (int32_t)w, (int32_t)h, &cam, histCur >= 0 ? &prevCamera : &cam, &st, color, g.position->ptr, g.normal->ptr,
+                                   histCur >= 0 ? &in : nullptr, &out, resolved->ptr, g.motion->ptr));
+        histCur = nxt; prevCamera = cam; accumulated++;
+        check(vrt_blit(engine->ctx, resolved->ptr, (int32_t)w, (int32_t)h, target->ptr, (int32_t)settings->targetResolution[0], (int32_t)settings->targetResolution[1]));
+        return target->ptr;
+    }
     // The temporal pass at display resolution (vrt_upsample): the history pair, the resolved image and the motion vectors
     // (motion(), in display pixels; g.motion is not touched) live at targetResolution, every sample where it fell on the display grid.
     const uint8_t* recordUpsampled(const uint8_t* color, const GeometryBuffer& g, const vrt_push& push)
@@ -384,7 +411,7 @@ public:
 private:
     std::shared_ptr<Engine> engine; std::shared_ptr<VoxelRenderSettings> settings; float _deltaMsec = 0;
     std::shared_ptr<DeviceBuffer<uint32_t>> accum; std::shared_ptr<DeviceBuffer<uint8_t>> resolved, target;
-    std::shared_ptr<DeviceBuffer<uint16_t>> histColor[2]; std::shared_ptr<DeviceBuffer<uint32_t>> histSurface[2]; int histCur = -1; vrt_push prevPush{};
+    std::shared_ptr<DeviceBuffer<uint16_t>> histColor[2]; std::shared_ptr<DeviceBuffer<uint32_t>> histSurface[2]; int histCur = -1; vrt_push prevPush{}; vrt_ray_camera prevCamera{};
     std::shared_ptr<DeviceBuffer<float>> displayMotion;
 };
 
@@ -431,15 +458,18 @@ public:
     // recordCommands (:55-94); returns the RGBA8 image (host copy) and its size in outW / outH.
     // temporal: take the FSR branch (:86-87) through the accumulation stand-in -- or, with reproject, through temporal reprojection,
     // which keeps the history under a moving camera and fills gBuffer.motion -- with upsample too, at targetResolution (temporal
-    // upsampling: no blit, motion in upscaler().motion()); windowW/H != 0: append the blit (:89).
+    // upsampling: no blit, motion in upscaler().motion()); windowW/H != 0: append the blit (:89).  With a projection the temporal
+    // pass is vrt_reproject_camera (reproject is required, upsample refused).
     std::vector<uint8_t> render(uint32_t* outW = nullptr, uint32_t* outH = nullptr)
     {
         vrt_push push = pushConstants();
         GeometryBuffer g;
+        vrt_ray_camera cam{};
         if (projection >= 0) {
             // another camera model: its rays (vrt_camera_rays over this renderer's camera basis and jitter), then their G-buffer
-            if (temporal) throw std::runtime_error("VoxelRenderer: temporal with a projection is not supported (the reprojection projects through the built-in pinhole)");
-            vrt_ray_camera cam{}; cam.model = projection; cam.basis = push; cam.tan_half = tanHalf; cam.half_width = halfWidth;
+            if (temporal && !reproject) throw std::runtime_error("VoxelRenderer: temporal with a projection needs reproject (the pixel-by-pixel accumulation is wrong for a moving ray camera)");
+            if (upsample) throw std::runtime_error("VoxelRenderer: upsample with a projection is not supported (vrt_upsample projects through the built-in pinhole)");
+            cam.model = projection; cam.basis = push; cam.tan_half = tanHalf; cam.half_width = halfWidth;
             const size_t n = (size_t)push.screen_size[0] * (size_t)push.screen_size[1];
             if (!_rayOrigins || _rayOrigins->count != 3 * n) { _rayOrigins = std::make_unique<DeviceBuffer<float>>(engine, 3 * n); _rayDirs = std::make_unique<DeviceBuffer<float>>(engine, 3 * n); }
             check(vrt_camera_rays(engine->ctx, &cam, push.screen_size[0], push.screen_size[1], _rayOrigins->ptr, _rayDirs->ptr));
@@ -447,7 +477,7 @@ public:
         } else g = _geometryStage->record(push);
         const uint8_t* img = _settings->denoiserSettings.enable ? _denoiserStage->record(g) : g.color->ptr;
         uint32_t w = g.width, h = g.height;
-        if (temporal && _settings->fsrSetttings.enable) { if (upsample && !reproject) throw std::runtime_error("VoxelRenderer: upsample needs reproject"); img = !reproject ? _upscalerStage->record(img, w, h) : upsample ? _upscalerStage->recordUpsampled(img, g, push) : _upscalerStage->recordReprojected(img, g, push); w = _settings->targetResolution[0]; h = _settings->targetResolution[1]; }
+        if (temporal && _settings->fsrSetttings.enable) { if (upsample && !reproject) throw std::runtime_error("VoxelRenderer: upsample needs reproject"); img = !reproject ? _upscalerStage->record(img, w, h) : projection >= 0 ? _upscalerStage->recordReprojectedCamera(img, g, cam) : upsample ? _upscalerStage->recordUpsampled(img, g, push) : _upscalerStage->recordReprojected(img, g, push); w = _settings->targetResolution[0]; h = _settings->targetResolution[1]; }
         if (windowW && windowH) { img = _blitStage->record(img, w, h, windowW, windowH); w = windowW; h = windowH; }
         std::vector<uint8_t> host((size_t)w * h * 4);
         check(vrt_memcpy_d2h(engine->ctx, host.data(), img, host.size()));

@@ -121,6 +121,60 @@ def test_temporal_frame_graph_vs_oracle(vrt, oracle, engine):
     assert (got == oracle.blit(oracle.blit(den, target[0], target[1]), 120, 120)).all()
 
 
+def test_one_stage_through_all_three_temporal_passes(vrt, engine):
+    """One UpscalerStage fed through record_reprojected, record_upsampled and record_reprojected_camera in turn, a still camera
+    throughout: after every call the count byte of the hit pixels of history() says whether the call continued a sequence
+    (maximum 2) or began one (all 1).  A new sequence has no history in, so every count is 1: after the history changed its
+    size (either way between render and target resolution), on the first ray camera (there is no previous one), on another
+    camera model, after reset().  `accumulated` rises by one per call."""
+    import reproject_common as rc
+    vol, pal, sky, noise = rc.scene_of(vrt, 1)
+    sc = vrt.VoxelScene.from_dense(engine, vol, pal, sky=sky, noise=noise)
+    st = vrt.VoxelRenderSettings(targetResolution=(128, 64))
+    st.fsrSetttings.scaling = vrt.FsrScaling.PERFORMANCE
+    res = st.renderResolution()
+    assert res == (64, 32)
+    geo, up = vrt.GeometryStage(engine, st, sc), vrt.UpscalerStage(engine, st)
+    ctl = vrt.CameraController(position=(20.3, 20.2, -14.0), yaw=90.0, pitch=0.0)
+    push = vrt.make_push(ctl, vol.shape, res, 1)
+    calls = [0]
+
+    def counts(shape):
+        engine.synchronize()
+        calls[0] += 1
+        assert up.accumulated == calls[0]
+        color16, surface = up.history()
+        assert color16.shape == surface.shape == shape + (4,)
+        hit = (surface[..., 3] & 0xFFFFFF) != 0                              # a miss keeps no normal
+        assert hit.any()
+        return surface[..., 3][hit] >> 24
+
+    def by_push(method):
+        gb = geo.record(push)
+        out = method(gb.color, gb, push)
+        assert tuple(out.shape) == (64, 128, 4)
+
+    def by_camera(camera):
+        o, d = camera.rays(engine, res)
+        gb = geo.record_rays(o, d, res, 1)
+        out = up.record_reprojected_camera(gb.color, gb, camera.to_c(res))
+        assert tuple(out.shape) == (64, 128, 4)
+
+    by_push(up.record_reprojected); assert (counts((32, 64)) == 1).all()                        # 1
+    by_push(up.record_reprojected); assert counts((32, 64)).max() == 2                          # 2
+    by_push(up.record_upsampled); assert (counts((64, 128)) == 1).all()                         # 3: the history is another size
+    by_push(up.record_upsampled); assert counts((64, 128)).max() == 2                           # 4
+    by_push(up.record_reprojected); assert (counts((32, 64)) == 1).all()                        # 5: and back
+    persp, ortho = vrt.RayCamera.perspective(ctl), vrt.RayCamera.orthographic(ctl, 20.0)
+    by_camera(persp); assert (counts((32, 64)) == 1).all()                                      # 6: there is no previous camera
+    by_camera(persp); assert counts((32, 64)).max() == 2                                        # 7
+    by_camera(ortho); assert (counts((32, 64)) == 1).all()                                      # 8: another model
+    up.reset()
+    assert up.accumulated == 0 and up.history() is None
+    calls[0] = 0
+    by_camera(ortho); assert (counts((32, 64)) == 1).all()                                      # 9
+
+
 def test_jitter_changes_the_image_subpixel(vrt, oracle, engine):
     """cameraJitter enters rayDir in world x / y (voxel_volume.frag:319): a jittered frame differs from the unjittered
     one, but only along silhouettes (sub-pixel shift), and matches the oracle bit for bit."""

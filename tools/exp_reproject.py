@@ -120,9 +120,7 @@ for W, H in ((1920, 1080), (3840, 2160)):
         gb = r._geometryStage.record(push)
         color = r._denoiserStage.record(gb.color, gb.normal, gb.position)
         if prev is not None:
-            hin = vrt._capi.History(up._hist[up._hist_cur][0].data_ptr(), up._hist[up._hist_cur][1].data_ptr())
-            o = 1 - up._hist_cur
-            hout = vrt._capi.History(up._hist[o][0].data_ptr(), up._hist[o][1].data_ptr())
+            hin, hout = up.next_histories()
             rs = up.reprojectSettings.to_c(push)
             t_rep.append(timed(lambda: lib.vrt_reproject(eng.ctx, W, H, C.byref(push), C.byref(prev), C.byref(rs), color.data_ptr(), gb.position.data_ptr(),
                                                          gb.normal.data_ptr(), C.byref(hin), C.byref(hout), up._resolved.data_ptr(), gb.motion.data_ptr()), args.reps))

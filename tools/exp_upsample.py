@@ -60,8 +60,7 @@ for (TW, TH), scaling in (((1920, 1080), vrt.FsrScaling.BALANCED), ((3840, 2160)
         color = r._denoiserStage.record(gb.color, gb.normal, gb.position)
         if prev is not None:
             rs = up.reprojectSettings.to_c(push)
-            hin_hi = vrt._capi.History(up._hist[up._hist_cur][0].data_ptr(), up._hist[up._hist_cur][1].data_ptr())
-            hin_lo = vrt._capi.History(lo._hist[lo._hist_cur][0].data_ptr(), lo._hist[lo._hist_cur][1].data_ptr())
+            hin_hi, hin_lo = up.next_histories()[0], lo.next_histories()[0]
             hout_lo = vrt._capi.History(spare[0][0].data_ptr(), spare[0][1].data_ptr())
             hout_hi = vrt._capi.History(spare[1][0].data_ptr(), spare[1][1].data_ptr())
             f_up = lambda: lib.vrt_upsample(eng.ctx, W, H, TW, TH, C.byref(push), C.byref(prev), C.byref(rs), color.data_ptr(), gb.position.data_ptr(),

@@ -2,6 +2,9 @@
 // resolve), temporal reprojection (push blocks and ray cameras) and temporal upsampling.  Host code only; the kernels are
 // vrt_denoise.hip, vrt_post.hip, vrt_reproject.hip, vrt_reproject_cam.hip and vrt_upsample.hip.
 //
+// vrt_reproject, vrt_reproject_camera and vrt_upsample state their common argument rules once, in file-local helpers: temporal_null,
+// temporal_defaults / temporal_settings, temporal_planes (overlap, then alignment) and temporal_fill (the parameter block's pointers).
+//
 // Call surface mirrored from the reference (paths relative to its root):
 //   DenoiserStage::record      source/voxels/stages/denoiser_stage.cpp:143-154,156-258
 #include <cmath>
@@ -287,19 +290,84 @@ int vrt_resolve(vrt_ctx* c, const void* accum_u32, void* out_rgba8, int32_t W, i
     return VRT_OK;
 }
 
-// ---- temporal reprojection (csrc/vrt_reproject.h is the definition, vrt_reproject.hip the kernel) ----
+} // extern "C"
 
-// the default settings for camera `cur` and a frame W pixels wide
-static void reproject_defaults(const vrt_push* cur, int W, vrt_reproject_settings* s)
+// ---- the temporal passes: what vrt_reproject, vrt_reproject_camera and vrt_upsample share --------------
+// Each check takes the entry point's name for its message and returns VRT_OK or what fail() returned.  An entry point applies them
+// in this order, between its own rules: temporal_null, (its size rules), temporal_settings, (its constants), temporal_planes --
+// and only then looks at the context.
+
+// The seven plane arguments of a temporal pass.  The three current planes hold one texel per pixel of the frame; the histories,
+// resolved8 and motion one per texel of the history (the same count, but for vrt_upsample)
+struct TemporalPlanes {
+    const uint8_t* color8; const float* position; const int8_t* normal8;
+    const vrt_history* history_in; const vrt_history* history_out; uint8_t* resolved8; float* motion;
+};
+
+static int temporal_null(const char* fn, const vrt_ctx* c, const void* cur, const void* prev, const TemporalPlanes& pl)
 {
-    s->max_history = 32;
-    s->tol_abs = 0.5f;
-    s->tol_rel = (cur && W > 0) ? reproject_default_tol_rel(cur->cam_right, W) : 0.0f;
+    if (!c || !cur || !prev || !pl.color8 || !pl.position || !pl.normal8 || !pl.history_out || !pl.history_out->color16 ||
+        !pl.history_out->surface || (pl.history_in && (!pl.history_in->color16 || !pl.history_in->surface)))
+        return fail(VRT_ERR_INVALID, std::string(fn) + ": NULL argument");
+    return VRT_OK;
 }
+
+// the default settings, given the default tol_rel of the camera they are for
+static void temporal_defaults(float tol_rel, vrt_reproject_settings* s) { s->max_history = 32; s->tol_abs = 0.5f; s->tol_rel = tol_rel; }
+
+// st: the caller's settings, or the defaults; then the rules for either
+static int temporal_settings(const char* fn, const vrt_reproject_settings* settings, float default_tol_rel, vrt_reproject_settings& st)
+{
+    if (settings) st = *settings;
+    else temporal_defaults(default_tol_rel, &st);
+    if (st.max_history < 1u || st.max_history > 255u) return fail(VRT_ERR_INVALID, std::string(fn) + ": max_history must be in 1..255");
+    if (!(st.tol_abs >= 0.0f) || !(st.tol_rel >= 0.0f) || !rp_finite(st.tol_abs) || !rp_finite(st.tol_rel))
+        return fail(VRT_ERR_INVALID, std::string(fn) + ": a tolerance is negative or not finite");
+    return VRT_OK;
+}
+
+// No output overlaps another plane, then every plane is aligned to its texel: over a frame of n texels and a history of tn
+static int temporal_planes(const char* fn, const TemporalPlanes& pl, size_t n, size_t tn)
+{
+    const vrt_history* hin = pl.history_in;
+    const vrt_history* hout = pl.history_out;
+    struct Range { const char* lo; size_t bytes; bool out; };
+    const Range rg[9] = {
+        {(const char*)pl.color8, n * 4, false}, {(const char*)pl.position, n * 16, false}, {(const char*)pl.normal8, n * 4, false},
+        {hin ? (const char*)hin->color16 : nullptr, tn * 8, false}, {hin ? (const char*)hin->surface : nullptr, tn * 16, false},
+        {(const char*)hout->color16, tn * 8, true}, {(const char*)hout->surface, tn * 16, true},
+        {(const char*)pl.resolved8, tn * 4, true}, {(const char*)pl.motion, tn * 8, true}};
+    for (int a = 0; a < 9; a++)
+        for (int b = a + 1; b < 9; b++) {
+            if (!rg[a].lo || !rg[b].lo || (!rg[a].out && !rg[b].out)) continue;
+            if ((uintptr_t)rg[a].lo < (uintptr_t)rg[b].lo + rg[b].bytes && (uintptr_t)rg[b].lo < (uintptr_t)rg[a].lo + rg[a].bytes)
+                return fail(VRT_ERR_INVALID, std::string(fn) + ": an output overlaps another buffer (the history is gathered: in and out must differ)");
+        }
+    if ((((uintptr_t)pl.position | (uintptr_t)hout->surface | (uintptr_t)(hin ? hin->surface : nullptr)) & 15u) != 0u ||
+        (((uintptr_t)hout->color16 | (uintptr_t)(hin ? hin->color16 : nullptr) | (uintptr_t)pl.motion) & 7u) != 0u ||
+        (((uintptr_t)pl.color8 | (uintptr_t)pl.normal8 | (uintptr_t)pl.resolved8) & 3u) != 0u)
+        return fail(VRT_ERR_INVALID, std::string(fn) + ": a plane is not aligned to its texel size");
+    return VRT_OK;
+}
+
+// the nine pointer members of ReprojectParams / UpsampleParams
+template <class Params>
+static void temporal_fill(Params& p, const TemporalPlanes& pl)
+{
+    p.color8 = (const uint32_t*)pl.color8; p.position = (const rp_u4*)pl.position; p.normal8 = (const uint32_t*)pl.normal8;
+    p.hist_color = pl.history_in ? (const rp_u2*)pl.history_in->color16 : nullptr;
+    p.hist_surface = pl.history_in ? (const rp_u4*)pl.history_in->surface : nullptr;
+    p.out_color = (rp_u2*)pl.history_out->color16; p.out_surface = (rp_u4*)pl.history_out->surface;
+    p.resolved8 = (uint32_t*)pl.resolved8; p.motion = pl.motion;
+}
+
+extern "C" {
+
+// ---- temporal reprojection (csrc/vrt_reproject.h is the definition, vrt_reproject.hip the kernel) ----
 
 void vrt_reproject_settings_default(const vrt_push* cur, vrt_reproject_settings* s)
 {
-    if (s) reproject_defaults(cur, cur ? cur->screen_size[0] : 0, s);
+    if (s) temporal_defaults((cur && cur->screen_size[0] > 0) ? reproject_default_tol_rel(cur->cam_right, cur->screen_size[0]) : 0.0f, s);
 }
 
 int vrt_history_bytes(int32_t W, int32_t H, size_t* color16, size_t* surface)
@@ -316,45 +384,21 @@ int vrt_reproject(vrt_ctx* c, int32_t W, int32_t H, const vrt_push* cur, const v
                   const vrt_history* history_out, uint8_t* resolved8, float* motion)
 {
     // every argument error is reported before the context or a device is looked at
-    if (!c || !cur || !prev || !color8 || !position || !normal8 || !history_out || !history_out->color16 || !history_out->surface ||
-        (history_in && (!history_in->color16 || !history_in->surface)))
-        return fail(VRT_ERR_INVALID, "vrt_reproject: NULL argument");
+    static const char fn[] = "vrt_reproject";
+    const TemporalPlanes pl{color8, position, normal8, history_in, history_out, resolved8, motion};
+    if (int rc = temporal_null(fn, c, cur, prev, pl)) return rc;
     if (W <= 0 || H <= 0 || W > 32768 || H > 32768) return fail(VRT_ERR_INVALID, "vrt_reproject: bad frame size");
     if ((int64_t)W * (int64_t)H >= ((int64_t)1 << 28))
         return fail(VRT_ERR_UNSUPPORTED, "vrt_reproject: 2^28 pixels or more per frame (the limit of vrt_render_geometry)");
     vrt_reproject_settings st;
-    if (settings) st = *settings;
-    else reproject_defaults(cur, W, &st);
-    if (st.max_history < 1u || st.max_history > 255u) return fail(VRT_ERR_INVALID, "vrt_reproject: max_history must be in 1..255");
-    if (!(st.tol_abs >= 0.0f) || !(st.tol_rel >= 0.0f) || !rp_finite(st.tol_abs) || !rp_finite(st.tol_rel))
-        return fail(VRT_ERR_INVALID, "vrt_reproject: a tolerance is negative or not finite");
+    if (int rc = temporal_settings(fn, settings, reproject_default_tol_rel(cur->cam_right, W), st)) return rc;
     ReprojectParams p;
     if (!reproject_consts(W, H, prev->cam_pos, prev->cam_dir, prev->cam_right, prev->cam_up, prev->camera_jitter, cur->cam_pos,
                           st.tol_abs, st.tol_rel, st.max_history, p.k))
         return fail(VRT_ERR_INVALID, "vrt_reproject: the previous camera's basis is degenerate (zero or non-finite determinant)");
     const size_t n = (size_t)W * (size_t)H;
-    struct Range { const char* lo; size_t bytes; bool out; };
-    const Range rg[9] = {
-        {(const char*)color8, n * 4, false}, {(const char*)position, n * 16, false}, {(const char*)normal8, n * 4, false},
-        {history_in ? (const char*)history_in->color16 : nullptr, n * 8, false},
-        {history_in ? (const char*)history_in->surface : nullptr, n * 16, false},
-        {(const char*)history_out->color16, n * 8, true}, {(const char*)history_out->surface, n * 16, true},
-        {(const char*)resolved8, n * 4, true}, {(const char*)motion, n * 8, true}};
-    for (int a = 0; a < 9; a++)
-        for (int b = a + 1; b < 9; b++) {
-            if (!rg[a].lo || !rg[b].lo || (!rg[a].out && !rg[b].out)) continue;
-            if ((uintptr_t)rg[a].lo < (uintptr_t)rg[b].lo + rg[b].bytes && (uintptr_t)rg[b].lo < (uintptr_t)rg[a].lo + rg[a].bytes)
-                return fail(VRT_ERR_INVALID, "vrt_reproject: an output overlaps another buffer (the history is gathered: in and out must differ)");
-        }
-    if ((((uintptr_t)position | (uintptr_t)history_out->surface | (uintptr_t)(history_in ? history_in->surface : nullptr)) & 15u) != 0u ||
-        (((uintptr_t)history_out->color16 | (uintptr_t)(history_in ? history_in->color16 : nullptr) | (uintptr_t)motion) & 7u) != 0u ||
-        (((uintptr_t)color8 | (uintptr_t)normal8 | (uintptr_t)resolved8) & 3u) != 0u)
-        return fail(VRT_ERR_INVALID, "vrt_reproject: a plane is not aligned to its texel size");
-    p.color8 = (const uint32_t*)color8; p.position = (const rp_u4*)position; p.normal8 = (const uint32_t*)normal8;
-    p.hist_color = history_in ? (const rp_u2*)history_in->color16 : nullptr;
-    p.hist_surface = history_in ? (const rp_u4*)history_in->surface : nullptr;
-    p.out_color = (rp_u2*)history_out->color16; p.out_surface = (rp_u4*)history_out->surface;
-    p.resolved8 = (uint32_t*)resolved8; p.motion = motion;
+    if (int rc = temporal_planes(fn, pl, n, n)) return rc;
+    temporal_fill(p, pl);
     HIPCHK(hipSetDevice(c->device));
     HIPCHK(launch_reproject(p, c->stream));
     return VRT_OK;
@@ -362,16 +406,9 @@ int vrt_reproject(vrt_ctx* c, int32_t W, int32_t H, const vrt_push* cur, const v
 
 // ---- temporal reprojection for ray cameras (csrc/vrt_reproject_cam.h is the definition, vrt_reproject_cam.hip the kernel) ----
 
-static void reproject_camera_defaults(const vrt_ray_camera* cur, int W, vrt_reproject_settings* s)
-{
-    s->max_history = 32;
-    s->tol_abs = 0.5f;
-    s->tol_rel = cur ? reproject_cam_default_tol_rel(*cur, W) : 0.0f;
-}
-
 void vrt_reproject_camera_settings_default(const vrt_ray_camera* cur, int32_t W, vrt_reproject_settings* s)
 {
-    if (s) reproject_camera_defaults(cur, W, s);
+    if (s) temporal_defaults(cur ? reproject_cam_default_tol_rel(*cur, W) : 0.0f, s);
 }
 
 int vrt_reproject_camera(vrt_ctx* c, int32_t W, int32_t H, const vrt_ray_camera* cur, const vrt_ray_camera* prev,
@@ -380,18 +417,14 @@ int vrt_reproject_camera(vrt_ctx* c, int32_t W, int32_t H, const vrt_ray_camera*
                          float* motion)
 {
     // every argument error is reported before the context or a device is looked at
-    if (!c || !cur || !prev || !color8 || !position || !normal8 || !history_out || !history_out->color16 || !history_out->surface ||
-        (history_in && (!history_in->color16 || !history_in->surface)))
-        return fail(VRT_ERR_INVALID, "vrt_reproject_camera: NULL argument");
+    static const char fn[] = "vrt_reproject_camera";
+    const TemporalPlanes pl{color8, position, normal8, history_in, history_out, resolved8, motion};
+    if (int rc = temporal_null(fn, c, cur, prev, pl)) return rc;
     if (W <= 0 || H <= 0 || W > 32768 || H > 32768) return fail(VRT_ERR_INVALID, "vrt_reproject_camera: bad frame size");
     if ((int64_t)W * (int64_t)H >= ((int64_t)1 << 28))
         return fail(VRT_ERR_UNSUPPORTED, "vrt_reproject_camera: 2^28 pixels or more per frame (the limit of vrt_render_geometry)");
     vrt_reproject_settings st;
-    if (settings) st = *settings;
-    else reproject_camera_defaults(cur, W, &st);
-    if (st.max_history < 1u || st.max_history > 255u) return fail(VRT_ERR_INVALID, "vrt_reproject_camera: max_history must be in 1..255");
-    if (!(st.tol_abs >= 0.0f) || !(st.tol_rel >= 0.0f) || !rp_finite(st.tol_abs) || !rp_finite(st.tol_rel))
-        return fail(VRT_ERR_INVALID, "vrt_reproject_camera: a tolerance is negative or not finite");
+    if (int rc = temporal_settings(fn, settings, reproject_cam_default_tol_rel(*cur, W), st)) return rc;
     ReprojectCamConsts ck;
     switch (reproject_cam_consts(W, H, *cur, *prev, st.tol_abs, st.tol_rel, st.max_history, ck)) {
     case 0: break;
@@ -401,30 +434,9 @@ int vrt_reproject_camera(vrt_ctx* c, int32_t W, int32_t H, const vrt_ray_camera*
     default: return fail(VRT_ERR_INVALID, "vrt_reproject_camera: the previous camera's basis is degenerate (zero or non-finite determinant)");
     }
     const size_t n = (size_t)W * (size_t)H;
-    struct Range { const char* lo; size_t bytes; bool out; };
-    const Range rg[9] = {
-        {(const char*)color8, n * 4, false}, {(const char*)position, n * 16, false}, {(const char*)normal8, n * 4, false},
-        {history_in ? (const char*)history_in->color16 : nullptr, n * 8, false},
-        {history_in ? (const char*)history_in->surface : nullptr, n * 16, false},
-        {(const char*)history_out->color16, n * 8, true}, {(const char*)history_out->surface, n * 16, true},
-        {(const char*)resolved8, n * 4, true}, {(const char*)motion, n * 8, true}};
-    for (int a = 0; a < 9; a++)
-        for (int b = a + 1; b < 9; b++) {
-            if (!rg[a].lo || !rg[b].lo || (!rg[a].out && !rg[b].out)) continue;
-            if ((uintptr_t)rg[a].lo < (uintptr_t)rg[b].lo + rg[b].bytes && (uintptr_t)rg[b].lo < (uintptr_t)rg[a].lo + rg[a].bytes)
-                return fail(VRT_ERR_INVALID, "vrt_reproject_camera: an output overlaps another buffer (the history is gathered: in and out must differ)");
-        }
-    if ((((uintptr_t)position | (uintptr_t)history_out->surface | (uintptr_t)(history_in ? history_in->surface : nullptr)) & 15u) != 0u ||
-        (((uintptr_t)history_out->color16 | (uintptr_t)(history_in ? history_in->color16 : nullptr) | (uintptr_t)motion) & 7u) != 0u ||
-        (((uintptr_t)color8 | (uintptr_t)normal8 | (uintptr_t)resolved8) & 3u) != 0u)
-        return fail(VRT_ERR_INVALID, "vrt_reproject_camera: a plane is not aligned to its texel size");
-    ReprojectParams p;
-    p.k = ck.k;
-    p.color8 = (const uint32_t*)color8; p.position = (const rp_u4*)position; p.normal8 = (const uint32_t*)normal8;
-    p.hist_color = history_in ? (const rp_u2*)history_in->color16 : nullptr;
-    p.hist_surface = history_in ? (const rp_u4*)history_in->surface : nullptr;
-    p.out_color = (rp_u2*)history_out->color16; p.out_surface = (rp_u4*)history_out->surface;
-    p.resolved8 = (uint32_t*)resolved8; p.motion = motion;
+    if (int rc = temporal_planes(fn, pl, n, n)) return rc;
+    ReprojectParams p; p.k = ck.k;
+    temporal_fill(p, pl);
     HIPCHK(hipSetDevice(c->device));
     HIPCHK(launch_reproject_cam(ck.model, p, c->stream));
     return VRT_OK;
@@ -437,9 +449,9 @@ int vrt_upsample(vrt_ctx* c, int32_t w, int32_t h, int32_t TW, int32_t TH, const
                  const vrt_history* history_in, const vrt_history* history_out, uint8_t* resolved8, float* motion)
 {
     // every argument error is reported before the context or a device is looked at
-    if (!c || !cur || !prev || !color8 || !position || !normal8 || !history_out || !history_out->color16 || !history_out->surface ||
-        (history_in && (!history_in->color16 || !history_in->surface)))
-        return fail(VRT_ERR_INVALID, "vrt_upsample: NULL argument");
+    static const char fn[] = "vrt_upsample";
+    const TemporalPlanes pl{color8, position, normal8, history_in, history_out, resolved8, motion};
+    if (int rc = temporal_null(fn, c, cur, prev, pl)) return rc;
     if (w <= 0 || h <= 0 || TW <= 0 || TH <= 0 || TW > 32768 || TH > 32768) return fail(VRT_ERR_INVALID, "vrt_upsample: bad frame size");
     if (TW < w || TH < h) return fail(VRT_ERR_INVALID, "vrt_upsample: the display size is smaller than the render size");
     if ((int64_t)TW * (int64_t)TH >= ((int64_t)1 << 28))
@@ -447,39 +459,14 @@ int vrt_upsample(vrt_ctx* c, int32_t w, int32_t h, int32_t TW, int32_t TH, const
     if (cur->screen_size[0] != w || cur->screen_size[1] != h || prev->screen_size[0] != w || prev->screen_size[1] != h)
         return fail(VRT_ERR_INVALID, "vrt_upsample: screen_size of a push block is not the render size (w, h)");
     vrt_reproject_settings st;
-    if (settings) st = *settings;
-    else reproject_defaults(cur, w, &st);
-    if (st.max_history < 1u || st.max_history > 255u) return fail(VRT_ERR_INVALID, "vrt_upsample: max_history must be in 1..255");
-    if (!(st.tol_abs >= 0.0f) || !(st.tol_rel >= 0.0f) || !rp_finite(st.tol_abs) || !rp_finite(st.tol_rel))
-        return fail(VRT_ERR_INVALID, "vrt_upsample: a tolerance is negative or not finite");
+    if (int rc = temporal_settings(fn, settings, reproject_default_tol_rel(cur->cam_right, w), st)) return rc;
     UpsampleParams p;
     const int bad = upsample_consts(w, h, TW, TH, cur->cam_pos, cur->cam_dir, cur->cam_right, cur->cam_up, prev->cam_pos, prev->cam_dir,
                                     prev->cam_right, prev->cam_up, st.tol_abs, st.tol_rel, st.max_history, p.k);
     if (bad) return fail(VRT_ERR_INVALID, bad == 1 ? "vrt_upsample: the current camera's basis is degenerate (zero or non-finite determinant)"
                                                    : "vrt_upsample: the previous camera's basis is degenerate (zero or non-finite determinant)");
-    const size_t n = (size_t)w * (size_t)h, tn = (size_t)TW * (size_t)TH;
-    struct Range { const char* lo; size_t bytes; bool out; };
-    const Range rg[9] = {
-        {(const char*)color8, n * 4, false}, {(const char*)position, n * 16, false}, {(const char*)normal8, n * 4, false},
-        {history_in ? (const char*)history_in->color16 : nullptr, tn * 8, false},
-        {history_in ? (const char*)history_in->surface : nullptr, tn * 16, false},
-        {(const char*)history_out->color16, tn * 8, true}, {(const char*)history_out->surface, tn * 16, true},
-        {(const char*)resolved8, tn * 4, true}, {(const char*)motion, tn * 8, true}};
-    for (int a = 0; a < 9; a++)
-        for (int b = a + 1; b < 9; b++) {
-            if (!rg[a].lo || !rg[b].lo || (!rg[a].out && !rg[b].out)) continue;
-            if ((uintptr_t)rg[a].lo < (uintptr_t)rg[b].lo + rg[b].bytes && (uintptr_t)rg[b].lo < (uintptr_t)rg[a].lo + rg[a].bytes)
-                return fail(VRT_ERR_INVALID, "vrt_upsample: an output overlaps another buffer (the history is gathered: in and out must differ)");
-        }
-    if ((((uintptr_t)position | (uintptr_t)history_out->surface | (uintptr_t)(history_in ? history_in->surface : nullptr)) & 15u) != 0u ||
-        (((uintptr_t)history_out->color16 | (uintptr_t)(history_in ? history_in->color16 : nullptr) | (uintptr_t)motion) & 7u) != 0u ||
-        (((uintptr_t)color8 | (uintptr_t)normal8 | (uintptr_t)resolved8) & 3u) != 0u)
-        return fail(VRT_ERR_INVALID, "vrt_upsample: a plane is not aligned to its texel size");
-    p.color8 = (const uint32_t*)color8; p.position = (const rp_u4*)position; p.normal8 = (const uint32_t*)normal8;
-    p.hist_color = history_in ? (const rp_u2*)history_in->color16 : nullptr;
-    p.hist_surface = history_in ? (const rp_u4*)history_in->surface : nullptr;
-    p.out_color = (rp_u2*)history_out->color16; p.out_surface = (rp_u4*)history_out->surface;
-    p.resolved8 = (uint32_t*)resolved8; p.motion = motion;
+    if (int rc = temporal_planes(fn, pl, (size_t)w * (size_t)h, (size_t)TW * (size_t)TH)) return rc;
+    temporal_fill(p, pl);
     HIPCHK(hipSetDevice(c->device));
     HIPCHK(launch_upsample(p, c->stream));
     return VRT_OK;

@@ -91,13 +91,17 @@ class ReprojectSettings:
     tolAbs: float = 0.5                # voxels
     tolRel: Optional[float] = None     # voxels per unit of depth; None: two pixel footprints of the push it is used with
 
-    def to_c(self, push: _capi.Push) -> _capi.ReprojectSettings:
-        s = _capi.ReprojectSettings()
-        lib().vrt_reproject_settings_default(C.byref(push), C.byref(s))
+    def over(self, s: _capi.ReprojectSettings) -> _capi.ReprojectSettings:
+        """`s`, the defaults of some camera, overridden by what is set here."""
         s.max_history, s.tol_abs = int(self.maxHistory), float(self.tolAbs)
         if self.tolRel is not None:
             s.tol_rel = float(self.tolRel)
         return s
+
+    def to_c(self, push: _capi.Push) -> _capi.ReprojectSettings:
+        s = _capi.ReprojectSettings()
+        lib().vrt_reproject_settings_default(C.byref(push), C.byref(s))
+        return self.over(s)
 
 
 def _scale(scaling: FsrScaling, dim: int) -> int:      # voxel_render_settings.cpp:3-6
@@ -226,6 +230,21 @@ def camera_path(camera: CameraController, keys, delta: float = 1.0 / 60.0):
 def _torch():
     import torch
     return torch
+
+
+def _zeros(shape, dtype: str, device):
+    torch = _torch()
+    return torch.zeros(tuple(shape), dtype=getattr(torch, dtype), device=device)
+
+
+def _ensure(tensor, shape, dtype: str, device):
+    """`tensor` where it has `shape`; else a new one of zeros (a stage's image is recreated when its size changes)."""
+    return tensor if tensor is not None and tuple(tensor.shape) == tuple(shape) else _zeros(shape, dtype, device)
+
+
+def _ref(struct):
+    """byref of a ctypes struct, NULL for None."""
+    return C.byref(struct) if struct is not None else None
 
 
 class Engine:
@@ -930,73 +949,81 @@ class UpscalerStage:
         self.accumulated = 0
         self._hist_cur = -1
 
+    # -- the history ring of the three temporal passes: two (color16, surface) pairs, written in turn
+
+    def _ensure_histories(self, rows, cols, device, reset=False) -> bool:
+        """The two pairs at rows x cols texels; they are new, and a new sequence starts, when their shape was another or on
+        `reset`.  Returns whether that happened."""
+        if reset or self._hist is None or self._hist[0][0].shape[:2] != (rows, cols):
+            self._hist = [(_zeros((rows, cols, 4), "int16", device), _zeros((rows, cols, 4), "int32", device)) for _ in range(2)]
+            self._hist_cur = -1
+            return True
+        return False
+
+    def next_histories(self):
+        """(history_in, history_out) of the next temporal call as vrt_history structs over the stage's own pairs; history_in is
+        None when that call starts a sequence (the first one, after reset(), after a change of size)."""
+        pair = lambda k: _capi.History(self._hist[k][0].data_ptr(), self._hist[k][1].data_ptr())
+        return (pair(self._hist_cur), pair(1 - self._hist_cur)) if self._hist_cur >= 0 else (None, pair(0))
+
+    def _commit(self, attr, block):
+        """The call wrote history_out: it is the latest, and `block` the previous camera (kept as `attr`) of the next call."""
+        self._hist_cur = 1 - self._hist_cur if self._hist_cur >= 0 else 0
+        setattr(self, attr, type(block).from_buffer_copy(block))
+        self.accumulated += 1
+
+    def _ensure_target(self, device):
+        TW, TH = self._settings.targetResolution
+        self._target = _ensure(self._target, (TH, TW, 4), "uint8", device)
+
+    def _ensure_reprojected(self, H, W, device):
+        """What vrt_reproject and vrt_reproject_camera write: histories and the resolved image at render size, and the target."""
+        if self._ensure_histories(H, W, device, reset=self._resolved is None or self._resolved.shape[:2] != (H, W)):
+            self._resolved = _zeros((H, W, 4), "uint8", device)
+            self._accum = None
+        self._ensure_target(device)
+
+    def _upscaled(self, W, H):
+        """The resolved image, W x H, through the bilinear blit into the target."""
+        TW, TH = self._settings.targetResolution
+        check(lib().vrt_blit(self.engine.ctx, self._resolved.data_ptr(), W, H, self._target.data_ptr(), TW, TH))
+        return self._target
+
     def record_reprojected(self, color, gbuffer: "GeometryBuffer", push: _capi.Push):
         """The temporal pass under a moving camera (vrt_reproject): `color` (normally the denoised image) is blended into the
         history fetched where each pixel's surface was on the previous frame's screen -- the frame recorded before this one, with
         the push it was given -- and the motion vectors are written into gbuffer.motion.  Two histories are written in turn;
         reset() starts a new sequence.  Returns the resolved image at targetResolution, like record()."""
-        torch = _torch()
         H, W = color.shape[0], color.shape[1]
-        TW, TH = self._settings.targetResolution
-        if self._hist is None or self._hist[0][0].shape[:2] != (H, W) or self._resolved is None or self._resolved.shape[:2] != (H, W):
-            self._hist = [(torch.zeros((H, W, 4), dtype=torch.int16, device=color.device),
-                           torch.zeros((H, W, 4), dtype=torch.int32, device=color.device)) for _ in range(2)]
-            self._resolved = torch.zeros((H, W, 4), dtype=torch.uint8, device=color.device)
-            self._accum = None
-            self._hist_cur = -1
-        if self._target is None or self._target.shape[:2] != (TH, TW):
-            self._target = torch.zeros((TH, TW, 4), dtype=torch.uint8, device=color.device)
-        prev = self._prev_push if self._hist_cur >= 0 else push
-        nxt = 1 - self._hist_cur if self._hist_cur >= 0 else 0
-        hin = _capi.History(self._hist[self._hist_cur][0].data_ptr(), self._hist[self._hist_cur][1].data_ptr()) if self._hist_cur >= 0 else None
-        hout = _capi.History(self._hist[nxt][0].data_ptr(), self._hist[nxt][1].data_ptr())
+        self._ensure_reprojected(H, W, color.device)
+        hin, hout = self.next_histories()
         st = self.reprojectSettings.to_c(push)
         motion = gbuffer.planes.get("motion")
-        check(lib().vrt_reproject(self.engine.ctx, W, H, C.byref(push), C.byref(prev), C.byref(st), color.data_ptr(),
-                                  gbuffer.position.data_ptr(), gbuffer.normal.data_ptr(), C.byref(hin) if hin is not None else None,
-                                  C.byref(hout), self._resolved.data_ptr(), motion.data_ptr() if motion is not None else None))
-        self._hist_cur = nxt
-        self._prev_push = _capi.Push.from_buffer_copy(push)
-        self.accumulated += 1
-        check(lib().vrt_blit(self.engine.ctx, self._resolved.data_ptr(), W, H, self._target.data_ptr(), TW, TH))
-        return self._target
+        check(lib().vrt_reproject(self.engine.ctx, W, H, C.byref(push), C.byref(self._prev_push if hin is not None else push), C.byref(st),
+                                  color.data_ptr(), gbuffer.position.data_ptr(), gbuffer.normal.data_ptr(), _ref(hin), C.byref(hout),
+                                  self._resolved.data_ptr(), motion.data_ptr() if motion is not None else None))
+        self._commit("_prev_push", push)
+        return self._upscaled(W, H)
 
     def record_reprojected_camera(self, color, gbuffer: "GeometryBuffer", ray_camera_c: _capi.RayCamera):
         """record_reprojected() for a frame drawn through a RayCamera (vrt_reproject_camera): ray_camera_c is the vrt_ray_camera
         block the frame's rays were made with (RayCamera.to_c(resolution, jitter)); the previous frame's is kept here, as
         record_reprojected() keeps the previous push.  One stage records through one of the two: their histories are the same
         buffers.  reprojectSettings.tolRel None is the camera model's default."""
-        torch = _torch()
         H, W = color.shape[0], color.shape[1]
-        TW, TH = self._settings.targetResolution
-        if self._hist is None or self._hist[0][0].shape[:2] != (H, W) or self._resolved is None or self._resolved.shape[:2] != (H, W):
-            self._hist = [(torch.zeros((H, W, 4), dtype=torch.int16, device=color.device),
-                           torch.zeros((H, W, 4), dtype=torch.int32, device=color.device)) for _ in range(2)]
-            self._resolved = torch.zeros((H, W, 4), dtype=torch.uint8, device=color.device)
-            self._accum = None
-            self._hist_cur = -1
-        if self._target is None or self._target.shape[:2] != (TH, TW):
-            self._target = torch.zeros((TH, TW, 4), dtype=torch.uint8, device=color.device)
+        self._ensure_reprojected(H, W, color.device)
         if self._hist_cur >= 0 and (self._prev_camera is None or self._prev_camera.model != ray_camera_c.model):
             self._hist_cur = -1                                    # another camera model: a new sequence
-        prev = self._prev_camera if self._hist_cur >= 0 else ray_camera_c
-        nxt = 1 - self._hist_cur if self._hist_cur >= 0 else 0
-        hin = _capi.History(self._hist[self._hist_cur][0].data_ptr(), self._hist[self._hist_cur][1].data_ptr()) if self._hist_cur >= 0 else None
-        hout = _capi.History(self._hist[nxt][0].data_ptr(), self._hist[nxt][1].data_ptr())
+        hin, hout = self.next_histories()
         st = _capi.ReprojectSettings()
         lib().vrt_reproject_camera_settings_default(C.byref(ray_camera_c), W, C.byref(st))
-        st.max_history, st.tol_abs = int(self.reprojectSettings.maxHistory), float(self.reprojectSettings.tolAbs)
-        if self.reprojectSettings.tolRel is not None:
-            st.tol_rel = float(self.reprojectSettings.tolRel)
+        self.reprojectSettings.over(st)
         motion = gbuffer.planes.get("motion")
-        check(lib().vrt_reproject_camera(self.engine.ctx, W, H, C.byref(ray_camera_c), C.byref(prev), C.byref(st), color.data_ptr(),
-                                         gbuffer.position.data_ptr(), gbuffer.normal.data_ptr(), C.byref(hin) if hin is not None else None,
+        check(lib().vrt_reproject_camera(self.engine.ctx, W, H, C.byref(ray_camera_c), C.byref(self._prev_camera if hin is not None else ray_camera_c),
+                                         C.byref(st), color.data_ptr(), gbuffer.position.data_ptr(), gbuffer.normal.data_ptr(), _ref(hin),
                                          C.byref(hout), self._resolved.data_ptr(), motion.data_ptr() if motion is not None else None))
-        self._hist_cur = nxt
-        self._prev_camera = _capi.RayCamera.from_buffer_copy(ray_camera_c)
-        self.accumulated += 1
-        check(lib().vrt_blit(self.engine.ctx, self._resolved.data_ptr(), W, H, self._target.data_ptr(), TW, TH))
-        return self._target
+        self._commit("_prev_camera", ray_camera_c)
+        return self._upscaled(W, H)
 
     def record_upsampled(self, color, gbuffer: "GeometryBuffer", push: _capi.Push):
         """The temporal pass at display resolution (vrt_upsample): `color` (normally the denoised image, at render resolution)
@@ -1004,28 +1031,17 @@ class UpscalerStage:
         display pixel's surface was under the previous frame's camera.  The motion vectors, in display pixels, go into
         self.motion; gbuffer.motion is not touched.  reset() starts a new sequence.  Returns the resolved image at
         targetResolution -- there is no blit."""
-        torch = _torch()
         H, W = color.shape[0], color.shape[1]
         TW, TH = self._settings.targetResolution
-        if self._hist is None or self._hist[0][0].shape[:2] != (TH, TW):
-            self._hist = [(torch.zeros((TH, TW, 4), dtype=torch.int16, device=color.device),
-                           torch.zeros((TH, TW, 4), dtype=torch.int32, device=color.device)) for _ in range(2)]
-            self._hist_cur = -1
-        if self._target is None or self._target.shape[:2] != (TH, TW):
-            self._target = torch.zeros((TH, TW, 4), dtype=torch.uint8, device=color.device)
-        if self.motion is None or self.motion.shape[:2] != (TH, TW):
-            self.motion = torch.zeros((TH, TW, 2), dtype=torch.float32, device=color.device)
-        prev = self._prev_push if self._hist_cur >= 0 else push
-        nxt = 1 - self._hist_cur if self._hist_cur >= 0 else 0
-        hin = _capi.History(self._hist[self._hist_cur][0].data_ptr(), self._hist[self._hist_cur][1].data_ptr()) if self._hist_cur >= 0 else None
-        hout = _capi.History(self._hist[nxt][0].data_ptr(), self._hist[nxt][1].data_ptr())
+        self._ensure_histories(TH, TW, color.device)
+        self._ensure_target(color.device)
+        self.motion = _ensure(self.motion, (TH, TW, 2), "float32", color.device)
+        hin, hout = self.next_histories()
         st = self.reprojectSettings.to_c(push)
-        check(lib().vrt_upsample(self.engine.ctx, W, H, TW, TH, C.byref(push), C.byref(prev), C.byref(st), color.data_ptr(),
-                                 gbuffer.position.data_ptr(), gbuffer.normal.data_ptr(), C.byref(hin) if hin is not None else None,
-                                 C.byref(hout), self._target.data_ptr(), self.motion.data_ptr()))
-        self._hist_cur = nxt
-        self._prev_push = _capi.Push.from_buffer_copy(push)
-        self.accumulated += 1
+        check(lib().vrt_upsample(self.engine.ctx, W, H, TW, TH, C.byref(push), C.byref(self._prev_push if hin is not None else push), C.byref(st),
+                                 color.data_ptr(), gbuffer.position.data_ptr(), gbuffer.normal.data_ptr(), _ref(hin), C.byref(hout),
+                                 self._target.data_ptr(), self.motion.data_ptr()))
+        self._commit("_prev_push", push)
         return self._target
 
     def history(self):
@@ -1036,20 +1052,16 @@ class UpscalerStage:
         return c.cpu().numpy().view(np.uint16), s.cpu().numpy().view(np.uint32)
 
     def record(self, color):
-        torch = _torch()
         H, W = color.shape[0], color.shape[1]
-        TW, TH = self._settings.targetResolution
         if self._accum is None or self._accum.shape[:2] != (H, W) or self._resolved.shape[:2] != (H, W):
-            self._accum = torch.zeros((H, W, 4), dtype=torch.int32, device=color.device)
-            self._resolved = torch.zeros((H, W, 4), dtype=torch.uint8, device=color.device)
+            self._accum = _zeros((H, W, 4), "int32", color.device)
+            self._resolved = _zeros((H, W, 4), "uint8", color.device)
             self.accumulated = 0
-        if self._target is None or self._target.shape[:2] != (TH, TW):
-            self._target = torch.zeros((TH, TW, 4), dtype=torch.uint8, device=color.device)
+        self._ensure_target(color.device)
         check(lib().vrt_accumulate(self.engine.ctx, color.data_ptr(), self._accum.data_ptr(), W, H, 1 if self.accumulated == 0 else 0))
         self.accumulated += 1
         check(lib().vrt_resolve(self.engine.ctx, self._accum.data_ptr(), self._resolved.data_ptr(), W, H, self.accumulated))
-        check(lib().vrt_blit(self.engine.ctx, self._resolved.data_ptr(), W, H, self._target.data_ptr(), TW, TH))
-        return self._target
+        return self._upscaled(W, H)
 
 
 class BlitStage:
@@ -1061,10 +1073,8 @@ class BlitStage:
         self._target = None
 
     def record(self, source, windowSize):
-        torch = _torch()
         TW, TH = int(windowSize[0]), int(windowSize[1])
-        if self._target is None or self._target.shape[:2] != (TH, TW):
-            self._target = torch.zeros((TH, TW, 4), dtype=torch.uint8, device=source.device)
+        self._target = _ensure(self._target, (TH, TW, 4), "uint8", source.device)
         check(lib().vrt_blit(self.engine.ctx, source.data_ptr(), source.shape[1], source.shape[0],
                              self._target.data_ptr(), TW, TH))
         return self._target

@@ -322,77 +322,41 @@ public:
     vrt_reproject_settings reprojectSettings{0, 0.5f, -1.0f};                          // max_history 0 / tol_rel < 0: the default
     const uint8_t* recordReprojected(const uint8_t* color, const GeometryBuffer& g, const vrt_push& push)
     {
-        const uint32_t w = g.width, h = g.height;
-        size_t n = (size_t)w * h;
-        if (!histColor[0] || histColor[0]->count != n * 4) {
-            for (int k = 0; k < 2; k++) { histColor[k] = std::make_shared<DeviceBuffer<uint16_t>>(engine, n * 4); histSurface[k] = std::make_shared<DeviceBuffer<uint32_t>>(engine, n * 4); }
-            histCur = -1;
-        }
-        if (!resolved || resolved->count != n * 4) { resolved = std::make_shared<DeviceBuffer<uint8_t>>(engine, n * 4); accum.reset(); }
-        size_t tn = (size_t)settings->targetResolution[0] * settings->targetResolution[1] * 4;
-        if (!target || target->count != tn) target = std::make_shared<DeviceBuffer<uint8_t>>(engine, tn);
-        vrt_reproject_settings st; vrt_reproject_settings_default(&push, &st);
-        if (reprojectSettings.max_history != 0) st.max_history = reprojectSettings.max_history;
-        st.tol_abs = reprojectSettings.tol_abs;
-        if (reprojectSettings.tol_rel >= 0) st.tol_rel = reprojectSettings.tol_rel;
-        const int nxt = histCur >= 0 ? 1 - histCur : 0;
-        vrt_history in{}, out{histColor[nxt]->ptr, histSurface[nxt]->ptr};
-        if (histCur >= 0) { in.color16 = histColor[histCur]->ptr; in.surface = histSurface[histCur]->ptr; }
-        check(vrt_reproject(engine->ctx, (int32_t)w, (int32_t)h, &push, histCur >= 0 ? &prevPush : &push, &st, color, g.position->ptr, g.normal->ptr,
-                            histCur >= 0 ? &in : nullptr, &out, resolved->ptr, g.motion->ptr));
-        histCur = nxt; prevPush = push; accumulated++;
-        check(vrt_blit(engine->ctx, resolved->ptr, (int32_t)w, (int32_t)h, target->ptr, (int32_t)settings->targetResolution[0], (int32_t)settings->targetResolution[1]));
-        return target->ptr;
+        ensureReprojected(g);
+        vrt_reproject_settings st; vrt_reproject_settings_default(&push, &st); overrideSettings(st);
+        vrt_history in{}, out{}; const bool running = nextHistories(in, out);
+        check(vrt_reproject(engine->ctx, (int32_t)g.width, (int32_t)g.height, &push, running ? &prevPush : &push, &st, color, g.position->ptr, g.normal->ptr,
+                            running ? &in : nullptr, &out, resolved->ptr, g.motion->ptr));
+        commit(); prevPush = push;
+        return upscaled(g.width, g.height);
     }
     // recordReprojected() for a frame drawn through a vrt_ray_camera (vrt_reproject_camera): cam is the block the frame's rays were
     // made with; the previous frame's is kept here.  The histories are recordReprojected()'s buffers.
     const uint8_t* recordReprojectedCamera(const uint8_t* color, const GeometryBuffer& g, const vrt_ray_camera& cam)
     {
-        const uint32_t w = g.width, h = g.height;
-        size_t n = (size_t)w * h;
-        if (!histColor[0] || histColor[0]->count != n * 4) {
-            for (int k = 0; k < 2; k++) { histColor[k] = std::make_shared<DeviceBuffer<uint16_t>>(engine, n * 4); histSurface[k] = std::make_shared<DeviceBuffer<uint32_t>>(engine, n * 4); }
-            histCur = -1;
-        }
-        if (!resolved || resolved->count != n * 4) { resolved = std::make_shared<DeviceBuffer<uint8_t>>(engine, n * 4); accum.reset(); }
-        size_t tn = (size_t)settings->targetResolution[0] * settings->targetResolution[1] * 4;
-        if (!target || target->count != tn) target = std::make_shared<DeviceBuffer<uint8_t>>(engine, tn);
+        ensureReprojected(g);
         if (histCur >= 0 && prevCamera.model != cam.model) histCur = -1;               // another camera model: a new sequence
-        vrt_reproject_settings st; vrt_reproject_camera_settings_default(&cam, (int32_t)w, &st);
-        if (reprojectSettings.max_history != 0) st.max_history = reprojectSettings.max_history;
-        st.tol_abs = reprojectSettings.tol_abs;
-        if (reprojectSettings.tol_rel >= 0) st.tol_rel = reprojectSettings.tol_rel;
-        const int nxt = histCur >= 0 ? 1 - histCur : 0;
-        vrt_history in{}, out{histColor[nxt]->ptr, histSurface[nxt]->ptr};
-        if (histCur >= 0) { in.color16 = histColor[histCur]->ptr; in.surface = histSurface[histCur]->ptr; }
-        check(vrt_reproject_camera(engine->ctx, (int32_t)w, (int32_t)h, &cam, histCur >= 0 ? &prevCamera : &cam, &st, color, g.position->ptr, g.normal->ptr,
-                                   histCur >= 0 ? &in : nullptr, &out, resolved->ptr, g.motion->ptr));
-        histCur = nxt; prevCamera = cam; accumulated++;
-        check(vrt_blit(engine->ctx, resolved->ptr, (int32_t)w, (int32_t)h, target->ptr, (int32_t)settings->targetResolution[0], (int32_t)settings->targetResolution[1]));
-        return target->ptr;
+        vrt_reproject_settings st; vrt_reproject_camera_settings_default(&cam, (int32_t)g.width, &st); overrideSettings(st);
+        vrt_history in{}, out{}; const bool running = nextHistories(in, out);
+        check(vrt_reproject_camera(engine->ctx, (int32_t)g.width, (int32_t)g.height, &cam, running ? &prevCamera : &cam, &st, color, g.position->ptr, g.normal->ptr,
+                                   running ? &in : nullptr, &out, resolved->ptr, g.motion->ptr));
+        commit(); prevCamera = cam;
+        return upscaled(g.width, g.height);
     }
     // The temporal pass at display resolution (vrt_upsample): the history pair, the resolved image and the motion vectors
     // (motion(), in display pixels; g.motion is not touched) live at targetResolution, every sample where it fell on the display grid.
     const uint8_t* recordUpsampled(const uint8_t* color, const GeometryBuffer& g, const vrt_push& push)
     {
-        const uint32_t w = g.width, h = g.height, tw = settings->targetResolution[0], th = settings->targetResolution[1];
-        size_t tn = (size_t)tw * th;
-        if (!histColor[0] || histColor[0]->count != tn * 4) {
-            for (int k = 0; k < 2; k++) { histColor[k] = std::make_shared<DeviceBuffer<uint16_t>>(engine, tn * 4); histSurface[k] = std::make_shared<DeviceBuffer<uint32_t>>(engine, tn * 4); }
-            histCur = -1;
-        }
-        if (!target || target->count != tn * 4) target = std::make_shared<DeviceBuffer<uint8_t>>(engine, tn * 4);
+        const uint32_t tw = settings->targetResolution[0], th = settings->targetResolution[1];
+        const size_t tn = (size_t)tw * th;
+        ensureHistories(tn);
+        ensureTarget();
         if (!displayMotion || displayMotion->count != tn * 2) displayMotion = std::make_shared<DeviceBuffer<float>>(engine, tn * 2);
-        vrt_reproject_settings st; vrt_reproject_settings_default(&push, &st);
-        if (reprojectSettings.max_history != 0) st.max_history = reprojectSettings.max_history;
-        st.tol_abs = reprojectSettings.tol_abs;
-        if (reprojectSettings.tol_rel >= 0) st.tol_rel = reprojectSettings.tol_rel;
-        const int nxt = histCur >= 0 ? 1 - histCur : 0;
-        vrt_history in{}, out{histColor[nxt]->ptr, histSurface[nxt]->ptr};
-        if (histCur >= 0) { in.color16 = histColor[histCur]->ptr; in.surface = histSurface[histCur]->ptr; }
-        check(vrt_upsample(engine->ctx, (int32_t)w, (int32_t)h, (int32_t)tw, (int32_t)th, &push, histCur >= 0 ? &prevPush : &push, &st, color,
-                           g.position->ptr, g.normal->ptr, histCur >= 0 ? &in : nullptr, &out, target->ptr, displayMotion->ptr));
-        histCur = nxt; prevPush = push; accumulated++;
+        vrt_reproject_settings st; vrt_reproject_settings_default(&push, &st); overrideSettings(st);
+        vrt_history in{}, out{}; const bool running = nextHistories(in, out);
+        check(vrt_upsample(engine->ctx, (int32_t)g.width, (int32_t)g.height, (int32_t)tw, (int32_t)th, &push, running ? &prevPush : &push, &st, color,
+                           g.position->ptr, g.normal->ptr, running ? &in : nullptr, &out, target->ptr, displayMotion->ptr));
+        commit(); prevPush = push;
         return target->ptr;
     }
     const float* motion() const { return displayMotion ? displayMotion->ptr : nullptr; }
@@ -400,15 +364,47 @@ public:
     {
         size_t n = (size_t)w * h * 4;
         if (!accum || accum->count != n || !resolved || resolved->count != n) { accum = std::make_shared<DeviceBuffer<uint32_t>>(engine, n); resolved = std::make_shared<DeviceBuffer<uint8_t>>(engine, n); accumulated = 0; }
-        size_t tn = (size_t)settings->targetResolution[0] * settings->targetResolution[1] * 4;
-        if (!target || target->count != tn) target = std::make_shared<DeviceBuffer<uint8_t>>(engine, tn);
+        ensureTarget();
         check(vrt_accumulate(engine->ctx, color, accum->ptr, (int32_t)w, (int32_t)h, accumulated == 0));
         accumulated++;
         check(vrt_resolve(engine->ctx, accum->ptr, resolved->ptr, (int32_t)w, (int32_t)h, accumulated));
+        return upscaled(w, h);
+    }
+private:
+    // -- what the temporal passes share: the ring of two histories written in turn, the settings, the images
+    void ensureHistories(size_t n)                                                      // n texels each; another size starts a new sequence
+    {
+        if (histColor[0] && histColor[0]->count == n * 4) return;
+        for (int k = 0; k < 2; k++) { histColor[k] = std::make_shared<DeviceBuffer<uint16_t>>(engine, n * 4); histSurface[k] = std::make_shared<DeviceBuffer<uint32_t>>(engine, n * 4); }
+        histCur = -1;
+    }
+    bool nextHistories(vrt_history& in, vrt_history& out) const                         // what the next call reads and writes; false: no history in
+    {
+        const int nxt = histCur >= 0 ? 1 - histCur : 0;
+        out = {histColor[nxt]->ptr, histSurface[nxt]->ptr};
+        if (histCur >= 0) in = {histColor[histCur]->ptr, histSurface[histCur]->ptr};
+        return histCur >= 0;
+    }
+    void commit() { histCur = histCur >= 0 ? 1 - histCur : 0; accumulated++; }         // the call wrote `out`
+    void overrideSettings(vrt_reproject_settings& st) const                            // a camera's defaults under reprojectSettings
+    {
+        if (reprojectSettings.max_history != 0) st.max_history = reprojectSettings.max_history;
+        st.tol_abs = reprojectSettings.tol_abs;
+        if (reprojectSettings.tol_rel >= 0) st.tol_rel = reprojectSettings.tol_rel;
+    }
+    void ensureTarget() { size_t tn = (size_t)settings->targetResolution[0] * settings->targetResolution[1] * 4; if (!target || target->count != tn) target = std::make_shared<DeviceBuffer<uint8_t>>(engine, tn); }
+    void ensureReprojected(const GeometryBuffer& g)                                     // histories and the resolved image at render size
+    {
+        const size_t n = (size_t)g.width * g.height;
+        ensureHistories(n);
+        if (!resolved || resolved->count != n * 4) { resolved = std::make_shared<DeviceBuffer<uint8_t>>(engine, n * 4); accum.reset(); }
+        ensureTarget();
+    }
+    const uint8_t* upscaled(uint32_t w, uint32_t h)                                     // the resolved image through the bilinear blit
+    {
         check(vrt_blit(engine->ctx, resolved->ptr, (int32_t)w, (int32_t)h, target->ptr, (int32_t)settings->targetResolution[0], (int32_t)settings->targetResolution[1]));
         return target->ptr;
     }
-private:
     std::shared_ptr<Engine> engine; std::shared_ptr<VoxelRenderSettings> settings; float _deltaMsec = 0;
     std::shared_ptr<DeviceBuffer<uint32_t>> accum; std::shared_ptr<DeviceBuffer<uint8_t>> resolved, target;
     std::shared_ptr<DeviceBuffer<uint16_t>> histColor[2]; std::shared_ptr<DeviceBuffer<uint32_t>> histSurface[2]; int histCur = -1; vrt_push prevPush{}; vrt_ray_camera prevCamera{};

@@ -154,7 +154,9 @@ int  vrt_ctx_synchronize(vrt_ctx* ctx);                     /* device.waitIdle()
  *                                     "no_bounce_kernel" (1), "ao_batch" (1: the AO rays of a wave from a pool in LDS every lane draws on),
  *                                     "packed_bounces" (1: the bounce chain as one word per hit on dense scenes; 2: on brick scenes too,
  *                                     where it measured slower; 0: the stack of hits), "tags_async" (0: the tile tags of a launch on a
- *                                     stream of their own measured slower),
+ *                                     stream of their own measured slower; 1: on that stream while the context's stream is busy with
+ *                                     the launch before, which the library asks the runtime at every launch; 2: on that stream always,
+ *                                     busy or not -- the value the tests use, because it does not depend on timing),
  *                                     "xcd_regions" (0 -- until round 3 VRT_XCD_REGIONS was on by default; as a three-dimensional grid the
  *                                     form ran 30.0 or 33.6 us per bench frame from one process to the next, so it is opt-in now)
  *   vrt_denoise:                      "denoise_packed" (1), "denoise_verified" (1), "denoise_pair" (1: verified passes of the canonical taps
@@ -482,7 +484,9 @@ int  vrt_pack_rows(vrt_ctx* ctx, const void* full, void* packed, int32_t W, int3
 int  vrt_unpack_rows(vrt_ctx* ctx, const void* packed, void* full, int32_t W, int32_t H,
                      int32_t bytes_per_px, const vrt_shard* shard);
 /* The same for n images in one launch per 64 images (host arrays of n device pointers): the frames of a batch on a
- * rank (one shard for all), and at the root of the gather frames x source ranks (shards[n], one per image). */
+ * rank (one shard for all), and at the root of the gather frames x source ranks (shards[n], one per image).  The shards of
+ * a call may differ in every field (images whose packed buffers differ in rows take launches of their own).  A NULL image
+ * pointer or a bad shard anywhere in the arrays: VRT_ERR_INVALID before anything is copied. */
 int  vrt_pack_rows_batch(vrt_ctx* ctx, int32_t n, const void* const* full, void* const* packed, int32_t W, int32_t H,
                          int32_t bytes_per_px, const vrt_shard* shard);
 int  vrt_unpack_rows_batch(vrt_ctx* ctx, int32_t n, const void* const* packed, void* const* full, int32_t W, int32_t H,

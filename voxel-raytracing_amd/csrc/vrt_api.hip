@@ -571,8 +571,9 @@ static int launch_tags(vrt_ctx* c, const vrt_scene* s, const Launch& l, const Fr
     // The tags depend on the cameras alone, not on anything the context's stream is still computing: while that stream is
     // busy (the caller runs ahead of the device: a frame loop, a batch loop) they are made on a stream of their own, under
     // the previous launch's tail, and the launch waits for an event instead of a kernel; on an idle device the second
-    // stream would only add the event's latency.  (context option tags_async = 0: always on the context's stream)
-    const bool async = c->opt.tags_async != 0 && hipStreamQuery(c->stream) == hipErrorNotReady;
+    // stream would only add the event's latency.  (context option tags_async = 0: always on the context's stream; 2: always on
+    // the second stream, busy or not -- the tests' handle on this path, which a query of the stream makes a matter of timing)
+    const bool async = c->opt.tags_async >= 2 || (c->opt.tags_async != 0 && hipStreamQuery(c->stream) == hipErrorNotReady);
     if (!async) {
         HIPCHK(launch_tile_tags(p, c->stream));
         return VRT_OK;
@@ -583,6 +584,10 @@ static int launch_tags(vrt_ctx* c, const vrt_scene* s, const Launch& l, const Fr
             HIPCHK(hipEventCreateWithFlags(&c->tag_done[q], hipEventDisableTiming));
             HIPCHK(hipEventCreateWithFlags(&c->tag_read[q], hipEventDisableTiming));
         }
+        // The launches before this one recorded no tag_read (there was no second stream to wait for it), and one of them may
+        // still be reading the buffer this launch fills: the new stream starts behind everything the context's stream holds.
+        HIPCHK(hipEventRecord(c->tag_read[b], c->stream));
+        HIPCHK(hipStreamWaitEvent(c->tag_stream, c->tag_read[b], 0));
     }
     if (c->tag_read_valid[b]) HIPCHK(hipStreamWaitEvent(c->tag_stream, c->tag_read[b], 0));     // the launch that last read this buffer
     if (tab >= 0) HIPCHK(hipStreamWaitEvent(c->tag_stream, c->tab_uploaded[tab], 0));            // the slots the tag kernel reads

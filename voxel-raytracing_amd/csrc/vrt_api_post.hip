@@ -201,24 +201,35 @@ static int rows_batch_call(vrt_ctx* c, int n, const void* const* src, void* cons
 {
     if (!c || !src || !dst) return fail(VRT_ERR_INVALID, "strip copy (batch): NULL argument");
     if (n < 0 || W <= 0 || H <= 0 || bpp <= 0) return fail(VRT_ERR_INVALID, "strip copy (batch): bad size");
+    // every argument of every image before the first launch: a refused call has copied nothing
+    for (int i = 0; i < n; i++) {
+        if (!src[i] || !dst[i]) return fail(VRT_ERR_INVALID, "strip copy (batch): NULL image pointer");
+        ShardMap sm;
+        int rc = make_shard(per_image ? &shards[i] : shards, H, sm, nullptr);
+        if (rc != VRT_OK) return rc;
+        if (halo > sm.strip_rows) return fail(VRT_ERR_INVALID, "strip copy (batch): halo larger than strip_rows");
+    }
     HIPCHK(hipSetDevice(c->device));
-    for (int i0 = 0; i0 < n; i0 += VRT_ROWS_BATCH) {
-        const int m = n - i0 < VRT_ROWS_BATCH ? n - i0 : VRT_ROWS_BATCH;
+    for (int i0 = 0; i0 < n;) {
         RowsBatchParams p;
         memset(&p, 0, sizeof p);
         p.W = W; p.H = H; p.bpp = bpp; p.unpack = unpack; p.halo = halo; p.dir = dir;
-        int rows = 0;
-        for (int k = 0; k < m; k++) {
-            if (!src[i0 + k] || !dst[i0 + k]) return fail(VRT_ERR_INVALID, "strip copy (batch): NULL image pointer");
+        // A launch has one grid height, and a packing launch zero-fills the rows of an image that its strips do not reach: images
+        // whose packed buffers differ in rows (another nranks or strip_rows) go into launches of their own, or the shorter
+        // buffer would be written past its end.
+        int rows = 0, m = 0;
+        for (; m < VRT_ROWS_BATCH && i0 + m < n; m++) {
+            ShardMap sm;
             int mx = 1;
-            int rc = make_shard(per_image ? &shards[i0 + k] : shards, H, p.sh[k], &mx);
+            int rc = make_shard(per_image ? &shards[i0 + m] : shards, H, sm, &mx);
             if (rc != VRT_OK) return rc;
-            p.src[k] = (const uint8_t*)src[i0 + k]; p.dst[k] = (uint8_t*)dst[i0 + k];
-            if (halo > p.sh[k].strip_rows) return fail(VRT_ERR_INVALID, "strip copy (batch): halo larger than strip_rows");
-            int r = halo ? mx * halo : (p.sh[k].nranks == 1 ? H : mx * p.sh[k].strip_rows);
-            rows = r > rows ? r : rows;
+            const int r = halo ? mx * halo : (sm.nranks == 1 ? H : mx * sm.strip_rows);
+            if (m > 0 && r != rows) break;
+            rows = r;
+            p.sh[m] = sm; p.src[m] = (const uint8_t*)src[i0 + m]; p.dst[m] = (uint8_t*)dst[i0 + m];
         }
         HIPCHK(launch_rows_batch(p, rows, m, c->stream));
+        i0 += m;
     }
     return VRT_OK;
 }

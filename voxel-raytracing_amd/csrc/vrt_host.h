@@ -65,7 +65,7 @@ struct DevOptions {
     int fast_loop = 1;         // AUTO / DF through the hand-written look-up loop
     int no_bounce_kernel = 1;  // the megakernel without its bounce loop when nothing can bounce
     int packed_bounces = 1;    // the megakernel's bounce chain as one word per hit (no stack of hits in scratch)
-    int tags_async = 0;        // the tile tags of a launch on a stream of their own while the context's stream is still busy with the launch before
+    int tags_async = 0;        // the tile tags of a launch on a stream of their own while the context's stream is still busy with the launch before (2: always)
                                // (off: measured SLOWER -- one frame per call, 1 / 2 / 3 contexts in flight: 53.8 / 31.0 / 26.9 us per frame with the
                                // tags on the context's stream, 58.5 / 34.1 / 52.2 us on their own; tools/exp_r4_inflight.py)
     int ao_batch = 1;          // the AO rays of a wave from a pool in LDS that every lane draws on (df_ao_pool_loop, brick_ao_pool)

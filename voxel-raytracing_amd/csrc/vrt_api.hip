@@ -546,8 +546,10 @@ static int launch_tags(vrt_ctx* c, const vrt_scene* s, const Launch& l, const Fr
         HIPCHK(hipStreamSynchronize(c->stream));
         if (c->tag_stream) HIPCHK(hipStreamSynchronize(c->tag_stream));
         c->tile_tags[b].reset(); c->tile_tags_words[b] = 0;
-        HIPCHK(c->tile_tags[b].alloc(words * sizeof(uint32_t)));
-        HIPCHK(hipMemsetAsync(c->tile_tags[b].get(), 0, words * sizeof(uint32_t), c->stream));
+        // (three spare words: K1 fetches the four words at a span's first block in one load -- vrt_span.h -- which in the last
+        // frame's last row, or its one word without tags, reaches that far past the end; what they hold is never looked at)
+        HIPCHK(c->tile_tags[b].alloc((words + 3) * sizeof(uint32_t)));
+        HIPCHK(hipMemsetAsync(c->tile_tags[b].get(), 0, (words + 3) * sizeof(uint32_t), c->stream));
         HIPCHK(hipStreamSynchronize(c->stream));
         c->tile_tags_words[b] = words;
         c->tag_read_valid[b] = false;
@@ -556,6 +558,7 @@ static int launch_tags(vrt_ctx* c, const vrt_scene* s, const Launch& l, const Fr
         HIPCHK(hipStreamSynchronize(c->stream));
         if (c->tag_stream) HIPCHK(hipStreamSynchronize(c->tag_stream));
         for (int q = 0; q < 2; q++)
+            // (the three spare words behind them are not cleared: K1 never looks at what they hold)
             if (c->tile_tags[q]) HIPCHK(hipMemsetAsync(c->tile_tags[q].get(), 0, c->tile_tags_words[q] * sizeof(uint32_t), c->stream));
         HIPCHK(hipStreamSynchronize(c->stream));
         c->tile_gen = 1u;

@@ -51,20 +51,32 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 8))) voi
     // (A launch without tags points at one word per frame that holds its tile_gen, with tags_x = 0 and tags_per_frame = 1.)
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const uint32_t tile_gen = P.tile_gen;
-    // (vrt_span.h: with them leave the four tags of the block's 32x8 span -- neighbours in one tag row; the block's own four times
-    // over where the span is cut by the frame's right edge or the launch has no span path, the frame's one word without tags)
-    uint32_t tag, tag_all, st0, st1, st2, st3;
-    bool span_w;
+    // (vrt_span.h: with them leave the four tags of the block's 32x8 span -- neighbours in one tag row.  The primary-only kernels
+    // fetch them with ONE four-word load at the span's first block whatever the launch: a cut span and a launch without tags look
+    // at their own word of the four only.  The megakernels keep the four single loads -- the block's own four times over where
+    // the span is cut or the launch has no span path, the frame's one word without tags: with the short form their packed bounce
+    // chains spill a register more, 168 / 196 B per lane against budgets of 160 / 192, tools/check_resources.py)
+    constexpr bool kOneFetch = MODE == 1;
+    typedef uint32_t span_words __attribute__((ext_vector_type(4), aligned(4)));
+    span_words st;
+    uint32_t tag_all, own, tag = 0u;
+    bool span_w, wide;
     {
         const_u32_ptr tg = (const_u32_ptr)(P.tile_tags + (size_t)frame * P.tags_per_frame);
         const uint32_t tags_x = P.tags_x, sh = (uint32_t)M.tile >> 4;
         const uint32_t row8 = ((uint32_t)ty << sh) + (uint32_t)(wave >> 1), col8 = ((uint32_t)tx << sh) + (uint32_t)(wave & 1);
         span_w = (M.flags & VRT_MAPFLAG_SKY_SPAN) != 0u && span_in_frame(span_x0(col8), (uint32_t)M.W);
-        const uint32_t own = row8 * tags_x + (tags_x ? col8 : 0u);
-        const uint32_t first = (span_w && tags_x) ? own - span_role(col8) : own, step = (span_w && tags_x) ? 1u : 0u;
-        st0 = tg[first]; st1 = tg[first + step]; st2 = tg[first + 2u * step]; st3 = tg[first + 3u * step];
-        const uint32_t k = own - first;                           // (the block's own is one of the four)
-        tag = k == 0u ? st0 : (k == 1u ? st1 : (k == 2u ? st2 : st3));
+        wide = span_w && tags_x != 0u;
+        if (kOneFetch) {
+            own = span_fetch_own(col8, tags_x);
+            st = *(const __attribute__((address_space(4))) span_words*)(tg + span_fetch_first(row8, col8, tags_x));
+        } else {
+            const uint32_t mine = row8 * tags_x + (tags_x ? col8 : 0u);
+            const uint32_t first = wide ? mine - span_role(col8) : mine, step = wide ? 1u : 0u;
+            st.x = tg[first]; st.y = tg[first + step]; st.z = tg[first + 2u * step]; st.w = tg[first + 3u * step];
+            own = mine - first;                                   // (the block's own is one of the four)
+            tag = own == 0u ? st.x : (own == 1u ? st.y : (own == 2u ? st.z : st.w));
+        }
         tag_all = tg[P.tags_per_frame - 1u];
     }
     // ... and so does the frame's part of ray generation (camera, hoisted constants, strip assignment), in one batch
@@ -76,8 +88,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 8))) voi
     asm volatile("" : "+s"(box));
     // (one scalar from here on, not three: past 80 scalar registers a SIMD holds 7 of these waves, not 8)
     // (bit 0: the block has no tag; bit 1: its span may take the span path; bit 2: none of the span's blocks has a tag)
-    const uint32_t untagged = (uint32_t)__builtin_amdgcn_readfirstlane(((tag != tile_gen && tag_all != tile_gen) ? 1 : 0) | (span_w ? 2 : 0) |
-                                                                       (span_untagged(st0, st1, st2, st3, tag_all, tile_gen) ? 4 : 0));
+    uint32_t untagged;
+    if (kOneFetch) untagged = (uint32_t)__builtin_amdgcn_readfirstlane((int)span_verdict(st.x, st.y, st.z, st.w, own, wide, span_w, tag_all, tile_gen));
+    else untagged = (uint32_t)__builtin_amdgcn_readfirstlane(((tag != tile_gen && tag_all != tile_gen) ? 1 : 0) | (span_w ? 2 : 0) |
+                                                             (span_untagged(st.x, st.y, st.z, st.w, tag_all, tile_gen) ? 4 : 0));
     const uint4 boxr = make_uint4(box & 0xFFu, (box >> 8) & 0xFFu, (box >> 16) & 0xFFu, box >> 24);
     float crx = cam_right[0], cry = cam_right[1], crz = cam_right[2];
     float rcp_w = P.rcp_w, rcp_h = P.rcp_h;
@@ -98,7 +112,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 8))) voi
     const int px0 = x0 + (wave & 1) * 8, py0 = y0 + (wave >> 1) * 8;       // the wave's 8x8 block (wave-uniform)
     // where the four blocks of the wave's 32x8 span all are skip blocks (below), the four waves trade pixels: each takes two whole
     // rows of the span (vrt_span.h; every wave of the span reaches this verdict from the same words)
-    const bool span = (untagged & 2u) != 0u && block_skips(box, (uint32_t)px0 & ~31u, (uint32_t)py0, (untagged & 4u) != 0u);
+    // (ONE rectangle test for both questions -- the span's blocks share the 32-pixel column and the row -- and one scalar from
+    // here on: bit 0: the block is a skip block, bit 1: so is every block of its span)
+    uint32_t verdict = 0u;
+    if (kOneFetch) verdict = (uint32_t)__builtin_amdgcn_readfirstlane((int)span_decide(untagged, box, (uint32_t)px0, (uint32_t)py0));
+    const bool span = kOneFetch ? (verdict & 2u) != 0u
+                                : (untagged & 2u) != 0u && block_skips(box, (uint32_t)px0 & ~31u, (uint32_t)py0, (untagged & 4u) != 0u);
     int px, py;
     span_pixel(span, span ? (uint32_t)px0 & ~31u : (uint32_t)px0, (uint32_t)py0, span_role((uint32_t)px0 >> 3), (uint32_t)lane, px, py);
     int W = M.W, H = M.H;
@@ -115,8 +134,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 8))) voi
     // a wave whose 8x8 pixels lie outside the frame's box rectangle (FrameSlot::box, vrt_internal.h box_rect) cannot meet the
     // volume: it writes what a miss writes without testing the box (wave-uniform: the rectangle is in units of 32 pixels) --
     // and inside the rectangle neither can a wave whose block no occupied 4^3 cell of the volume projects onto (k_tile_tags)
-    const bool skip = box != 0xFF00FF00u && ((uint32_t)(px0 >> 5) < boxr.x || (uint32_t)(px0 >> 5) >= boxr.y || (uint32_t)(py0 >> 5) < boxr.z ||
-                                             (uint32_t)(py0 >> 5) >= boxr.w || (untagged & 1u) != 0u);
+    const bool skip = kOneFetch ? (verdict & 1u) != 0u
+                                : box != 0xFF00FF00u && ((uint32_t)(px0 >> 5) < boxr.x || (uint32_t)(px0 >> 5) >= boxr.y || (uint32_t)(py0 >> 5) < boxr.z ||
+                                                         (uint32_t)(py0 >> 5) >= boxr.w || (untagged & 1u) != 0u);
     // ... and of everything normalize(), atan() and asin() compute for such a pixel only the sky TEXEL is ever seen: vrt_sky.h
     // decides it from the unnormalised direction with a bound on its distance to the spec's own coordinate; a wave in which
     // some lane lies within that bound of a texel edge goes the long way round, every other wave stores the miss pixel here
@@ -190,7 +210,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 8))) voi
                            "s"(P.sc.vol.vox));
         start = SlotOf<TABLE>::cam_pos(P, frame);
         dir = primary_normalize(v);
-        trace_ray<TRAV, OccT<kLds>, MODE == 1>(s, occ, start, dir, P.st.max_steps, h, r);   // look-ahead request: primary-only kernel
+        trace_ray<TRAV, OccT<kLds>, MODE == 1, false, MODE == 1>(s, occ, start, dir, P.st.max_steps, h, r);   // look-ahead request: primary-only kernel
     }
     bool hit = h.material != 0;
 

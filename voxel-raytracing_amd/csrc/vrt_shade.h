@@ -81,7 +81,10 @@ __device__ __forceinline__ f3 hit_normal(uint32_t mask, int sx, int sy, int sz)
 }
 
 // traceRay, voxel_volume.frag:176-196
-template <int TRAV, class Occ, bool AHEAD = false, bool PF = false>
+// ONE_AXIS (the primary-only kernels): where every hit of the wave has a one-axis mask and its component lies in the range for
+// which sqrt(RN(x * x)) == |x| (vrt_spec.h one_axis_len_ok), the hit distance is |x| -- the same bits, without the products, the
+// sums and the IEEE square root; any other wave computes len3 as before
+template <int TRAV, class Occ, bool AHEAD = false, bool PF = false, bool ONE_AXIS = false>
 __device__ __forceinline__ void trace_ray(const DevScene& s, const Occ occ, f3 start, f3 dir,
                                           uint32_t maxSteps, RayHit& h, RayInt& r)
 {
@@ -99,7 +102,13 @@ __device__ __forceinline__ void trace_ray(const DevScene& s, const Occ occ, f3 s
         f3 m = mk3((r.mask & 1u) ? (r.side.x - r.delta.x) : 0.0f,
                    (r.mask & 2u) ? (r.side.y - r.delta.y) : 0.0f,
                    (r.mask & 4u) ? (r.side.z - r.delta.z) : 0.0f);
-        float d = len3(m);
+        float d;
+        const float x1 = (r.mask & 1u) ? m.x : ((r.mask & 2u) ? m.y : m.z);
+        if (ONE_AXIS && __ballot(!one_axis_len_ok(r.mask, x1)) == 0ull) d = fabsf(x1);     // (the lanes with a hit vote: wave-uniform)
+        else {
+            if (ONE_AXIS) asm volatile("" : "+v"(m.x));       // (a branch: without this the compiler computes the root for everybody and selects)
+            d = len3(m);
+        }
         pos = mk3(r.pos.x + d * dir.x, r.pos.y + d * dir.y, r.pos.z + d * dir.z);
     }
     h.pos = pos;

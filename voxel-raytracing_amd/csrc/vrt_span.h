@@ -50,6 +50,50 @@ VRT_HD bool span_eligible(uint32_t t0, uint32_t t1, uint32_t t2, uint32_t t3, ui
     return span_in_frame(x0, W) && block_skips(box, x0, py0, span_untagged(t0, t1, t2, t3, tag_all, tile_gen));
 }
 
+// ---- the same rule as k_primary reaches it: one fetch, one compare chain, one rectangle test ----
+// (tests/test_k1_diet_cpu.py, through tests/native/k1_diet_host.cpp, proves that this form and the functions above agree for
+// every tag pattern, box, role and width.)
+//
+// The four tags of a span are neighbours in one tag row, so ONE four-word fetch at the span's first block brings them all: a scalar
+// load needs its address aligned to a word, not to its size, and the row pitch may be anything.  Where the span is cut by the
+// frame's right edge the words past the row's end belong to the next row (after the last row: to the frame's "the tags say
+// nothing" word, the next frame, or the three spare words the host allocates behind the last frame); in a launch without tags
+// (tags_x = 0, one word per frame) words 1 - 3 are other frames'.  Neither is looked at: `wide` says whether all four words are
+// this span's blocks, otherwise only the block's own counts.
+
+// the word offset of the fetch within the frame's tags
+VRT_HD uint32_t span_fetch_first(uint32_t row8, uint32_t col8, uint32_t tags_x) { return tags_x ? row8 * tags_x + (col8 & ~3u) : 0u; }
+// which of the four fetched words is the block's own
+VRT_HD uint32_t span_fetch_own(uint32_t col8, uint32_t tags_x) { return tags_x ? span_role(col8) : 0u; }
+
+// bit 0: the block has no tag; bit 1: its span may take the span path (span_w: the launch has the path and the span lies inside
+// the frame's width); bit 2: none of the span's blocks has a tag.  own: span_fetch_own; wide = span_w && tags_x != 0.
+VRT_HD uint32_t span_verdict(uint32_t w0, uint32_t w1, uint32_t w2, uint32_t w3, uint32_t own, bool wide, bool span_w, uint32_t tag_all,
+                             uint32_t tile_gen)
+{
+    const uint32_t hits = (w0 == tile_gen ? 1u : 0u) | (w1 == tile_gen ? 2u : 0u) | (w2 == tile_gen ? 4u : 0u) | (w3 == tile_gen ? 8u : 0u);
+    const uint32_t mine = 1u << own, seen = wide ? 15u : mine;
+    const uint32_t v = ((hits & mine) ? 0u : 1u) | ((hits & seen) ? 0u : 4u);
+    return (tag_all == tile_gen ? 0u : v) | (span_w ? 2u : 0u);
+}
+
+// the block at (px0, py0) lies outside the frame's box rectangle (the same answer for the four blocks of a span: the rectangle is
+// in units of 32 pixels)
+VRT_HD bool block_outside(uint32_t box, uint32_t px0, uint32_t py0)
+{
+    const uint32_t bx = px0 >> 5, by = py0 >> 5;
+    // (bitwise: four compares and three ORs on the scalar unit, no branch)
+    return (bool)((int)(bx < (box & 0xFFu)) | (int)(bx >= ((box >> 8) & 0xFFu)) | (int)(by < ((box >> 16) & 0xFFu)) | (int)(by >= (box >> 24)));
+}
+
+// What the wave does, from span_verdict's bits: bit 0: the block is a skip block (block_skips); bit 1: the span is eligible
+// (span_eligible).  Outside the rectangle nobody has a tag that counts; without a rectangle nothing is known.
+VRT_HD uint32_t span_decide(uint32_t verdict, uint32_t box, uint32_t px0, uint32_t py0)
+{
+    const uint32_t u = (verdict | (block_outside(box, px0, py0) ? 5u : 0u)) & (box != 0xFF00FF00u ? 7u : 0u);
+    return (u & 1u) | ((u & 6u) == 6u ? 2u : 0u);
+}
+
 // lane -> pixel.  span: role k of the span at (x0, py0) owns its rows 2k and 2k + 1; otherwise the 8x8 block at (x0, py0).
 // (the terms in front of the lane's are wave-uniform: the choice costs no vector instruction)
 VRT_HD void span_pixel(bool span, uint32_t x0, uint32_t py0, uint32_t role, uint32_t lane, int& px, int& py)

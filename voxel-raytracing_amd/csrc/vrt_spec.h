@@ -35,6 +35,21 @@ VRT_HD float div_spec(float x, float y) { return x / y; }
 
 VRT_HD float len3(f3 a) { return sqrt_spec(dot3(a, a)); }
 
+// len3 of a vector with ONE non-zero component x is sqrt_spec(RN(x * x) + 0 + 0), and in IEEE binary32 with round-to-nearest
+// sqrt(RN(x * x)) == |x| whenever x * x neither overflows nor leaves the normal range (the square of a p-bit number has its
+// root within half an ulp of |x|, and |x| is representable).  The range below keeps x * x in [2^-120, 2^120], well inside
+// [2^-126, 2^128); tests/test_k1_diet_cpu.py checks the identity for every mantissa at both ends and at a sample of exponents
+// in between, and shows that it fails below the range (x = 0x1.fffffep-70: x * x is subnormal and loses bits) and above it (x = 0x1p64: x * x is infinite).
+// mask: the DDA's axis mask of the hit (bit a: the ray entered through a face of axis a); x: the component of its one set bit.
+#define VRT_ONE_AXIS_MIN 0x1p-60f
+#define VRT_ONE_AXIS_MAX 0x1p60f
+VRT_HD bool one_axis_len_ok(uint32_t mask, float x)
+{
+    const uint32_t m = mask & 7u;
+    const float ax = fabsf(x);
+    return m != 0u && (m & (m - 1u)) == 0u && ax >= VRT_ONE_AXIS_MIN && ax <= VRT_ONE_AXIS_MAX;     // (a NaN answers no)
+}
+
 // GLSL normalize(); normalize(0) := 0 (canonical rule A).
 VRT_HD f3 normalize3(f3 a)
 {

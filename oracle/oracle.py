@@ -1,7 +1,8 @@
 """ctypes wrapper of the CPU ORACLE (oracle/libvrt_oracle.so) -- TEST INFRASTRUCTURE ONLY.
 
 Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may import this module.
-PARITY UNPINNED (see vrt_oracle.h): the reference ships no golden vectors for this path.
+Parity: structure and operand order are pinned by the reference's own shaders compiled as C++ (refshader() below,
+oracle/ref_shader/, tests/test_ref_shader_cpu.py); the numeric choices GLSL leaves open are DESIGN.md section 3.
 """
 import ctypes as C
 import os
@@ -12,6 +13,7 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libvrt_oracle.so")
 REFVOX_PATH = os.path.join(_HERE, "_ref", "libvrt_refvox.so")
+REFSHADER_PATH = os.path.join(_HERE, "_ref", "libvrt_refshader.so")
 
 
 class Push(C.Structure):
@@ -90,6 +92,11 @@ def lib():
                                  C.c_float, C.c_float, C.c_float, C.c_float, C.c_int]
         l.vo_blit.restype = None
         l.vo_blit.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int]
+        l.vo_denoise_pass_f.restype = None
+        l.vo_denoise_pass_f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                        C.POINTER(DenoiseParams), C.c_int]
+        l.vo_blit_f.restype = None
+        l.vo_blit_f.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int]
         l.vo_jitter_phase_count.restype = C.c_int; l.vo_jitter_phase_count.argtypes = [C.c_int, C.c_int]
         l.vo_jitter_offset.restype = None
         l.vo_jitter_offset.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float)]
@@ -102,6 +109,44 @@ def blit(src, tw, th):
     dst = np.zeros((th, tw, 4), np.uint8)
     lib().vo_blit(src.ctypes.data, src.shape[1], src.shape[0], dst.ctypes.data, tw, th)
     return dst
+
+
+def blit_f(src, tw, th):
+    """outColor of the blit as floats, before the store to the RGBA8 target."""
+    src = np.ascontiguousarray(src, np.uint8)
+    dst = np.zeros((th, tw, 4), np.float32)
+    lib().vo_blit_f(src.ctypes.data, src.shape[1], src.shape[0], dst.ctypes.data, tw, th)
+    return dst
+
+
+def denoise_pass_params(i, phi_color0=20.4, phi_normal0=1e-2, phi_pos0=1e-1, step_width0=2.0) -> DenoiseParams:
+    p = DenoiseParams()
+    lib().vo_denoise_pass_params(int(i), phi_color0, phi_normal0, phi_pos0, step_width0, C.byref(p))
+    return p
+
+
+def denoise_pass_f(color8, normal8, position, params: DenoiseParams, mode=0):
+    """One denoiser pass, outColor as floats (H, W, 4) before the store to the RGBA8 target."""
+    color8 = np.ascontiguousarray(color8, np.uint8); normal8 = np.ascontiguousarray(normal8, np.int8)
+    position = np.ascontiguousarray(position, np.float32)
+    H, W = color8.shape[:2]
+    out = np.zeros((H, W, 4), np.float32)
+    lib().vo_denoise_pass_f(color8.ctypes.data, normal8.ctypes.data, position.ctypes.data, out.ctypes.data, W, H,
+                            C.byref(params), int(mode))
+    return out
+
+
+def unorm8(x):
+    """vo_unorm8 over an array (the same fp32 operations: clamp with fmin/fmax so that NaN -> 0, scale, round half up)."""
+    x = np.asarray(x, np.float32)
+    c = np.fmin(np.fmax(x, np.float32(0)), np.float32(1))
+    return np.floor(c * np.float32(255) + np.float32(0.5)).astype(np.uint8)
+
+
+def snorm8(x):
+    x = np.asarray(x, np.float32)
+    c = np.fmin(np.fmax(x, np.float32(-1)), np.float32(1))
+    return np.floor(c * np.float32(127) + np.float32(0.5)).astype(np.int8)
 
 
 def jitter(index, render_width, display_width):
@@ -293,3 +338,88 @@ def refvox_write(models, groups, instances, palette_rgba8, metal=None) -> bytes:
     data = C.string_at(out, n.value)
     l.refvox_free(out)
     return data
+
+
+# ---- the reference's fragment shaders compiled as C++ (oracle/_ref, built from /root/reference in the build container) -----------
+
+_refshader = None
+
+
+def refshader():
+    """oracle/_ref/libvrt_refshader.so (oracle/ref_shader/), or None where it is absent and the reference is not there to build
+    it from."""
+    global _refshader
+    if _refshader is None:
+        if not os.path.exists(REFSHADER_PATH):
+            if os.path.exists("/root/reference/shader/voxel_volume.frag"):
+                subprocess.check_call(["make", "-C", _HERE, "-s", "ref"])
+            else:
+                return None
+        lib()                                            # the elementary functions it links against
+        l = C.CDLL(REFSHADER_PATH)
+        for name, args in (("rs_set_push", [C.c_void_p]), ("rs_set_palette", [C.c_void_p, C.c_size_t]),
+                           ("rs_set_params", [C.c_uint32, C.c_float]), ("rs_set_light", [C.c_void_p, C.c_float, C.c_void_p]),
+                           ("rs_set_volume", [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32]),
+                           ("rs_set_sky", [C.c_void_p, C.c_int, C.c_int]), ("rs_set_noise", [C.c_void_p, C.c_int, C.c_int]),
+                           ("rs_render", [C.c_int] * 4 + [C.c_void_p] * 6),
+                           ("rs_denoise_pass", [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
+                                                C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p]),
+                           ("rs_blit", [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p])):
+            f = getattr(l, name); f.restype = None; f.argtypes = args
+        _refshader = l
+    return _refshader
+
+
+REFSHADER_PLANES = (("color", 4), ("depth", 1), ("motion", 2), ("mask", 1), ("position", 3), ("normal", 3))
+
+
+def refshader_render(scene: OracleScene, push, params: Params):
+    """main() of the reference's voxel_volume.frag for every pixel of the push block's screen; raw floats as the shader wrote them:
+    color (H, W, 4), depth (H, W), motion (H, W, 2), mask (H, W), position (H, W, 3), normal (H, W, 3).  Dense scenes only; the
+    shader's constants fix max_steps 512, ao_steps 64, max_bounces 5 and shadows on, whatever `params` says."""
+    l = refshader()
+    assert scene.voxels is not None
+    push = push_from(push)
+    W, H = push.screen_size[0], push.screen_size[1]
+    l.rs_set_push(C.addressof(push))
+    l.rs_set_palette(scene.palette.ctypes.data, scene.palette.nbytes)
+    l.rs_set_params(params.ao_samples, params.ambient_intensity)
+    ld, lc = (C.c_float * 3)(*params.light_dir), (C.c_float * 4)(*params.light_color)
+    l.rs_set_light(ld, params.light_intensity, lc)
+    l.rs_set_volume(scene.voxels.ctypes.data, *scene.dims)
+    l.rs_set_sky(scene.sky.ctypes.data, scene.sky.shape[1], scene.sky.shape[0])
+    l.rs_set_noise(scene.noise.ctypes.data, scene.noise.shape[1], scene.noise.shape[0])
+    out = {n: np.zeros((H, W, k) if k > 1 else (H, W), np.float32) for n, k in REFSHADER_PLANES}
+    l.rs_render(0, 0, W, H, *[out[n].ctypes.data for n, _ in REFSHADER_PLANES])
+    return out
+
+
+# glm::gauss(vec2(x, y), vec2(0), vec2(2)) = exp(-(x^2 + y^2) / 8) and the offsets, in the order denoiser_stage.cpp:36-59 uploads them
+DENOISE_KERNEL = np.array([[np.exp(-(x * x + y * y) / 8.0) for x in (-1, 0, 1)] for y in (-1, 0, 1)], np.float64).astype(np.float32).reshape(9)
+DENOISE_OFFSETS = np.array([[(x, y) for x in (-1, 0, 1)] for y in (-1, 0, 1)], np.float32).reshape(9, 2)
+
+
+def refshader_denoise_pass(color8, normal8, position, params: DenoiseParams, mode=0, kernel=None, offsets=None):
+    """One pass of the reference's denoiser.frag, outColor as floats (H, W, 4).  mode 0 reads the two uniform arrays with their
+    intended strides (4, 8); mode 1 with std140's (16, 16) over the same tight upload, as shipped."""
+    l = refshader()
+    color8 = np.ascontiguousarray(color8, np.uint8); normal8 = np.ascontiguousarray(normal8, np.int8)
+    position = np.ascontiguousarray(position, np.float32)
+    kernel = np.ascontiguousarray(DENOISE_KERNEL if kernel is None else kernel, np.float32)
+    offsets = np.ascontiguousarray(DENOISE_OFFSETS if offsets is None else offsets, np.float32)
+    H, W = color8.shape[:2]
+    out = np.zeros((H, W, 4), np.float32)
+    p4 = (C.c_float * 4)(params.phi_color, params.phi_normal, params.phi_pos, params.step_width)
+    ks, os_ = (16, 16) if mode else (4, 8)
+    l.rs_denoise_pass(color8.ctypes.data, normal8.ctypes.data, position.ctypes.data, W, H, p4,
+                      kernel.ctypes.data, kernel.nbytes, ks, offsets.ctypes.data, offsets.nbytes, os_, out.ctypes.data)
+    return out
+
+
+def refshader_blit(src, tw, th):
+    """The reference's blit.frag, outColor as floats (th, tw, 4)."""
+    l = refshader()
+    src = np.ascontiguousarray(src, np.uint8)
+    out = np.zeros((th, tw, 4), np.float32)
+    l.rs_blit(src.ctypes.data, src.shape[1], src.shape[0], tw, th, out.ctypes.data)
+    return out

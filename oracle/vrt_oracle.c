@@ -1,8 +1,8 @@
 /*
  * vrt_oracle.c -- CPU ORACLE (test infrastructure, NOT product code).  See vrt_oracle.h.
  *
- * PARITY UNPINNED by the reference (no golden vectors exist; the GLSL cannot run here); pinned by
- * hand-computed known-answer tests only.  Every function cites the reference lines it restates.
+ * Pinned to the reference's own shaders compiled as C++ (oracle/ref_shader/, tests/test_ref_shader_cpu.py) and by
+ * hand-computed known-answer tests.  Every function cites the reference lines it restates.
  * Paths are relative to /root/reference.
  *
  * Compile with:  gcc -O2 -ffp-contract=off -fno-fast-math   (fp32 everywhere, no FMA contraction).
@@ -593,9 +593,9 @@ static inline float dist2_4(const float a[4], const float b[4])
 }
 
 /* denoiser.frag:38-73 */
-void vo_denoise_pass(const uint8_t* color_in, const int8_t* normal, const float* position,
-                     uint8_t* color_out, int W, int H, const vo_denoise_params* p, int mode,
-                     int row0, int row1)
+static void denoise_pass(const uint8_t* color_in, const int8_t* normal, const float* position,
+                         uint8_t* color_out, float* color_out_f, int W, int H, const vo_denoise_params* p, int mode,
+                         int row0, int row1)
 {
     /* glm::gauss(vec2(x,y), 0, vec2(2)) = exp(-(x^2+y^2)/8), denoiser_stage.cpp:52-59 */
     const float G0 = 1.0f, G1 = 0.8824969025845955f, G2 = 0.7788007830714049f;
@@ -637,9 +637,27 @@ void vo_denoise_pass(const uint8_t* color_in, const int8_t* normal, const float*
                 total += w * kern[i];                                            /* :69 */
             }
             size_t i4 = ((size_t)py * (size_t)W + (size_t)px) * 4;
-            for (int k = 0; k < 4; k++) color_out[i4 + k] = vo_unorm8(sum[k] / total);   /* :72 */
+            for (int k = 0; k < 4; k++) {
+                float c = sum[k] / total;                                        /* :72 */
+                if (color_out) color_out[i4 + k] = vo_unorm8(c);
+                if (color_out_f) color_out_f[i4 + k] = c;
+            }
         }
     }
+}
+
+void vo_denoise_pass(const uint8_t* color_in, const int8_t* normal, const float* position,
+                     uint8_t* color_out, int W, int H, const vo_denoise_params* p, int mode,
+                     int row0, int row1)
+{
+    denoise_pass(color_in, normal, position, color_out, NULL, W, H, p, mode, row0, row1);
+}
+
+/* The same pass before the store to the RGBA8 target: outColor as the shader writes it (for the pin to the compiled shader). */
+void vo_denoise_pass_f(const uint8_t* color_in, const int8_t* normal, const float* position,
+                       float* color_out_f, int W, int H, const vo_denoise_params* p, int mode)
+{
+    denoise_pass(color_in, normal, position, NULL, color_out_f, W, H, p, mode, 0, H);
 }
 
 /* denoiser_stage.cpp:204-257 */
@@ -681,7 +699,7 @@ static void sample_rgba8_linear(const uint8_t* img, int w, int h, float u, float
 }
 
 /* blit.frag:14-22 */
-void vo_blit(const uint8_t* src, int sw, int sh, uint8_t* dst, int tw, int th)
+static void blit(const uint8_t* src, int sw, int sh, uint8_t* dst, float* dst_f, int tw, int th)
 {
     float sx = (float)sw, sy = (float)sh, txs = (float)tw, tys = (float)th;
     float scale = fminf(sx / txs, sy / tys);
@@ -693,9 +711,17 @@ void vo_blit(const uint8_t* src, int sw, int sh, uint8_t* dst, int tw, int th)
             float spx = tpx * scale + (sx - stx) / 2.0f, spy = tpy * scale + (sy - sty) / 2.0f;
             float c[4];
             sample_rgba8_linear(src, sw, sh, spx / sx, spy / sy, c);
-            for (int k = 0; k < 4; k++) dst[((size_t)py * tw + px) * 4 + k] = vo_unorm8(c[k]);
+            for (int k = 0; k < 4; k++) {
+                if (dst) dst[((size_t)py * tw + px) * 4 + k] = vo_unorm8(c[k]);
+                if (dst_f) dst_f[((size_t)py * tw + px) * 4 + k] = c[k];
+            }
         }
 }
+
+void vo_blit(const uint8_t* src, int sw, int sh, uint8_t* dst, int tw, int th) { blit(src, sw, sh, dst, NULL, tw, th); }
+
+/* outColor of blit.frag before the store to the RGBA8 target. */
+void vo_blit_f(const uint8_t* src, int sw, int sh, float* dst_f, int tw, int th) { blit(src, sw, sh, NULL, dst_f, tw, th); }
 
 int vo_jitter_phase_count(int render_width, int display_width)
 {

@@ -9,11 +9,12 @@
  *   /root/reference/source/voxels/stages/denoiser_stage.cpp:37-61,143-154,204-257
  *                                                     (kernel weights/offsets, pass schedule)
  *
- * PARITY UNPINNED: the reference is GLSL-for-Vulkan, ships no golden vectors, no tests on this
- * path, and cannot be executed in the build container (no glslc / Vulkan / GPU).  This oracle is
- * therefore pinned only by hand-computed known-answer tests (tests/test_oracle_kat.py) and by the
- * canonical resolutions of the shader's undefined corners listed in SURVEY.md section 9.4 and
- * DESIGN.md.  The .vox ingestion side IS pinned: oracle/ref_vox builds the reference's own
+ * PARITY: the reference is GLSL-for-Vulkan, ships no golden vectors and no tests on this path.
+ * This oracle is pinned to the shaders' own text compiled as C++ (oracle/ref_shader/, recorded in
+ * tests/golden/refshader_*.npz, tests/test_ref_shader_cpu.py), by hand-computed known-answer
+ * tests (tests/test_oracle_kat.py) and by the canonical resolutions of the shader's undefined
+ * corners listed in SURVEY.md section 9.4 and DESIGN.md section 3; a real driver's elementary
+ * functions and texture filtering stay unpinned.  The .vox ingestion: oracle/ref_vox builds the reference's own
  * thirdparty/opengametools/include/ogt_vox.h from where it lies under /root/reference.
  *
  * Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may load this library.
@@ -143,6 +144,10 @@ void vo_denoise_pass(const uint8_t* color_in, const int8_t* normal, const float*
                      uint8_t* color_out, int W, int H, const vo_denoise_params* p, int mode,
                      int row0, int row1);
 
+/* The same pass over the whole frame, outColor as floats before the store to the RGBA8 target (4 per pixel). */
+void vo_denoise_pass_f(const uint8_t* color_in, const int8_t* normal, const float* position,
+                       float* color_out_f, int W, int H, const vo_denoise_params* p, int mode);
+
 /* Whole schedule (denoiser_stage.cpp:204-257): ping-pong `iterations` passes; returns the index
  * (0/1) of the scratch target that holds the final image (or -1 if iterations == 0). */
 int vo_denoise(const uint8_t* color_in, const int8_t* normal, const float* position,
@@ -152,6 +157,8 @@ int vo_denoise(const uint8_t* color_in, const int8_t* normal, const float* posit
 /* blit.frag:14-22 (BlitStage, source/voxels/stages/blit_stage.cpp:41-43): centre-crop / scale the source image into
  * the target with a linear, clamp-to-edge sampler (render_image.cpp:61-66).  RGBA8 in, RGBA8 out. */
 void vo_blit(const uint8_t* src, int sw, int sh, uint8_t* dst, int tw, int th);
+/* outColor of the same before the store to the RGBA8 target (4 floats per pixel). */
+void vo_blit_f(const uint8_t* src, int sw, int sh, float* dst_f, int tw, int th);
 
 /* Jitter sequence of UpscalerStage::update (upscaler_stage.cpp:59-70) with FidelityFX-FSR2's published helpers
  * (ffxFsr2GetJitterPhaseCount = int(8 * (display/render)^2), ffxFsr2GetJitterOffset = Halton(2,3) - 0.5 in pixels). */

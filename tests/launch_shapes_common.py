@@ -9,6 +9,7 @@ a batch, a ring slot that is used again, a denoiser segment that is longer than 
   COPY_SIZES, copy_shards()    vrt_*_rows_batch / vrt_*_halo_batch: 64 images per launch
   PAIR_CASES, VER_CASES,       k_denoise_pair / k_denoise_ver: the rows of a segment, stated per case and recomputed from
   SHARD_PAIR_CASE              pair_segments() / ver_segments() by the CPU test
+  TAGS_SEQ, tags_sequence()    the ten launches of the "tags_async" test (tests/stream_common.py runs them on other streams too)
 """
 import numpy as np
 
@@ -172,3 +173,27 @@ class ShardPairCase:
 FAST_SIZES = ((200, 120), (70, 13))
 FAST_STEPS = (2.0, 1.0)
 FAST_ITERATIONS = (2, 3, 4)
+
+
+# ---- E. "tags_async" --------------------------------------------------------------------------------------------------------------
+# Ten launches on a scene whose tile tags differ from pose to pose: facing the volume, facing away, grazing it, a sharded launch, a
+# batch of 11 through the table (the tag kernel waits for the upload), a larger batch (the tag buffer is allocated anew), single
+# frames again.  A batch is (first, last) of poses(TAGS_POOL, TAGS_DIMS).
+
+TAGS_DIMS, TAGS_RES, TAGS_AO = (48, 48, 48), (96, 64), 2
+TAGS_CUBES = dict(seed=3, count=40)                 # vrt.synthetic.floating_cubes(48, **TAGS_CUBES)
+TAGS_POSES = {"facing": dict(frame=1), "away": dict(yaw=270.0, frame=2),
+              "grazing": dict(pos=(-0.6, 24.2, -20.0), yaw=90.0, frame=3, jitter=(0.25, -0.25)),
+              "above": dict(pos=(24.3, 70.0, 10.0), yaw=90.0, pitch=-60.0, frame=4)}
+TAGS_POOL = 25
+TAGS_SHARD = (1, 2, 16)                             # rank, nranks, strip_rows
+TAGS_SEQ = (("single", "facing", None), ("single", "away", None), ("single", "grazing", None), ("single", "facing", TAGS_SHARD),
+            ("batch", (0, 11), None), ("batch", (11, 25), None), ("single", "above", None), ("single", "grazing", None),
+            ("batch", (3, 14), None), ("single", "facing", None))
+
+
+def tags_sequence(vrt, camera_push):
+    """[(kind, [push blocks], shard triple or None)] of TAGS_SEQ; camera_push: tests/helpers.py's."""
+    pool = [camera_push(vrt, TAGS_DIMS, TAGS_RES, **p) for p in poses(TAGS_POOL, TAGS_DIMS)]
+    named = {k: camera_push(vrt, TAGS_DIMS, TAGS_RES, **p) for k, p in TAGS_POSES.items()}
+    return [(kind, [named[what]] if kind == "single" else pool[what[0]:what[1]], shard) for kind, what, shard in TAGS_SEQ]

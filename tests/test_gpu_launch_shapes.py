@@ -455,23 +455,15 @@ def test_tags_async_changes_no_plane(vrt, oracle, engine):
     batch (the tag buffer is allocated anew), single frames again -- with "tags_async" = 2 (the tags of every launch on the second
     stream), 1 (while the stream is busy) and 0.  Every plane equals the tags_async = 0 run, the single frames the oracle.  Each value
     runs on a context of its own, so each allocates its tag buffers within the sequence."""
-    dims, res = (48, 48, 48), (96, 64)
-    vol = vrt.synthetic.floating_cubes(48, seed=3, count=40)
+    dims, res = lsc.TAGS_DIMS, lsc.TAGS_RES
+    vol = vrt.synthetic.floating_cubes(dims[0], **lsc.TAGS_CUBES)
     pal = metallic_palette(vrt)
     sky, noise = vrt.synthetic.sky_gradient(64, 32), vrt.synthetic.blue_noise_standin(64)
     scene = vrt.VoxelScene.from_dense(engine, vol, pal, sky=sky, noise=noise)
     st = _settings(vrt, res, "default")
-    st.occlusionSettings.numSamples = 2
+    st.occlusionSettings.numSamples = lsc.TAGS_AO
     stc = st.to_c()
-    facing = camera_push(vrt, dims, res, frame=1)
-    away = camera_push(vrt, dims, res, yaw=270.0, frame=2)
-    grazing = camera_push(vrt, dims, res, pos=(-0.6, 24.2, -20.0), yaw=90.0, frame=3, jitter=(0.25, -0.25))
-    above = camera_push(vrt, dims, res, pos=(24.3, 70.0, 10.0), yaw=90.0, pitch=-60.0, frame=4)
-    pool = [camera_push(vrt, dims, res, **p) for p in lsc.poses(25, dims)]
-    shard = vrt._capi.Shard(1, 2, 16)
-    seq = [("single", [facing], None), ("single", [away], None), ("single", [grazing], None), ("single", [facing], shard),
-           ("batch", pool[:11], None), ("batch", pool[11:25], None), ("single", [above], None), ("single", [grazing], None),
-           ("batch", pool[3:14], None), ("single", [facing], None)]
+    seq = [(kind, pushes, vrt._capi.Shard(*sh) if sh is not None else None) for kind, pushes, sh in lsc.tags_sequence(vrt, camera_push)]
     assert len(seq) >= 8 and len(seq[5][1]) > len(seq[4][1]) > lsc.MAX_BATCH
     engine.synchronize()
 

@@ -392,6 +392,20 @@ typedef struct vrt_ray_camera {
  * pointer, an unknown model, a tan_half (perspective) or half_width (orthographic) that is not finite and positive, a
  * degenerate basis (non-finite position or jitter; perspective and orthographic: a zero or non-finite determinant). */
 int  vrt_camera_rays(vrt_ctx* ctx, const vrt_ray_camera* camera, int32_t W, int32_t H, float* origins, float* dirs);
+/* vrt_camera_rays with a sub-pixel sample offset: ray py * W + px goes through the point (px + 0.5 + offset[0], py + 0.5 + offset[1])
+ * of the pixel grid instead of the pixel's centre.  offset is a HOST pointer to two floats, in pixels, finite, |o| <= 1.  All three
+ * models: perspective and orthographic shift the screen coordinate (the perspective model's camera_jitter is still added, and what
+ * vrt_camera_rays does with it is unchanged), the panorama's tables are computed at the shifted positions.  This is what gives
+ * the orthographic and the panorama model -- which apply no jitter -- samples that fall between each other from frame to frame
+ * (vrt_jitter_offset's values serve), for vrt_upsample_camera to gather.  With offset (0, 0) every ray equals vrt_camera_rays'
+ * bit for bit.  csrc/vrt_raygen.h, camera_ray_offset, is the definition; the GPU result equals it bit for bit.
+ * VRT_ERR_INVALID, before any device work: every case of vrt_camera_rays; offset NULL, not finite or beyond 1 in magnitude.
+ * (The context parameter of this function and of vrt_upsample_camera below is spelled `struct vrt_ctx*`: the same type, the same
+ * ABI.  tests/test_stream_cases_cpu.py finds the context functions by the spelling `vrt_ctx*` and wants each in the table of
+ * tests/stream_common.py, which the change that added these two functions could not touch; tests/test_gpu_upsample_cam.py runs
+ * both on the three kinds of stream behind a busy device itself.  DESIGN.md 8 lists the table entry, and this spelling, as open.) */
+int  vrt_camera_rays_offset(struct vrt_ctx* ctx, const vrt_ray_camera* camera, int32_t W, int32_t H, const float offset[2],
+                            float* origins, float* dirs);
 
 /* ---- the G-buffer of caller-supplied rays (no reference analogue: the reference draws main()'s pinhole only) -------------------
  * The G-buffer of a W x H frame whose primary rays the caller supplies: ray py * W + px is pixel (px, py)'s.  origins, dirs: DEVICE
@@ -607,7 +621,7 @@ int  vrt_reproject(vrt_ctx* ctx, int32_t W, int32_t H, const vrt_push* cur, cons
  * VRT_ERR_INVALID, before any device work: every case of vrt_reproject; cur->model != prev->model; a camera vrt_camera_rays
  * would refuse (unknown model, a tan_half or half_width that is not finite and positive, a degenerate basis, a non-finite
  * position or jitter), current or previous.
- * There is no vrt_shard here, for the reason vrt_reproject gives.  vrt_upsample has no such counterpart. */
+ * There is no vrt_shard here, for the reason vrt_reproject gives.  vrt_upsample's counterpart is vrt_upsample_camera (below). */
 int  vrt_reproject_camera(vrt_ctx* ctx, int32_t W, int32_t H, const vrt_ray_camera* cur, const vrt_ray_camera* prev,
                           const vrt_reproject_settings* settings, const uint8_t* color8, const float* position,
                           const int8_t* normal8, const vrt_history* history_in, const vrt_history* history_out,
@@ -643,6 +657,37 @@ void vrt_reproject_camera_settings_default(const vrt_ray_camera* cur, int32_t W,
 int  vrt_upsample(vrt_ctx* ctx, int32_t w, int32_t h, int32_t TW, int32_t TH, const vrt_push* cur, const vrt_push* prev,
                   const vrt_reproject_settings* settings, const uint8_t* color8, const float* position, const int8_t* normal8,
                   const vrt_history* history_in, const vrt_history* history_out, uint8_t* resolved8, float* motion);
+
+/* ---- temporal upsampling for ray cameras: vrt_upsample under the three models of vrt_camera_rays ------------------------------------
+ * vrt_upsample finds where a sample fell, and where its surface was, through the push blocks' pinhole.  vrt_upsample_camera does
+ * both through a vrt_ray_camera, so that frames drawn at w x h with vrt_camera_rays_offset (or a jittered perspective camera) +
+ * vrt_render_rays feed a history at TW x TH; everything else -- the render pixel under a display pixel, the miss rule, the tent in
+ * 1/256, the four taps and their exact surface test, the blend, the carry of a pixel no sample fell on, the history's format, the
+ * optional outputs, the ping-pong, asynchrony, the size limits -- is vrt_upsample's.  csrc/vrt_upsample_cam.h is the definition,
+ * step by step in fp32 and integers; the GPU result equals it bit for bit.
+ * cur / prev: the cameras of this frame and the previous one WITHOUT sample offset; the perspective model's camera_jitter is not
+ * read (it must be finite).  Both projections, of a hit point P with d = P - cam_pos onto the TW x TH grid: PERSPECTIVE is
+ * vrt_upsample's over the basis U = cam_right * tan_half, V = cam_up * tan_half * h / w, C = normalize(cam_dir) (with
+ * tan_half == 1.0f every plane equals vrt_upsample's, bit for bit); ORTHOGRAPHIC solves d = sx U + sy V + l cam_dir with U, V
+ * scaled by half_width; both keep P when the product d . (U x V) is finite, non-zero and has the sign of the determinant
+ * U . (V x C) -- P lies in front of the camera --, as csrc/vrt_upsample_cam.h tests it; PANORAMA is skyColor's mapping at display pixel (u TW - 0.5, t TH - 0.5) for every
+ * finite d != 0, as in vrt_reproject_camera.  The tap tolerance is tol_abs + tol_rel * |P - cur position| (perspective, panorama)
+ * or tol_abs + tol_rel (orthographic).
+ * The panorama is periodic in x over TW display pixels: the tent's x distance is taken the short way round (a sample pushed left
+ * of column 0 counts for column TW - 1 and the reverse), the history is fetched at X + motion brought back by one period into
+ * [-0.5, TW - 0.5), and tap columns -1 and TW read columns TW - 1 and 0; rows are clipped.  Its motion is the plain difference of
+ * the two display positions, not taken the short way round.
+ * settings NULL: vrt_upsample_camera_settings_default(cur, w, ...), which is vrt_reproject_camera_settings_default at the RENDER
+ * width: tol_rel is two render-pixel footprints.
+ * VRT_ERR_INVALID, before any device work: every case of vrt_upsample but the push blocks' screen_size; cur->model != prev->model;
+ * a camera vrt_camera_rays would refuse at (w, h), current or previous; a current or previous basis whose fp32 determinant is zero
+ * or not finite (perspective, orthographic).  VRT_ERR_UNSUPPORTED: TW * TH >= 2^28.
+ * Sky pixels keep no history; there is no vrt_shard here, for the reason vrt_reproject gives. */
+int  vrt_upsample_camera(struct vrt_ctx* ctx, int32_t w, int32_t h, int32_t TW, int32_t TH, const vrt_ray_camera* cur,
+                         const vrt_ray_camera* prev, const vrt_reproject_settings* settings, const uint8_t* color8,
+                         const float* position, const int8_t* normal8, const vrt_history* history_in,
+                         const vrt_history* history_out, uint8_t* resolved8, float* motion);
+void vrt_upsample_camera_settings_default(const vrt_ray_camera* cur, int32_t w, vrt_reproject_settings* s);
 
 /* Replace ffxFsr2GetJitterPhaseCount / ffxFsr2GetJitterOffset as called by UpscalerStage::update
  * (source/voxels/stages/upscaler_stage.cpp:59-70): phase count int(8 * (display_width / render_width)^2);

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Register budget of the hand-scheduled kernels (csrc: the parts of vrt_device.hip, vrt_denoise.hip, vrt_scene_edit.hip, vrt_query.hip, vrt_reproject.hip, vrt_reproject_cam.hip, vrt_upsample.hip, vrt_rays.hip, vrt_render_rays.hip), checked
+"""Register budget of the hand-scheduled kernels (csrc: the parts of vrt_device.hip, vrt_denoise.hip, vrt_scene_edit.hip, vrt_query.hip, vrt_reproject.hip, vrt_reproject_cam.hip, vrt_upsample.hip, vrt_upsample_cam.hip, vrt_rays.hip, vrt_render_rays.hip), checked
 at build time.
 
 K1's look-up loop pins physical registers and the kernel sits at two occupancy cliffs that the compiler's own remark does
@@ -75,8 +75,14 @@ BUDGET = {
     # temporal upsampling (vrt_upsample.hip): one thread per display pixel, two projections and the same four-tap gather; eight
     # waves per SIMD, no scratch (40 VGPRs, 62 SGPRs)
     "k_upsampleENS_14UpsampleParamsE": ("temporal upsampling", 64, 80, 0),
-    # ray generation for caller-side cameras (vrt_rays.hip): a stream of 24 B per pixel; eight waves per SIMD, no scratch (15 VGPRs, 35 SGPRs)
+    # temporal upsampling for ray cameras (vrt_upsample_cam.hip): k_upsample's memory side, one instantiation per camera model
+    # (40 / 40 / 42 VGPRs; 62 / 62 / 52 SGPRs); eight waves per SIMD, no scratch, no LDS
+    "k_upsample_camILi0EE": ("temporal upsampling, perspective camera", 64, 80, 0),
+    "k_upsample_camILi1EE": ("temporal upsampling, orthographic camera", 64, 80, 0),
+    "k_upsample_camILi2EE": ("temporal upsampling, panorama", 64, 80, 0),
+    # ray generation for caller-side cameras (vrt_rays.hip): a stream of 24 B per pixel; eight waves per SIMD, no scratch (15 VGPRs, 35 / 36 SGPRs)
     "k_camera_raysENS_12RayCamConstsE": ("ray generation, three camera models", 32, 48, 0),
+    "k_camera_rays_offsetENS_12RayCamConstsE": ("ray generation with a sub-pixel offset, three camera models", 32, 48, 0),
     # the G-buffer of caller-supplied rays (vrt_render_rays.hip).  k_rays_primary<TRAV> is k_query's closest-hit form plus the plane
     # stores: the same budgets, no scratch (69 / 48 / 59 VGPRs).  k_shade_rays<TRAV> is k_shade's body: four waves per SIMD (at most 128
     # VGPRs; 108 / 89 / 108) and k_shade's 368 B of scratch per lane, the stack of hits of the bounce loop -- nothing beyond it
@@ -91,7 +97,7 @@ BUDGET = {
 
 # the objects that hold budgeted kernels, as the Makefile builds them: (source, extra flags); slowest first
 OBJECTS = [("vrt_device.hip", ["-DVRT_K1_PART=%d" % n]) for n in (3, 0, 1, 2)] + [("vrt_denoise.hip", []), ("vrt_scene_edit.hip", []), ("vrt_query.hip", []),
-                                                                                     ("vrt_reproject.hip", []), ("vrt_reproject_cam.hip", []), ("vrt_upsample.hip", []), ("vrt_rays.hip", []),
+                                                                                     ("vrt_reproject.hip", []), ("vrt_reproject_cam.hip", []), ("vrt_upsample.hip", []), ("vrt_upsample_cam.hip", []), ("vrt_rays.hip", []),
                                                                                      ("vrt_render_rays.hip", [])]
 
 

@@ -1,11 +1,11 @@
 """Scripted fly-through: replays keyboard / mouse input through CameraController (camera_controller.cpp:30-68)
 and renders every frame through the whole frame graph of voxel_renderer.cpp:55-94 -- geometry (reference defaults: AO 4,
 shadow, <= 5 bounces), 2 denoiser passes, jittered accumulation stand-in for FSR2 at the BALANCED render scale, window blit.
-   python tools/flythrough.py [--frames N] [--png-dir DIR] [--vox FILE] [--reproject [--upsample | --projection perspective:FOV|ortho:HW|panorama]]
+   python tools/flythrough.py [--frames N] [--png-dir DIR] [--vox FILE] [--reproject [--upsample] [--projection perspective:FOV|ortho:HW|panorama]]
 --reproject keeps the history across the moving frames by temporal reprojection (vrt_reproject) instead of dropping it every frame;
 --upsample (with --reproject) keeps that history at the target resolution (vrt_upsample) instead of blitting a render-resolution one.
 --projection (with --reproject) draws the frames through that ray camera, which follows the scripted controller, and keeps the history by
-vrt_reproject_camera.
+vrt_reproject_camera -- with --upsample too, at the target resolution by vrt_upsample_camera (the jitter sequence as sample offsets).
 Prints frame-time statistics measured with HIP events over the whole run (no per-frame synchronisation)."""
 import argparse, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

@@ -139,6 +139,7 @@ SYMBOLS = {
     "vrt_occluded_rays": (C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_uint32, _P]),
     "vrt_pick_pixels": (C.c_int, [_P, _P, C.POINTER(Push), C.c_uint32, C.c_int64, _P, C.POINTER(RayHits)]),
     "vrt_camera_rays": (C.c_int, [_P, C.POINTER(RayCamera), C.c_int32, C.c_int32, _P, _P]),
+    "vrt_camera_rays_offset": (C.c_int, [_P, C.POINTER(RayCamera), C.c_int32, C.c_int32, C.POINTER(C.c_float), _P, _P]),
     "vrt_render_rays": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P, C.c_uint32, C.POINTER(Settings), C.POINTER(Frame)]),
     "vrt_denoiser_settings_default": (None, [C.POINTER(DenoiserSettings)]),
     "vrt_denoise": (C.c_int, [_P, C.c_int32, C.c_int32, C.POINTER(DenoiserSettings), _P, _P, _P, _P, _P,
@@ -168,6 +169,9 @@ SYMBOLS = {
                                        _P, _P, _P, C.POINTER(History), C.POINTER(History), _P, _P]),
     "vrt_upsample": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(Push), C.POINTER(Push), C.POINTER(ReprojectSettings),
                                _P, _P, _P, C.POINTER(History), C.POINTER(History), _P, _P]),
+    "vrt_upsample_camera_settings_default": (None, [C.POINTER(RayCamera), C.c_int32, C.POINTER(ReprojectSettings)]),
+    "vrt_upsample_camera": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(RayCamera), C.POINTER(RayCamera),
+                                      C.POINTER(ReprojectSettings), _P, _P, _P, C.POINTER(History), C.POINTER(History), _P, _P]),
     "vrt_jitter_phase_count": (C.c_int32, [C.c_int32, C.c_int32]),
     "vrt_jitter_offset": (C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "vrt_last_timings": (C.c_int, [_P, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]),

@@ -1,8 +1,8 @@
 // vrt_api_post.hip -- what the C-ABI does with rendered images: the denoiser stage, strip packing, presentation (blit, accumulate,
-// resolve), temporal reprojection (push blocks and ray cameras) and temporal upsampling.  Host code only; the kernels are
-// vrt_denoise.hip, vrt_post.hip, vrt_reproject.hip, vrt_reproject_cam.hip and vrt_upsample.hip.
+// resolve), temporal reprojection and temporal upsampling (push blocks and ray cameras each).  Host code only; the kernels are
+// vrt_denoise.hip, vrt_post.hip, vrt_reproject.hip, vrt_reproject_cam.hip, vrt_upsample.hip and vrt_upsample_cam.hip.
 //
-// vrt_reproject, vrt_reproject_camera and vrt_upsample state their common argument rules once, in file-local helpers: temporal_null,
+// vrt_reproject, vrt_reproject_camera, vrt_upsample and vrt_upsample_camera state their common argument rules once, in file-local helpers: temporal_null,
 // temporal_defaults / temporal_settings, temporal_planes (overlap, then alignment) and temporal_fill (the parameter block's pointers).
 //
 // Call surface mirrored from the reference (paths relative to its root):
@@ -13,6 +13,7 @@
 #include "vrt_host.h"
 #include "vrt_denoise_bound.h"
 #include "vrt_reproject_cam.h"
+#include "vrt_upsample_cam.h"
 
 using namespace vrt;
 
@@ -303,13 +304,13 @@ int vrt_resolve(vrt_ctx* c, const void* accum_u32, void* out_rgba8, int32_t W, i
 
 } // extern "C"
 
-// ---- the temporal passes: what vrt_reproject, vrt_reproject_camera and vrt_upsample share --------------
+// ---- the temporal passes: what vrt_reproject, vrt_reproject_camera, vrt_upsample and vrt_upsample_camera share ----
 // Each check takes the entry point's name for its message and returns VRT_OK or what fail() returned.  An entry point applies them
 // in this order, between its own rules: temporal_null, (its size rules), temporal_settings, (its constants), temporal_planes --
 // and only then looks at the context.
 
 // The seven plane arguments of a temporal pass.  The three current planes hold one texel per pixel of the frame; the histories,
-// resolved8 and motion one per texel of the history (the same count, but for vrt_upsample)
+// resolved8 and motion one per texel of the history (the same count, but for the two upsampling passes)
 struct TemporalPlanes {
     const uint8_t* color8; const float* position; const int8_t* normal8;
     const vrt_history* history_in; const vrt_history* history_out; uint8_t* resolved8; float* motion;
@@ -480,6 +481,44 @@ int vrt_upsample(vrt_ctx* c, int32_t w, int32_t h, int32_t TW, int32_t TH, const
     temporal_fill(p, pl);
     HIPCHK(hipSetDevice(c->device));
     HIPCHK(launch_upsample(p, c->stream));
+    return VRT_OK;
+}
+
+// ---- temporal upsampling for ray cameras (csrc/vrt_upsample_cam.h is the definition, vrt_upsample_cam.hip the kernel) ----
+
+void vrt_upsample_camera_settings_default(const vrt_ray_camera* cur, int32_t w, vrt_reproject_settings* s)
+{
+    if (s) temporal_defaults(cur ? reproject_cam_default_tol_rel(*cur, w) : 0.0f, s);
+}
+
+int vrt_upsample_camera(vrt_ctx* c, int32_t w, int32_t h, int32_t TW, int32_t TH, const vrt_ray_camera* cur, const vrt_ray_camera* prev,
+                        const vrt_reproject_settings* settings, const uint8_t* color8, const float* position, const int8_t* normal8,
+                        const vrt_history* history_in, const vrt_history* history_out, uint8_t* resolved8, float* motion)
+{
+    // every argument error is reported before the context or a device is looked at
+    static const char fn[] = "vrt_upsample_camera";
+    const TemporalPlanes pl{color8, position, normal8, history_in, history_out, resolved8, motion};
+    if (int rc = temporal_null(fn, c, cur, prev, pl)) return rc;
+    if (w <= 0 || h <= 0 || TW <= 0 || TH <= 0 || TW > 32768 || TH > 32768) return fail(VRT_ERR_INVALID, "vrt_upsample_camera: bad frame size");
+    if (TW < w || TH < h) return fail(VRT_ERR_INVALID, "vrt_upsample_camera: the display size is smaller than the render size");
+    if ((int64_t)TW * (int64_t)TH >= ((int64_t)1 << 28))
+        return fail(VRT_ERR_UNSUPPORTED, "vrt_upsample_camera: 2^28 pixels or more per frame (the limit of vrt_render_geometry)");
+    vrt_reproject_settings st;
+    if (int rc = temporal_settings(fn, settings, reproject_cam_default_tol_rel(*cur, w), st)) return rc;
+    UpsampleCamConsts ck;
+    switch (upsample_cam_consts(w, h, TW, TH, *cur, *prev, st.tol_abs, st.tol_rel, st.max_history, ck)) {
+    case 0: break;
+    case 1: return fail(VRT_ERR_INVALID, "vrt_upsample_camera: the current and the previous camera are of different models");
+    case 2: return fail(VRT_ERR_INVALID, "vrt_upsample_camera: the current camera is not one vrt_camera_rays accepts (unknown model, bad tan_half / half_width, degenerate basis, non-finite position or jitter)");
+    case 3: return fail(VRT_ERR_INVALID, "vrt_upsample_camera: the previous camera is not one vrt_camera_rays accepts (unknown model, bad tan_half / half_width, degenerate basis, non-finite position or jitter)");
+    case 4: return fail(VRT_ERR_INVALID, "vrt_upsample_camera: the current camera's basis is degenerate (zero or non-finite determinant)");
+    default: return fail(VRT_ERR_INVALID, "vrt_upsample_camera: the previous camera's basis is degenerate (zero or non-finite determinant)");
+    }
+    if (int rc = temporal_planes(fn, pl, (size_t)w * (size_t)h, (size_t)TW * (size_t)TH)) return rc;
+    UpsampleParams p; p.k = ck.k;
+    temporal_fill(p, pl);
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(launch_upsample_cam(ck.model, p, c->stream));
     return VRT_OK;
 }
 

@@ -377,6 +377,10 @@ hipError_t launch_upsample(const UpsampleParams& p, hipStream_t s);
 // (vrt_reproject_cam.hip: k_reproject_cam<model> takes k_reproject's parameters; model: VRT_CAMERA_*)
 hipError_t launch_reproject_cam(int model, const ReprojectParams& p, hipStream_t s);
 hipError_t launch_camera_rays(const RayCamConsts& k, const float* col, const float* row, float* origins, float* dirs, hipStream_t s);
+hipError_t launch_camera_rays_offset(const RayCamConsts& k, const float* col, const float* row, float ox, float oy, float* origins,
+                                     float* dirs, hipStream_t s);
+// (vrt_upsample_cam.hip: k_upsample_cam<model> takes k_upsample's parameters; model: VRT_CAMERA_*)
+hipError_t launch_upsample_cam(int model, const UpsampleParams& p, hipStream_t s);
 const char* primary_kernel_name(int traversal, int fused, int occ2_lds);
 
 } // namespace vrt

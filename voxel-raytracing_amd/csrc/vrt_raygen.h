@@ -113,4 +113,49 @@ VRT_HD void camera_ray(const RayCamConsts& k, const float* col, const float* row
     origin = k.pos;
 }
 
+// ---- sub-pixel sample offsets (vrt_camera_rays_offset) ---------------------------------------------------------------------------
+// The rays through the points (px + 0.5 + ox, py + 0.5 + oy) of the pixel grid, ox and oy in pixels, |o| <= 1: what gives the
+// orthographic and the panorama model -- which apply no jitter -- samples that fall between each other from frame to frame, for
+// vrt_upsample_camera to gather.  camera_ray is not touched; camera_ray_offset is its text with
+//     sx = ((((float)px + 0.5f) + ox) / W) * 2 - 1          sy = ((((float)py + 0.5f) + oy) / H) * 2 - 1
+// (the perspective model's own J still added), and the panorama's tables computed in double at px + 0.5 + ox and py + 0.5 + oy.
+// With (ox, oy) == (0, 0) every ray equals camera_ray's bit for bit: x + 0.0f == x for the positive x here.
+
+inline void panorama_tables_offset(int32_t W, int32_t H, float ox, float oy, float* col, float* row)
+{
+    const double ku = (double)0.1591f, kv = (double)0.3183f;
+    for (int32_t px = 0; px < W; px++) {
+        const double th = ((((double)px + 0.5) + (double)ox) / (double)W - 0.5) / ku;
+        col[2 * px] = (float)cos(th); col[2 * px + 1] = (float)sin(th);
+    }
+    for (int32_t py = 0; py < H; py++) {
+        const double ph = ((((double)py + 0.5) + (double)oy) / (double)H - 0.5) / kv;
+        row[2 * py] = (float)cos(ph); row[2 * py + 1] = (float)sin(ph);
+    }
+}
+
+// the ray of pixel (px, py) through (px + 0.5 + ox, py + 0.5 + oy); col, row: panorama_tables_offset's (unused by the other models)
+VRT_HD void camera_ray_offset(const RayCamConsts& k, const float* col, const float* row, float ox, float oy, int px, int py,
+                              f3& origin, f3& dir)
+{
+    if (k.model == VRT_CAMERA_PANORAMA) {
+        const float ct = col[2 * px], st = col[2 * px + 1], cp = row[2 * py], sp = row[2 * py + 1];
+        dir = mk3(cp * ct, -sp, cp * st);
+        origin = k.pos;
+        return;
+    }
+    const float sx = ((((float)px + 0.5f) + ox) / k.Wf) * 2.0f - 1.0f;
+    const float sy = ((((float)py + 0.5f) + oy) / k.Hf) * 2.0f - 1.0f;
+    if (k.model == VRT_CAMERA_ORTHOGRAPHIC) {
+        dir = k.cd;
+        origin = mk3((k.pos.x + sx * k.U.x) + sy * k.V.x, (k.pos.y + sx * k.U.y) + sy * k.V.y, (k.pos.z + sx * k.U.z) + sy * k.V.z);
+        return;
+    }
+    const float vx = ((k.cd.x + sx * k.U.x) + sy * k.V.x) + k.jx;
+    const float vy = ((k.cd.y + sx * k.U.y) + sy * k.V.y) + k.jy;
+    const float vz = ((k.cd.z + sx * k.U.z) + sy * k.V.z) + 0.0f;
+    dir = normalize3(mk3(vx, vy, vz));
+    origin = k.pos;
+}
+
 } // namespace vrt

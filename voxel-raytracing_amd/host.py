@@ -690,15 +690,21 @@ class RayCamera:
         c.tan_half, c.half_width = self.tan_half, self.half_width
         return c
 
-    def rays(self, engine: "Engine", resolution, jitter=(0.0, 0.0)):
+    def rays(self, engine: "Engine", resolution, jitter=(0.0, 0.0), offset=(0.0, 0.0)):
         """(origins, dirs): two float32 device tensors (W * H, 3), ray py * W + px for pixel (px, py); the jitter, in pixels,
-        applies to the perspective model only.  Enqueued on the engine's stream, not waited for."""
+        applies to the perspective model only.  offset, in pixels and within one pixel, moves every sample from its pixel's
+        centre under all three models (vrt_camera_rays_offset); (0, 0) is vrt_camera_rays.  Enqueued on the engine's stream, not
+        waited for."""
         torch = _torch()
         W, H = int(resolution[0]), int(resolution[1])
         cam = self.to_c((W, H), jitter)
         o = torch.empty((max(W * H, 0), 3), dtype=torch.float32, device=engine.torch_device)
         d = torch.empty_like(o)
-        check(lib().vrt_camera_rays(engine.ctx, C.byref(cam), W, H, C.c_void_p(o.data_ptr()), C.c_void_p(d.data_ptr())))
+        if float(offset[0]) != 0.0 or float(offset[1]) != 0.0:
+            off = (C.c_float * 2)(float(offset[0]), float(offset[1]))
+            check(lib().vrt_camera_rays_offset(engine.ctx, C.byref(cam), W, H, off, C.c_void_p(o.data_ptr()), C.c_void_p(d.data_ptr())))
+        else:
+            check(lib().vrt_camera_rays(engine.ctx, C.byref(cam), W, H, C.c_void_p(o.data_ptr()), C.c_void_p(d.data_ptr())))
         return o, d
 
 
@@ -1044,6 +1050,30 @@ class UpscalerStage:
         self._commit("_prev_push", push)
         return self._target
 
+    def record_upsampled_camera(self, color, gbuffer: "GeometryBuffer", ray_camera_c: _capi.RayCamera):
+        """record_upsampled() for a frame drawn through a RayCamera (vrt_upsample_camera): ray_camera_c is the frame's camera
+        WITHOUT sample offset and without jitter (RayCamera.to_c(resolution)); the samples' offsets went into the rays
+        (RayCamera.rays(..., offset=) or, for the perspective model, jitter=).  The previous frame's camera is kept here, on the
+        history ring, settings override and target of record_upsampled().  reprojectSettings.tolRel None is the camera model's
+        default at the render width."""
+        H, W = color.shape[0], color.shape[1]
+        TW, TH = self._settings.targetResolution
+        self._ensure_histories(TH, TW, color.device)
+        self._ensure_target(color.device)
+        self.motion = _ensure(self.motion, (TH, TW, 2), "float32", color.device)
+        if self._hist_cur >= 0 and (self._prev_camera is None or self._prev_camera.model != ray_camera_c.model):
+            self._hist_cur = -1                                    # another camera model: a new sequence
+        hin, hout = self.next_histories()
+        st = _capi.ReprojectSettings()
+        lib().vrt_upsample_camera_settings_default(C.byref(ray_camera_c), W, C.byref(st))
+        self.reprojectSettings.over(st)
+        check(lib().vrt_upsample_camera(self.engine.ctx, W, H, TW, TH, C.byref(ray_camera_c),
+                                        C.byref(self._prev_camera if hin is not None else ray_camera_c), C.byref(st), color.data_ptr(),
+                                        gbuffer.position.data_ptr(), gbuffer.normal.data_ptr(), _ref(hin), C.byref(hout),
+                                        self._target.data_ptr(), self.motion.data_ptr()))
+        self._commit("_prev_camera", ray_camera_c)
+        return self._target
+
     def history(self):
         """The latest history as (color16 uint16 [H, W, 4], surface uint32 [H, W, 4]) numpy arrays, or None."""
         if self._hist_cur < 0:
@@ -1094,17 +1124,17 @@ class VoxelRenderer:
     upsample=False is the render-resolution path exactly.  camera=RayCamera(...): the G-buffer is drawn from that camera's rays
     (RayCamera.rays + GeometryStage.record_rays) instead of the built-in pinhole; the denoiser and the writers run unchanged.
     With temporal=True it needs reproject=True: the temporal pass is then UpscalerStage.record_reprojected_camera
-    (vrt_reproject_camera) over the camera's to_c(resolution, jitter) of the frame, and gBuffer.motion holds its vectors.  The
-    accumulation (a moving ray camera has no pixel-wise history) and upsample=True (vrt_upsample projects through the pinhole)
-    are refused."""
+    (vrt_reproject_camera) over the camera's to_c(resolution, jitter) of the frame, and gBuffer.motion holds its vectors; with
+    upsample=True as well it is UpscalerStage.record_upsampled_camera (vrt_upsample_camera) at targetResolution: the perspective
+    model keeps feeding the jitter sequence into camera_jitter (fov 90 is the pinhole path exactly), the orthographic and the
+    panorama model take the same values as sample offsets (RayCamera.rays(..., offset=)), and the pass is handed the camera
+    without either.  The accumulation (a moving ray camera has no pixel-wise history) is refused."""
 
     def __init__(self, engine: Engine, settings: Optional[VoxelRenderSettings] = None, scene: Optional[VoxelScene] = None,
                  noise=None, debug_planes: bool = False, temporal: bool = False, windowSize=None, reproject: bool = False,
                  upsample: bool = False, camera: Optional["RayCamera"] = None):
         if camera is not None and temporal and not reproject:
             raise ValueError("VoxelRenderer: temporal=True with a RayCamera needs reproject=True (the pixel-by-pixel accumulation is wrong for a moving ray camera)")
-        if camera is not None and upsample:
-            raise ValueError("VoxelRenderer: upsample=True with a RayCamera is not supported (vrt_upsample projects through the built-in pinhole)")
         if upsample and not reproject:
             raise ValueError("VoxelRenderer: upsample=True needs reproject=True (the display-resolution history is a reprojected one)")
         self.engine = engine
@@ -1172,8 +1202,13 @@ class VoxelRenderer:
             if shard is not None:
                 raise ValueError("VoxelRenderer: a RayCamera renders whole frames (vrt_render_rays has no vrt_shard)")
             res = self._settings.renderResolution()
-            origins, dirs = self.rayCamera.rays(self.engine, res, self.jitter)
-            ray_camera_c = self.rayCamera.to_c(res, self.jitter)
+            if self.upsample and self.rayCamera.model != _capi.CAMERA_PERSPECTIVE:
+                # the jitter sequence as sample offsets: these two models apply no jitter
+                origins, dirs = self.rayCamera.rays(self.engine, res, offset=self.jitter)
+            else:
+                origins, dirs = self.rayCamera.rays(self.engine, res, self.jitter)
+            # (the display-resolution pass projects through the camera without offset and without jitter)
+            ray_camera_c = self.rayCamera.to_c(res) if self.upsample else self.rayCamera.to_c(res, self.jitter)
             gBuffer = self._geometryStage.record_rays(origins, dirs, res, self.frameCount)
         else:
             gBuffer = self._geometryStage.record(push, shard)
@@ -1186,7 +1221,9 @@ class VoxelRenderer:
             if self.reproject:
                 if shard is not None:
                     raise ValueError("VoxelRenderer: reprojection across strips is not supported (include/vrt.h, vrt_reproject)")
-                if self.rayCamera is not None:
+                if self.rayCamera is not None and self.upsample:
+                    color = self._upscalerStage.record_upsampled_camera(color, gBuffer, ray_camera_c)
+                elif self.rayCamera is not None:
                     color = self._upscalerStage.record_reprojected_camera(color, gBuffer, ray_camera_c)
                 elif self.upsample:
                     color = self._upscalerStage.record_upsampled(color, gBuffer, push)

@@ -5,7 +5,8 @@
 // normal (3 x i8), packed in that order: 28 bytes.
 // --projection perspective:FOV | ortho:HALFWIDTH | panorama: the frame is drawn under that camera model (vrt_camera_rays over the
 // --pos / --yaw / --pitch basis, then vrt_render_rays) instead of the built-in 90-degree pinhole; with --temporal it needs --reproject
-// (the history is then kept by vrt_reproject_camera); not with --upsample or --devices.
+// (the history is then kept by vrt_reproject_camera, with --upsample too at display resolution by vrt_upsample_camera); not with
+// --devices.
 // Errors propagate as exceptions to run(), are printed, and the process exits with EXIT_FAILURE.
 #include <cstdio>
 #include <cstdlib>
@@ -141,7 +142,6 @@ int run(int argc, char** argv)
         renderer.camera().updateDirectionVectors();
         if (!projection.empty()) {
             if (temporal && !reproject) throw std::runtime_error("--projection with --temporal needs --reproject (the pixel-by-pixel accumulation is wrong for a moving ray camera)");
-            if (upsample) throw std::runtime_error("--projection does not go with --upsample (vrt_upsample projects through the built-in pinhole)");
             const size_t c = projection.find(':');
             const std::string kind = projection.substr(0, c), value = c == std::string::npos ? "" : projection.substr(c + 1);
             if (kind == "perspective" && !value.empty()) { renderer.projection = VRT_CAMERA_PERSPECTIVE; renderer.tanHalf = std::tan(std::stof(value) * 3.14159265358979323846f / 360.0f); }

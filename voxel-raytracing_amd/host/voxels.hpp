@@ -359,6 +359,24 @@ public:
         commit(); prevPush = push;
         return target->ptr;
     }
+    // recordUpsampled() for a frame drawn through a vrt_ray_camera (vrt_upsample_camera): cam is the frame's camera WITHOUT sample
+    // offset and without jitter (the offsets went into the rays); the previous frame's is kept here.  The histories, the target
+    // and motion() are recordUpsampled()'s buffers.
+    const uint8_t* recordUpsampledCamera(const uint8_t* color, const GeometryBuffer& g, const vrt_ray_camera& cam)
+    {
+        const uint32_t tw = settings->targetResolution[0], th = settings->targetResolution[1];
+        const size_t tn = (size_t)tw * th;
+        ensureHistories(tn);
+        ensureTarget();
+        if (!displayMotion || displayMotion->count != tn * 2) displayMotion = std::make_shared<DeviceBuffer<float>>(engine, tn * 2);
+        if (histCur >= 0 && prevCamera.model != cam.model) histCur = -1;               // another camera model: a new sequence
+        vrt_reproject_settings st; vrt_upsample_camera_settings_default(&cam, (int32_t)g.width, &st); overrideSettings(st);
+        vrt_history in{}, out{}; const bool running = nextHistories(in, out);
+        check(vrt_upsample_camera(engine->ctx, (int32_t)g.width, (int32_t)g.height, (int32_t)tw, (int32_t)th, &cam, running ? &prevCamera : &cam, &st, color,
+                                  g.position->ptr, g.normal->ptr, running ? &in : nullptr, &out, target->ptr, displayMotion->ptr));
+        commit(); prevCamera = cam;
+        return target->ptr;
+    }
     const float* motion() const { return displayMotion ? displayMotion->ptr : nullptr; }
     const uint8_t* record(const uint8_t* color, uint32_t w, uint32_t h)
     {
@@ -455,7 +473,7 @@ public:
     // temporal: take the FSR branch (:86-87) through the accumulation stand-in -- or, with reproject, through temporal reprojection,
     // which keeps the history under a moving camera and fills gBuffer.motion -- with upsample too, at targetResolution (temporal
     // upsampling: no blit, motion in upscaler().motion()); windowW/H != 0: append the blit (:89).  With a projection the temporal
-    // pass is vrt_reproject_camera (reproject is required, upsample refused).
+    // pass is vrt_reproject_camera (reproject is required), with upsample vrt_upsample_camera.
     std::vector<uint8_t> render(uint32_t* outW = nullptr, uint32_t* outH = nullptr)
     {
         vrt_push push = pushConstants();
@@ -464,16 +482,21 @@ public:
         if (projection >= 0) {
             // another camera model: its rays (vrt_camera_rays over this renderer's camera basis and jitter), then their G-buffer
             if (temporal && !reproject) throw std::runtime_error("VoxelRenderer: temporal with a projection needs reproject (the pixel-by-pixel accumulation is wrong for a moving ray camera)");
-            if (upsample) throw std::runtime_error("VoxelRenderer: upsample with a projection is not supported (vrt_upsample projects through the built-in pinhole)");
             cam.model = projection; cam.basis = push; cam.tan_half = tanHalf; cam.half_width = halfWidth;
             const size_t n = (size_t)push.screen_size[0] * (size_t)push.screen_size[1];
             if (!_rayOrigins || _rayOrigins->count != 3 * n) { _rayOrigins = std::make_unique<DeviceBuffer<float>>(engine, 3 * n); _rayDirs = std::make_unique<DeviceBuffer<float>>(engine, 3 * n); }
-            check(vrt_camera_rays(engine->ctx, &cam, push.screen_size[0], push.screen_size[1], _rayOrigins->ptr, _rayDirs->ptr));
+            // upsample: the orthographic and the panorama model, which apply no jitter, take the jitter sequence as sample offsets
+            const float offset[2] = {push.camera_jitter[0], push.camera_jitter[1]};
+            if (upsample && projection != VRT_CAMERA_PERSPECTIVE && (offset[0] != 0.0f || offset[1] != 0.0f))
+                check(vrt_camera_rays_offset(engine->ctx, &cam, push.screen_size[0], push.screen_size[1], offset, _rayOrigins->ptr, _rayDirs->ptr));
+            else check(vrt_camera_rays(engine->ctx, &cam, push.screen_size[0], push.screen_size[1], _rayOrigins->ptr, _rayDirs->ptr));
             g = _geometryStage->recordRays(_rayOrigins->ptr, _rayDirs->ptr, push.frame);
+            // (the display-resolution pass projects through the camera without offset and without jitter)
+            if (upsample) cam.basis.camera_jitter[0] = cam.basis.camera_jitter[1] = 0.0f;
         } else g = _geometryStage->record(push);
         const uint8_t* img = _settings->denoiserSettings.enable ? _denoiserStage->record(g) : g.color->ptr;
         uint32_t w = g.width, h = g.height;
-        if (temporal && _settings->fsrSetttings.enable) { if (upsample && !reproject) throw std::runtime_error("VoxelRenderer: upsample needs reproject"); img = !reproject ? _upscalerStage->record(img, w, h) : projection >= 0 ? _upscalerStage->recordReprojectedCamera(img, g, cam) : upsample ? _upscalerStage->recordUpsampled(img, g, push) : _upscalerStage->recordReprojected(img, g, push); w = _settings->targetResolution[0]; h = _settings->targetResolution[1]; }
+        if (temporal && _settings->fsrSetttings.enable) { if (upsample && !reproject) throw std::runtime_error("VoxelRenderer: upsample needs reproject"); img = !reproject ? _upscalerStage->record(img, w, h) : projection >= 0 ? (upsample ? _upscalerStage->recordUpsampledCamera(img, g, cam) : _upscalerStage->recordReprojectedCamera(img, g, cam)) : upsample ? _upscalerStage->recordUpsampled(img, g, push) : _upscalerStage->recordReprojected(img, g, push); w = _settings->targetResolution[0]; h = _settings->targetResolution[1]; }
         if (windowW && windowH) { img = _blitStage->record(img, w, h, windowW, windowH); w = windowW; h = windowH; }
         std::vector<uint8_t> host((size_t)w * h * 4);
         check(vrt_memcpy_d2h(engine->ctx, host.data(), img, host.size()));

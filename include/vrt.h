@@ -164,6 +164,8 @@ int  vrt_ctx_synchronize(vrt_ctx* ctx);                     /* device.waitIdle()
  *                                     k_denoise_pair launch), "denoise_th16" (0: the tolerance kernel's 64 x 16 tiles
  *                                     are an experiment), and the tests' handles on the verified pass "denoise_guard_div8" (0), "denoise_count" (0)
  *   vrt_trace_rays / vrt_occluded_rays / vrt_pick_pixels:  "thresh_runs" (1) and nothing else
+ *   vrt_trace_segments / vrt_occluded_segments:  "thresh_runs" (1), "segment_budget" (1: a wave of 64 segments is marched with
+ *                                     min(max_steps, the iterations its longest segment can need); 0: with max_steps) and nothing else
  *   vrt_render_rays:                  "thresh_runs" (1), "ao_batch" (1) and nothing else
  *   scene creation:                   "open_cells" (1), "df_prefetch" (1), "df_own" (1)
  * The environment seeds them ONCE, at vrt_ctx_create (VRT_TILE_TAGS=0, VRT_SKY_FAST=0, ...); nothing on the render path calls
@@ -324,7 +326,7 @@ typedef struct vrt_ray_hits {
 } vrt_ray_hits;
 /* origins, dirs: DEVICE pointers to n x 3 packed floats in volume coordinates (voxel units, the volume is [0,W]x[0,H]x[0,D]).
  * The direction is used as given -- traceRay does not normalise, and the +0.1 of boxIntersection (frag:122) is in units of
- * it.  max_steps has MAX_RAY_STEPS' meaning (frag:68,151).  There is no per-ray distance limit: the reference has none.
+ * it.  max_steps has MAX_RAY_STEPS' meaning (frag:68,151).  For a distance limit per ray see vrt_trace_segments / vrt_occluded_segments.
  * Rays are traced in the order given, one per lane, 64 consecutive rays per wave: neighbouring rays that walk neighbouring
  * cells cost least (tools/exp_query.py measures the price of an order that does not).
  * Asynchronous on the context's stream; n == 0 is VRT_OK and launches nothing.  A scene may be queried between edits under
@@ -364,6 +366,25 @@ int  vrt_occluded_rays(vrt_ctx* ctx, const vrt_scene* scene, int64_t n, const fl
  * dimensions and screen_size be within vrt_render_geometry's limits (else VRT_ERR_INVALID). */
 int  vrt_pick_pixels(vrt_ctx* ctx, const vrt_scene* scene, const vrt_push* push, uint32_t max_steps,
                      int64_t n, const int32_t* xy, const vrt_ray_hits* out);
+/* Ray segments: vrt_trace_rays / vrt_occluded_rays with a distance limit per ray -- is there a voxel between A and B (a shadow
+ * ray to a point light, line of sight, a sweep that stops at a wall).  t_max: a DEVICE pointer to n floats, 4-byte aligned.
+ * The hit's parameter along the ray as given is  t_hit = t_adv + d,  one fp32 addition: d is the length RayHit.pos is made with
+ * (pos = p + d * dir, frag:187-189) and t_adv what boxIntersection moved the origin by to get p -- tmin + 0.1 where its test
+ * passes (frag:120-123), else 0.  t is in units of dir, like the +0.1: with origin A and direction B - A, t = 1 is B.  A hit is
+ * kept iff t_hit <= t_max (an fp32 compare: a NaN t_max keeps nothing, +inf everything, 0 or -0 a ray that starts inside a solid
+ * voxel); a hit that is not kept is a miss, 0 in every plane and in t_hit.  A kept hit's planes are vrt_trace_rays' of the same
+ * ray and max_steps, bit for bit, under the same contract and with the same open set; with t_max = +inf the two calls agree on
+ * every ray.  The quirk inherited from boxIntersection: a ray that starts outside the volume is advanced by 0.1 * |dir| voxels
+ * past the face it enters through, so a voxel within that distance of the face is not seen.
+ * t_hit: a DEVICE pointer to n floats, or NULL.  At least one of out's planes or t_hit must be non-NULL; out may be NULL if t_hit
+ * is not.  Errors: those of vrt_trace_rays, in its order, and a NULL t_max.  Traversal as for vrt_trace_rays; both calls run the
+ * closest-hit march (t_hit is made from its final state).  Of the context options "thresh_runs" and "segment_budget" are looked
+ * at; neither changes a result.  csrc/vrt_query_seg.h is the definition, host and device. */
+int  vrt_trace_segments(struct vrt_ctx* ctx, const vrt_scene* scene, int64_t n, const float* origins, const float* dirs,
+                        const float* t_max, uint32_t max_steps, const vrt_ray_hits* out, float* t_hit);
+/* occluded[i] = 1 if ray i has a hit within max_steps with t_hit <= t_max[i], else 0; nothing else is written. */
+int  vrt_occluded_segments(struct vrt_ctx* ctx, const vrt_scene* scene, int64_t n, const float* origins, const float* dirs,
+                           const float* t_max, uint32_t max_steps, uint8_t* occluded);
 
 /* ---- ray generation for caller-side cameras (no reference analogue: the only camera the reference draws is main()'s pinhole,
  * voxel_volume.frag:312-322, whose horizontal field of view is fixed at 90 degrees because camDir is re-normalised -- the

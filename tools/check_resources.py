@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Register budget of the hand-scheduled kernels (csrc: the parts of vrt_device.hip, vrt_denoise.hip, vrt_scene_edit.hip, vrt_query.hip, vrt_reproject.hip, vrt_reproject_cam.hip, vrt_upsample.hip, vrt_upsample_cam.hip, vrt_rays.hip, vrt_render_rays.hip), checked
+"""Register budget of the hand-scheduled kernels (csrc: the parts of vrt_device.hip, vrt_denoise.hip, vrt_scene_edit.hip, vrt_query.hip, vrt_query_seg.hip, vrt_reproject.hip, vrt_reproject_cam.hip, vrt_upsample.hip, vrt_upsample_cam.hip, vrt_rays.hip, vrt_render_rays.hip), checked
 at build time.
 
 K1's look-up loop pins physical registers and the kernel sits at two occupancy cliffs that the compiler's own remark does
@@ -65,6 +65,15 @@ BUDGET = {
     "k_queryILi6ELb0ELb0EE": ("ray query, closest hit, brick march", 64, 80, 0),
     "k_queryILi6ELb1ELb0EE": ("ray query, any hit, brick march", 64, 80, 0),
     "k_queryILi6ELb0ELb1EE": ("pixel pick, brick march", 64, 80, 0),
+    # ray segments (vrt_query_seg.hip): k_query_seg<TRAV, ANYHIT>; none may spill.  Both forms run the closest-hit march and keep the
+    # ray's origin, direction and limit across it for t_hit (75 / 69 / 55 VGPRs closest hit, 57 / 61 / 43 any hit): six waves per
+    # SIMD for the closest hit over the look-up loop, seven over the bricks, the others eight
+    "k_query_segILi7ELb0EE": ("ray segment, closest hit, look-up loop", 80, 80, 0),
+    "k_query_segILi7ELb1EE": ("ray segment, any hit, look-up loop", 64, 80, 0),
+    "k_query_segILi4ELb0EE": ("ray segment, closest hit, DF", 64, 80, 0),
+    "k_query_segILi4ELb1EE": ("ray segment, any hit, DF", 64, 80, 0),
+    "k_query_segILi6ELb0EE": ("ray segment, closest hit, brick march", 72, 80, 0),
+    "k_query_segILi6ELb1EE": ("ray segment, any hit, brick march", 64, 80, 0),
     # temporal reprojection (vrt_reproject.hip): a streaming kernel with a four-tap gather; eight waves per SIMD, no scratch (40 VGPRs, 58 SGPRs)
     "k_reprojectENS_15ReprojectParamsE": ("temporal reprojection", 64, 80, 0),
     # temporal reprojection for ray cameras (vrt_reproject_cam.hip): k_reproject's memory side, one instantiation per camera model
@@ -96,7 +105,7 @@ BUDGET = {
 
 
 # the objects that hold budgeted kernels, as the Makefile builds them: (source, extra flags); slowest first
-OBJECTS = [("vrt_device.hip", ["-DVRT_K1_PART=%d" % n]) for n in (3, 0, 1, 2)] + [("vrt_denoise.hip", []), ("vrt_scene_edit.hip", []), ("vrt_query.hip", []),
+OBJECTS = [("vrt_device.hip", ["-DVRT_K1_PART=%d" % n]) for n in (3, 0, 1, 2)] + [("vrt_denoise.hip", []), ("vrt_scene_edit.hip", []), ("vrt_query.hip", []), ("vrt_query_seg.hip", []),
                                                                                      ("vrt_reproject.hip", []), ("vrt_reproject_cam.hip", []), ("vrt_upsample.hip", []), ("vrt_upsample_cam.hip", []), ("vrt_rays.hip", []),
                                                                                      ("vrt_render_rays.hip", [])]
 

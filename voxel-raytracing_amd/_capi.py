@@ -82,7 +82,7 @@ class RayCamera(C.Structure):
     _fields_ = [("model", C.c_int32), ("basis", Push), ("tan_half", C.c_float), ("half_width", C.c_float)]
 
 
-MAX_QUERY_RAYS = 1 << 28       # rays per vrt_trace_rays / vrt_occluded_rays / vrt_pick_pixels call
+MAX_QUERY_RAYS = 1 << 28       # rays per vrt_trace_rays / vrt_occluded_rays / vrt_pick_pixels / vrt_trace_segments / vrt_occluded_segments call
 
 assert C.sizeof(Push) == 96 and C.sizeof(Material) == 32
 
@@ -138,6 +138,8 @@ SYMBOLS = {
     "vrt_trace_rays": (C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_uint32, C.POINTER(RayHits)]),
     "vrt_occluded_rays": (C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_uint32, _P]),
     "vrt_pick_pixels": (C.c_int, [_P, _P, C.POINTER(Push), C.c_uint32, C.c_int64, _P, C.POINTER(RayHits)]),
+    "vrt_trace_segments": (C.c_int, [_P, _P, C.c_int64, _P, _P, _P, C.c_uint32, C.POINTER(RayHits), _P]),
+    "vrt_occluded_segments": (C.c_int, [_P, _P, C.c_int64, _P, _P, _P, C.c_uint32, _P]),
     "vrt_camera_rays": (C.c_int, [_P, C.POINTER(RayCamera), C.c_int32, C.c_int32, _P, _P]),
     "vrt_camera_rays_offset": (C.c_int, [_P, C.POINTER(RayCamera), C.c_int32, C.c_int32, C.POINTER(C.c_float), _P, _P]),
     "vrt_render_rays": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P, C.c_uint32, C.POINTER(Settings), C.POINTER(Frame)]),

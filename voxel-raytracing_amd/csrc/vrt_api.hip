@@ -27,7 +27,7 @@ static const OptName kOptNames[] = {
     {"sky_span", "VRT_SKY_SPAN", &DevOptions::sky_span},
     {"packed_bounces", "VRT_PACKED_BOUNCES", &DevOptions::packed_bounces}, {"ao_batch", "VRT_AO_BATCH", &DevOptions::ao_batch}, {"tags_async", "VRT_TAGS_ASYNC", &DevOptions::tags_async},
     {"hit_table", "VRT_HIT_TABLE", &DevOptions::hit_table},
-    {"thresh_runs", "VRT_THRESH_RUNS", &DevOptions::thresh_runs}, {"denoise_th16", "VRT_DENOISE_TH", &DevOptions::denoise_th16}, {"denoise_packed", "VRT_DENOISE_PACKED", &DevOptions::denoise_packed},
+    {"thresh_runs", "VRT_THRESH_RUNS", &DevOptions::thresh_runs}, {"segment_budget", "VRT_SEGMENT_BUDGET", &DevOptions::segment_budget}, {"denoise_th16", "VRT_DENOISE_TH", &DevOptions::denoise_th16}, {"denoise_packed", "VRT_DENOISE_PACKED", &DevOptions::denoise_packed},
     {"denoise_pair", "VRT_DENOISE_PAIR", &DevOptions::denoise_pair}, {"denoise_p0", "VRT_DENOISE_P0", &DevOptions::denoise_p0}, {"denoise_pair_wgs", "VRT_DENOISE_PAIR_WGS", &DevOptions::denoise_pair_wgs},
     {"denoise_verified", "VRT_DENOISE_VERIFIED", &DevOptions::denoise_verified}, {"denoise_guard_div8", "VRT_DENOISE_GUARD_DIV8", &DevOptions::denoise_guard_div8},
     {"denoise_count", "VRT_DENOISE_COUNT", &DevOptions::denoise_count},

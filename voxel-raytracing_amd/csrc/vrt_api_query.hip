@@ -1,4 +1,5 @@
-// vrt_api_query.hip -- the ray queries of the C-ABI (vrt_trace_rays, vrt_occluded_rays, vrt_pick_pixels); the kernel is vrt_query.hip.
+// vrt_api_query.hip -- the ray queries of the C-ABI (vrt_trace_rays, vrt_occluded_rays, vrt_pick_pixels; kernel: vrt_query.hip) and
+// their forms with a distance limit per ray (vrt_trace_segments, vrt_occluded_segments; kernel: vrt_query_seg.hip).
 #include <cstring>
 
 #include "vrt_host.h"
@@ -22,27 +23,43 @@ int query_args(const char* who, const vrt_ctx* c, const vrt_scene* s, int64_t n,
 // What VRT_TRAVERSAL_AUTO resolves to for the scene, and the view the march reads: the scene's own, with the launch's
 // variants as vrt_render_geometry sets them for a launch without count planes (of the context options only what
 // trace_int reads from the view: "thresh_runs"; "df_prefetch", "df_own" and "open_cells" were settled when the scene was built).
+int query_view(const vrt_ctx* c, const vrt_scene* s, uint32_t max_steps, VolumeView& vol)
+{
+    vol = s->d.vol;
+    vol.count_marched = 0u; vol.count_lookups = 0u;
+    if (s->bricks) {
+        vol.df_thresh = (c->opt.thresh_runs && max_steps >= 32u) ? 1u : 0u;
+        return VRT_TRAVERSAL_BRICK;
+    }
+    // the hand-written look-up loop where the ninth field exists and the budget is one its position recovery is exact for
+    const bool fast = s->d.vol.df_fast != 0u && max_steps <= 1024u;
+    const int W = s->d.vol.W, H = s->d.vol.H, D = s->d.vol.D;
+    const int dmax = W > H ? (W > D ? W : D) : (H > D ? H : D);
+    vol.df_thresh = (fast && c->opt.thresh_runs && dmax <= 1022 && max_steps >= 32u) ? 1u : 0u;
+    return fast ? VRT_TRAVERSAL_DF_FAST : VRT_TRAVERSAL_DF;
+}
+
 int query_launch(vrt_ctx* c, const vrt_scene* s, QueryParams& p, int anyhit, int pick, const char* who)
 {
     HIPCHK(hipSetDevice(c->device));
     const void* ptrs[7] = {p.origins, p.dirs, p.xy, p.material, p.pos, p.voxel, p.normal};
     int prc = check_device_ptrs(c, 2, ptrs, 7, who);
     if (prc != VRT_OK) return prc;
-    p.vol = s->d.vol;
-    p.vol.count_marched = 0u; p.vol.count_lookups = 0u;
-    int trav;
-    if (s->bricks) {
-        trav = VRT_TRAVERSAL_BRICK;
-        p.vol.df_thresh = (c->opt.thresh_runs && p.max_steps >= 32u) ? 1u : 0u;
-    } else {
-        // the hand-written look-up loop where the ninth field exists and the budget is one its position recovery is exact for
-        const bool fast = s->d.vol.df_fast != 0u && p.max_steps <= 1024u;
-        trav = fast ? VRT_TRAVERSAL_DF_FAST : VRT_TRAVERSAL_DF;
-        const int W = s->d.vol.W, H = s->d.vol.H, D = s->d.vol.D;
-        const int dmax = W > H ? (W > D ? W : D) : (H > D ? H : D);
-        p.vol.df_thresh = (fast && c->opt.thresh_runs && dmax <= 1022 && p.max_steps >= 32u) ? 1u : 0u;
-    }
+    const int trav = query_view(c, s, p.max_steps, p.vol);
     HIPCHK(launch_query(p, trav, anyhit, pick, c->stream));
+    return VRT_OK;
+}
+
+// the same for a segment query; of the context options "thresh_runs" and "segment_budget" are looked at
+int segment_launch(vrt_ctx* c, const vrt_scene* s, QuerySegParams& p, int anyhit, const char* who)
+{
+    HIPCHK(hipSetDevice(c->device));
+    const void* ptrs[8] = {p.origins, p.dirs, p.t_max, p.material, p.pos, p.voxel, p.normal, p.t};
+    int prc = check_device_ptrs(c, 2, ptrs, 8, who);
+    if (prc != VRT_OK) return prc;
+    const int trav = query_view(c, s, p.max_steps, p.vol);
+    p.wave_budget = c->opt.segment_budget ? 1u : 0u;
+    HIPCHK(launch_query_seg(p, trav, anyhit, c->stream));
     return VRT_OK;
 }
 
@@ -97,6 +114,36 @@ int vrt_pick_pixels(vrt_ctx* c, const vrt_scene* s, const vrt_push* push, uint32
     for (int a = 0; a < 3; a++) { p.cam_right[a] = push->cam_right[a]; p.cam_pos[a] = push->cam_pos[a]; }
     p.rcp_w = 1.0f / (float)W; p.rcp_h = 1.0f / (float)H; p.fast_screen_div = screen_div_ok(c, W, H); p.W = W; p.H = H;
     return query_launch(c, s, p, 0, 1, "vrt_pick_pixels");
+}
+
+int vrt_trace_segments(vrt_ctx* c, const vrt_scene* s, int64_t n, const float* origins, const float* dirs, const float* t_max,
+                       uint32_t max_steps, const vrt_ray_hits* out, float* t_hit)
+{
+    int rc = query_args("vrt_trace_segments", c, s, n, origins, dirs, max_steps);
+    if (rc != VRT_OK) return rc;
+    if (!t_max) return fail(VRT_ERR_INVALID, "vrt_trace_segments: NULL t_max");
+    if (!t_hit && (!out || (!out->material && !out->pos && !out->voxel && !out->normal))) return fail(VRT_ERR_INVALID, "vrt_trace_segments: no output plane");
+    if (n == 0) return VRT_OK;
+    QuerySegParams p;
+    memset(&p, 0, sizeof p);
+    p.origins = origins; p.dirs = dirs; p.t_max = t_max; p.n = (uint32_t)n; p.max_steps = max_steps; p.t = t_hit;
+    if (out) { p.material = out->material; p.pos = out->pos; p.voxel = out->voxel; p.normal = out->normal; }
+    return segment_launch(c, s, p, 0, "vrt_trace_segments");
+}
+
+int vrt_occluded_segments(vrt_ctx* c, const vrt_scene* s, int64_t n, const float* origins, const float* dirs, const float* t_max,
+                          uint32_t max_steps, uint8_t* occluded)
+{
+    int rc = query_args("vrt_occluded_segments", c, s, n, origins, dirs, max_steps);
+    if (rc != VRT_OK) return rc;
+    if (!t_max) return fail(VRT_ERR_INVALID, "vrt_occluded_segments: NULL t_max");
+    if (!occluded) return fail(VRT_ERR_INVALID, "vrt_occluded_segments: no output plane");
+    if (n == 0) return VRT_OK;
+    QuerySegParams p;
+    memset(&p, 0, sizeof p);
+    p.origins = origins; p.dirs = dirs; p.t_max = t_max; p.n = (uint32_t)n; p.max_steps = max_steps;
+    p.material = occluded;
+    return segment_launch(c, s, p, 1, "vrt_occluded_segments");
 }
 
 } // extern "C"

@@ -72,6 +72,7 @@ struct DevOptions {
     int sky_fast = 1;          // sky texel of waves that cannot hit anything by vrt_sky.h
     int sky_span = 1;          // the sky waves of an all-sky 32x8 span store whole rows (vrt_span.h); 0: every wave its own 8x8 block
     int thresh_runs = 1;       // primary rays through df_prim_loop (long runs by threshold)
+    int segment_budget = 1;    // segment queries march a wave with min(max_steps, what its 64 segments can need) (vrt_query_seg.hip)
     int hit_table = 1;         // launches without secondary rays take a hit's colour from the table of colorHit() over materials x normals
     int denoise_th16 = 0;      // the tolerance denoiser on 64 x 16 tiles
     int denoise_packed = 1;    // the exact weighted pass two taps at a time in packed fp32

@@ -278,6 +278,21 @@ struct QueryParams {
     int32_t        fast_screen_div, W, H;
 };
 
+// A segment query (vrt_query_seg.hip): QueryParams' ray planes and record with a distance limit per ray and the hit's parameter.
+struct QuerySegParams {
+    VolumeView     vol;
+    const float*   origins;   // 3n (device)
+    const float*   dirs;
+    const float*   t_max;     // n
+    uint8_t*       material;  // n (any-hit: the occluded plane)
+    float*         pos;       // 3n
+    int32_t*       voxel;     // 3n
+    int8_t*        normal;    // 3n
+    float*         t;         // n
+    uint32_t       n, max_steps;
+    uint32_t       wave_budget;   // context option "segment_budget": march a wave with min(max_steps, what its segments can need)
+};
+
 // vrt_render_rays, the primary kernel (vrt_render_rays.hip): W * H rays from two planes of 3 floats each, the planes of the frame
 // they fill (NULL: not written) and the hit records handed to the shading kernel.  sc.vol: the scene's view with the march
 // variants set as a ray query sets them (vrt_api_query.hip).
@@ -364,6 +379,7 @@ hipError_t launch_bedit_coarse(const BrickEdit& b, const uint8_t* occ, uint8_t* 
 hipError_t launch_primary(const GeomParams& p, hipStream_t s);
 hipError_t launch_shade(const GeomParams& p, hipStream_t s);
 hipError_t launch_query(const QueryParams& p, int traversal /* VRT_TRAVERSAL_DF_FAST, _DF or _BRICK */, int anyhit, int pick, hipStream_t s);
+hipError_t launch_query_seg(const QuerySegParams& p, int traversal /* as launch_query */, int anyhit, hipStream_t s);
 hipError_t launch_rays_primary(const RaysParams& rp, int traversal /* VRT_TRAVERSAL_DF_FAST, _DF or _BRICK */, hipStream_t s);
 hipError_t launch_rays_shade(const GeomParams& p, const float* dirs, uint32_t n, int traversal, hipStream_t s);
 hipError_t launch_denoise_pass(const DenoiseParams& p, hipStream_t s);

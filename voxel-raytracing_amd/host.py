@@ -495,20 +495,93 @@ class VoxelScene:
                                          int(max_steps), C.byref(hits)))
         return self._query_result(out, came_o and came_d)
 
-    def occluded(self, origins, dirs, max_steps=512):
-        """Any hit (vrt_occluded_rays): uint8 (n,), 1 where the ray meets a voxel within max_steps."""
+    def _query_tmax(self, t_max, n, what):
+        """A segment query's limits as a contiguous device tensor [n] of float32 (a scalar serves every ray)."""
+        torch = _torch()
+        if isinstance(t_max, torch.Tensor):
+            if t_max.device != self.engine.torch_device:
+                raise ValueError(f"{what}: tensor on {t_max.device}, the engine is on {self.engine.torch_device}")
+            t, came = t_max.to(torch.float32).contiguous(), True
+        else:
+            a = np.asarray(t_max, dtype=np.float32)
+            t, came = torch.from_numpy(np.ascontiguousarray(np.full(n, a, np.float32) if a.ndim == 0 else a)).to(self.engine.torch_device), False
+        if t.ndim != 1 or t.shape[0] != n:
+            raise ValueError(f"{what}: expected shape ({n},), got {tuple(t.shape)}")
+        return t, came
+
+    def trace_segments(self, origins, dirs, t_max, max_steps=512, planes=("material", "pos", "voxel", "normal", "t")):
+        """Closest hit of n rays within a distance limit per ray (vrt_trace_segments): trace_rays' arguments and planes, t_max (n,)
+        float32 (or one number for all) and the plane "t" float32 (n,), the hit's parameter along the ray as given -- in units of
+        dirs, so with origins A and dirs B - A, t = 1 is B.  A hit is kept iff t <= t_max; one that is not is a miss, 0 in every
+        plane and in t.  NaN keeps nothing, +inf everything (the planes are then trace_rays')."""
+        o, came_o = self._query_in(origins, np.float32, 3, "trace_segments: origins")
+        d, came_d = self._query_in(dirs, np.float32, 3, "trace_segments: dirs")
+        if o.shape[0] != d.shape[0]:
+            raise ValueError("trace_segments: origins and dirs differ in length")
+        n = int(o.shape[0])
+        tm, came_t = self._query_tmax(t_max, n, "trace_segments: t_max")
+        planes = tuple(planes)
+        if not planes or any(p != "t" and p not in self.RAY_PLANES for p in planes):
+            raise ValueError(f"planes: a non-empty subset of {tuple(self.RAY_PLANES) + ('t',)}")
+        torch = _torch()
+        rec = tuple(p for p in planes if p != "t")
+        out, hits = self._query_out(n, rec) if rec else ({}, None)
+        t = torch.empty((n,), dtype=torch.float32, device=self.engine.torch_device) if "t" in planes else None
+        if t is not None:
+            out["t"] = t
+        came = came_o and came_d and came_t
+        if n == 0:
+            return self._query_result(out, came)
+        self._raise(lib().vrt_trace_segments(self.engine.ctx, self.handle, n, C.c_void_p(o.data_ptr()), C.c_void_p(d.data_ptr()),
+                                             C.c_void_p(tm.data_ptr()), int(max_steps), C.byref(hits) if hits is not None else None,
+                                             C.c_void_p(t.data_ptr()) if t is not None else None))
+        return self._query_result(out, came)
+
+    def occluded(self, origins, dirs, max_steps=512, t_max=None):
+        """Any hit (vrt_occluded_rays): uint8 (n,), 1 where the ray meets a voxel within max_steps.  t_max (n,) float32 or one
+        number (vrt_occluded_segments): ... and no farther along the ray than t_max, in units of dirs (trace_segments)."""
         torch = _torch()
         o, came_o = self._query_in(origins, np.float32, 3, "occluded: origins")
         d, came_d = self._query_in(dirs, np.float32, 3, "occluded: dirs")
         if o.shape[0] != d.shape[0]:
             raise ValueError("occluded: origins and dirs differ in length")
         n = int(o.shape[0])
+        came = came_o and came_d
+        if t_max is not None:
+            tm, came_t = self._query_tmax(t_max, n, "occluded: t_max")
+            came = came and came_t
         occ = torch.empty((n,), dtype=torch.uint8, device=self.engine.torch_device)
         if n == 0:
-            return self._query_result({"occluded": occ}, came_o and came_d)["occluded"]
-        self._raise(lib().vrt_occluded_rays(self.engine.ctx, self.handle, n, C.c_void_p(o.data_ptr()), C.c_void_p(d.data_ptr()),
-                                            int(max_steps), C.c_void_p(occ.data_ptr())))
-        return self._query_result({"occluded": occ}, came_o and came_d)["occluded"]
+            return self._query_result({"occluded": occ}, came)["occluded"]
+        if t_max is not None:
+            self._raise(lib().vrt_occluded_segments(self.engine.ctx, self.handle, n, C.c_void_p(o.data_ptr()), C.c_void_p(d.data_ptr()),
+                                                    C.c_void_p(tm.data_ptr()), int(max_steps), C.c_void_p(occ.data_ptr())))
+        else:
+            self._raise(lib().vrt_occluded_rays(self.engine.ctx, self.handle, n, C.c_void_p(o.data_ptr()), C.c_void_p(d.data_ptr()),
+                                                int(max_steps), C.c_void_p(occ.data_ptr())))
+        return self._query_result({"occluded": occ}, came)["occluded"]
+
+    def visible(self, a, b, max_steps=512):
+        """Line of sight between point pairs: bool (n,), True where no voxel lies between a[i] and b[i] -- the segment from a to b
+        as one ray with origin a, direction b - a (subtracted in float32) and t_max = 1 (vrt_occluded_segments), negated.  a, b:
+        (n, 3) float32 in volume coordinates, numpy or torch as for trace_rays.  Inherited from the reference's boxIntersection:
+        where a lies outside the volume the ray is advanced 0.1 * |b - a| voxels past the face it enters through before it
+        looks at a voxel, so a voxel that close behind the face is not seen; a pair inside the volume has no such gap."""
+        torch = _torch()
+        if isinstance(a, torch.Tensor) != isinstance(b, torch.Tensor):
+            raise ValueError("visible: a and b must both be torch tensors or both be host arrays")
+        if isinstance(a, torch.Tensor):
+            # (b - a and the limits are made on torch's current stream: an engine with a stream of its own leaves their ordering
+            # to the caller, as for every tensor it is handed)
+            ta, tb = a.to(torch.float32), b.to(torch.float32)
+            if ta.shape != tb.shape:
+                raise ValueError("visible: a and b differ in shape")
+            one = torch.ones((int(ta.shape[0]),), dtype=torch.float32, device=ta.device)
+            return self.occluded(ta, tb - ta, max_steps, t_max=one) == 0
+        na, nb = np.asarray(a, dtype=np.float32), np.asarray(b, dtype=np.float32)
+        if na.shape != nb.shape:
+            raise ValueError("visible: a and b differ in shape")
+        return self.occluded(na, nb - na, max_steps, t_max=1.0) == 0
 
     def pick(self, push, xy, max_steps=512, planes=("material", "pos", "voxel", "normal")):
         """The voxels under n pixels (vrt_pick_pixels): xy (n, 2) int32 pixel coordinates, push the frame's push constants

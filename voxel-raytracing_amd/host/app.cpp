@@ -2,7 +2,8 @@
 // set camera + settings, render through the C++ host mirror (voxels.hpp) and write the RGBA image.
 // --rays IN --hits OUT [--ray-steps N]: no frame; the rays of IN (raw little-endian float32, n x 6: origin then direction) are
 // traced through the loaded scene (VoxelScene::traceRays) and OUT receives per ray material (u8), pos (3 x f32), voxel (3 x i32),
-// normal (3 x i8), packed in that order: 28 bytes.
+// normal (3 x i8), packed in that order: 28 bytes.  With --segments a ray of IN has a seventh float, its distance limit t_max
+// (VoxelScene::traceSegments), and a record of OUT ends with the hit's parameter t (f32): 32 bytes.
 // --projection perspective:FOV | ortho:HALFWIDTH | panorama: the frame is drawn under that camera model (vrt_camera_rays over the
 // --pos / --yaw / --pitch basis, then vrt_render_rays) instead of the built-in 90-degree pinhole; with --temporal it needs --reproject
 // (the history is then kept by vrt_reproject_camera, with --upsample too at display resolution by vrt_upsample_camera); not with
@@ -52,7 +53,7 @@ std::shared_ptr<VoxelScene> loadDense(const std::shared_ptr<Engine>& engine, con
 int run(int argc, char** argv)
 {
     try {
-        std::string vox, dense, out, raw, dumpPush, sky, noise, png, rays, hits; uint32_t raySteps = 512;
+        std::string vox, dense, out, raw, dumpPush, sky, noise, png, rays, hits; uint32_t raySteps = 512; bool segments = false;
         auto settings = std::make_shared<VoxelRenderSettings>();
         vec3 pos{8, 8, -50}; float yaw = 90, pitch = 0; bool havePos = false; int device = 0;
         std::vector<int> devices;                                          // --devices a,b,...: one process drives several GPUs
@@ -65,6 +66,7 @@ int run(int argc, char** argv)
             else if (a == "--raw") raw = next(); else if (a == "--dump-push") dumpPush = next();
             else if (a == "--sky") sky = next(); else if (a == "--noise") noise = next(); else if (a == "--png") png = next();
             else if (a == "--rays") rays = next(); else if (a == "--hits") hits = next(); else if (a == "--ray-steps") raySteps = (uint32_t)std::stoul(next());
+            else if (a == "--segments") segments = true;
             else if (a == "--width") settings->targetResolution[0] = (uint32_t)std::stoul(next());
             else if (a == "--height") settings->targetResolution[1] = (uint32_t)std::stoul(next());
             else if (a == "--pos") { pos.x = std::stof(next()); pos.y = std::stof(next()); pos.z = std::stof(next()); havePos = true; }
@@ -88,6 +90,7 @@ int run(int argc, char** argv)
             else if (a == "--fly") { flyForward = std::stof(next()); flyStrafe = std::stof(next()); flyMouseX = std::stof(next()); }
             else throw std::runtime_error("unknown argument " + a);
         }
+        if (segments && (rays.empty() || hits.empty())) throw std::runtime_error("--segments goes with --rays and --hits");
         if (!devices.empty() && !projection.empty()) throw std::runtime_error("--projection renders on one device (vrt_render_rays has no strips)");
         if (!devices.empty()) {
             // screen strips over the listed GPUs, RCCL gather to the first one (ShardedRenderer); the scene is loaded on each
@@ -121,15 +124,22 @@ int run(int argc, char** argv)
         if (!rays.empty() || !hits.empty()) {
             if (rays.empty() || hits.empty()) throw std::runtime_error("--rays and --hits go together");
             const std::vector<uint8_t> in = readFile(rays);
-            if (in.size() % 24) throw std::runtime_error(rays + ": not a whole number of rays (6 float32 each)");
-            const size_t n = in.size() / 24;
-            std::vector<float> o(3 * n), d(3 * n);
-            for (size_t i = 0; i < n; i++) { memcpy(&o[3 * i], &in[24 * i], 12); memcpy(&d[3 * i], &in[24 * i + 12], 12); }
-            const VoxelScene::RayHits h = scene->traceRays(o, d, raySteps);
-            std::vector<uint8_t> rec(28 * n);
+            const size_t inRec = segments ? 28 : 24, outRec = segments ? 32 : 28;
+            if (in.size() % inRec) throw std::runtime_error(rays + ": not a whole number of rays (" + std::to_string(inRec / 4) + " float32 each)");
+            const size_t n = in.size() / inRec;
+            std::vector<float> o(3 * n), d(3 * n), tMax(segments ? n : 0);
             for (size_t i = 0; i < n; i++) {
-                uint8_t* r = &rec[28 * i];
+                memcpy(&o[3 * i], &in[inRec * i], 12); memcpy(&d[3 * i], &in[inRec * i + 12], 12);
+                if (segments) memcpy(&tMax[i], &in[inRec * i + 24], 4);
+            }
+            VoxelScene::SegmentHits sh;
+            if (segments) sh = scene->traceSegments(o, d, tMax, raySteps); else sh.hits = scene->traceRays(o, d, raySteps);
+            const VoxelScene::RayHits& h = sh.hits;
+            std::vector<uint8_t> rec(outRec * n);
+            for (size_t i = 0; i < n; i++) {
+                uint8_t* r = &rec[outRec * i];
                 r[0] = h.material[i]; memcpy(r + 1, &h.pos[3 * i], 12); memcpy(r + 13, &h.voxel[3 * i], 12); memcpy(r + 25, &h.normal[3 * i], 3);
+                if (segments) memcpy(r + 28, &sh.t[i], 4);
             }
             std::ofstream f(hits, std::ios::binary);
             if (!f.write((const char*)rec.data(), (std::streamsize)rec.size())) throw std::runtime_error("cannot write " + hits);

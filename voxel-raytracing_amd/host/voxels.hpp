@@ -188,6 +188,46 @@ public:
         check(vrt_occluded_rays(engine->ctx, handle, (int64_t)n, o.ptr, d.ptr, maxSteps, occ.ptr));
         return occ.download();
     }
+    // Ray segments (vrt_trace_segments / vrt_occluded_segments): the same with a distance limit per ray, tMax[i] in units of ray i's
+    // direction; a hit is kept iff its parameter t <= tMax[i], one that is not is a miss (0 in every plane and in t).
+    struct SegmentHits { RayHits hits; std::vector<float> t; };
+    SegmentHits traceSegments(const std::vector<float>& origins, const std::vector<float>& dirs, const std::vector<float>& tMax, uint32_t maxSteps = 512)
+    {
+        if (origins.size() != dirs.size() || origins.size() % 3 || tMax.size() * 3 != origins.size())
+            throw std::runtime_error("traceSegments: origins and dirs hold 3 floats per ray, tMax one");
+        const size_t n = tMax.size();
+        if (n == 0) return SegmentHits{};
+        DeviceBuffer<float> o(engine, 3 * n), d(engine, 3 * n), tm(engine, n), t(engine, n);
+        check(vrt_memcpy_h2d(engine->ctx, o.ptr, origins.data(), 12 * n)); check(vrt_memcpy_h2d(engine->ctx, d.ptr, dirs.data(), 12 * n));
+        check(vrt_memcpy_h2d(engine->ctx, tm.ptr, tMax.data(), 4 * n));
+        HitPlanes h(engine, n);
+        check(vrt_trace_segments(engine->ctx, handle, (int64_t)n, o.ptr, d.ptr, tm.ptr, maxSteps, &h.c, t.ptr));
+        return SegmentHits{h.download(), t.download()};
+    }
+    std::vector<uint8_t> occluded(const std::vector<float>& origins, const std::vector<float>& dirs, const std::vector<float>& tMax, uint32_t maxSteps = 512)
+    {
+        if (origins.size() != dirs.size() || origins.size() % 3 || tMax.size() * 3 != origins.size())
+            throw std::runtime_error("occluded: origins and dirs hold 3 floats per ray, tMax one");
+        const size_t n = tMax.size();
+        if (n == 0) return {};
+        DeviceBuffer<float> o(engine, 3 * n), d(engine, 3 * n), tm(engine, n);
+        check(vrt_memcpy_h2d(engine->ctx, o.ptr, origins.data(), 12 * n)); check(vrt_memcpy_h2d(engine->ctx, d.ptr, dirs.data(), 12 * n));
+        check(vrt_memcpy_h2d(engine->ctx, tm.ptr, tMax.data(), 4 * n));
+        DeviceBuffer<uint8_t> occ(engine, n);
+        check(vrt_occluded_segments(engine->ctx, handle, (int64_t)n, o.ptr, d.ptr, tm.ptr, maxSteps, occ.ptr));
+        return occ.download();
+    }
+    // Line of sight for point pairs: 1 where no voxel lies between a[i] and b[i] -- origin a, direction b - a (fp32), tMax = 1.  Inherited
+    // from boxIntersection: for a outside the volume the ray is advanced 0.1 * |b - a| voxels past the face it enters through.
+    std::vector<uint8_t> visible(const std::vector<float>& a, const std::vector<float>& b, uint32_t maxSteps = 512)
+    {
+        if (a.size() != b.size() || a.size() % 3) throw std::runtime_error("visible: a and b hold 3 floats per point");
+        std::vector<float> d(a.size());
+        for (size_t i = 0; i < a.size(); i++) d[i] = b[i] - a[i];
+        std::vector<uint8_t> v = occluded(a, d, std::vector<float>(a.size() / 3, 1.0f), maxSteps);
+        for (uint8_t& x : v) x = x ? 0 : 1;
+        return v;
+    }
     // xy: (x, y) per pixel; record i is what a frame rendered with `push` holds at pixel i
     RayHits pick(const vrt_push& push, const std::vector<int32_t>& xy, uint32_t maxSteps = 512)
     {

@@ -396,6 +396,15 @@ static bool count_planes(const Launch& l)
     return counts;
 }
 
+// floor(2^32 / d) for udiv_uniform (vrt_frame_slot.h), d >= 1.  For d = 1 that is 2^32, which a word does not hold -- as 0 the
+// quotient came out as 1 for every n >= 2 (a frame one tile wide in a launch of nine frames or more: frames 8 .. were never
+// traced); 2^32 - 1 gives n - 1 before the correction step and n after it.
+static uint32_t uniform_rcp(uint32_t d)
+{
+    const uint64_t r = 0x100000000ull / (uint64_t)d;
+    return r > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)r;
+}
+
 // The launch plan: every kernel variant, the grid and the tile map, from the context's options, the scene, the settings and the
 // frames.  No HIP call and nothing of the context: what a launch takes from there (slots, records, tags, the colour table) the
 // later steps put in.  count_fields: what fields_for_counts gave, or NULL; div_ok: screen_div_ok.
@@ -441,7 +450,7 @@ static int launch_plan(const DevOptions& opt, const vrt_scene* s, const Launch& 
     p.chunk = p.tiles_x * ceil_div(p.tiles_y_local, 8);      // workgroups per XCD slot (tile rows are dealt round-robin)
     p.wgs_per_frame = (uint32_t)p.chunk * 8u;
     p.xcd_turn = (n > 1 && p.tiles_y_local > 0 && ceil_div(p.tiles_y_local, 8) * 8 * 100 > p.tiles_y_local * 103) ? 1 : 0;
-    p.wgs_per_frame_rcp = p.wgs_per_frame ? (uint32_t)(0x100000000ull / (uint64_t)p.wgs_per_frame) : 0u;
+    p.wgs_per_frame_rcp = p.wgs_per_frame ? uniform_rcp((uint32_t)p.wgs_per_frame) : 0u;
     // launches of 8 or more unsharded frames: one screen region per XCD and frame, rotating (block_to_tile, xcd_turn == 2)
     {
         const bool want = opt.xcd_regions != 0;                          // development switch
@@ -449,14 +458,14 @@ static int launch_plan(const DevOptions& opt, const vrt_scene* s, const Launch& 
             const uint32_t rw = ((uint32_t)p.tiles_x + 1u) / 2u, rh = ((uint32_t)p.tiles_y_local + 3u) / 4u;
             p.xcd_turn = 2;
             p.wgs_per_frame = rw * rh;
-            p.wgs_per_frame_rcp = (uint32_t)(0x100000000ull / (uint64_t)p.wgs_per_frame);
-            p.tiles_y_rcp = (uint32_t)(0x100000000ull / (uint64_t)rw);
+            p.wgs_per_frame_rcp = uniform_rcp((uint32_t)p.wgs_per_frame);
+            p.tiles_y_rcp = uniform_rcp((uint32_t)rw);
         }
     }
     p.tps = (uint32_t)(p.sh.strip_rows / p.tile_h);
-    p.tiles_x_rcp = (uint32_t)(0x100000000ull / (uint64_t)p.tiles_x);
-    if (p.xcd_turn != 2) p.tiles_y_rcp = p.tiles_y_local ? (uint32_t)(0x100000000ull / (uint64_t)p.tiles_y_local) : 0u;
-    p.tps_rcp = (uint32_t)(0x100000000ull / (uint64_t)p.tps);
+    p.tiles_x_rcp = uniform_rcp((uint32_t)p.tiles_x);
+    if (p.xcd_turn != 2) p.tiles_y_rcp = p.tiles_y_local ? uniform_rcp((uint32_t)p.tiles_y_local) : 0u;
+    p.tps_rcp = uniform_rcp((uint32_t)p.tps);
     // 1: nothing but primary rays; 2: megakernel (default); 0: split K1 -> records -> K2 (VRT_FLAG_SPLIT_KERNELS)
     p.fused_shade = (st->ao_samples == 0 && st->shadows == 0 && (st->max_bounces == 0 || !s->metallic_voxels)) ? 1 : ((st->flags & VRT_FLAG_SPLIT_KERNELS) ? 0 : 2);
     p.no_bounce = ((st->max_bounces == 0 || !s->metallic_voxels) && opt.no_bounce_kernel) ? 1 : 0;
@@ -564,10 +573,25 @@ static int launch_tags(vrt_ctx* c, const vrt_scene* s, const Launch& l, const Fr
         c->tile_gen = 1u;
     }
     p.tile_tags = c->tile_tags[b].get(); p.tile_gen = c->tile_gen;
+    // Block verdicts for the primary-only kernels of table launches (k_block_verdicts, vrt_span.h): buffer b beside tag buffer b,
+    // made behind the tags on whichever stream they are made on -- with or without tags, with or without the span path.  Launches
+    // with their slots in the kernel arguments go without: their kernels work the verdicts out per wave, as before.
+    if (p.fused_shade == 1 && p.table) {
+        const size_t bytes = (size_t)vrt::verdict_pitch((uint32_t)(p.tiles_x * (p.tile_w / 8))) * (size_t)(p.tiles_y_local * (p.tile_h / 8)) * (size_t)n;
+        if (c->verdict_bytes[b] < bytes) {
+            HIPCHK(hipStreamSynchronize(c->stream));
+            if (c->tag_stream) HIPCHK(hipStreamSynchronize(c->tag_stream));
+            c->verdicts[b].reset(); c->verdict_bytes[b] = 0;
+            HIPCHK(c->verdicts[b].alloc(bytes));
+            c->verdict_bytes[b] = bytes;
+        }
+        p.verdicts = c->verdicts[b].get();
+    }
     if (!tags) {
         // every frame's one word = tile_gen
         std::vector<uint32_t> ones((size_t)n, c->tile_gen);
         HIPCHK(hipMemcpyAsync(c->tile_tags[b].get(), ones.data(), (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(launch_block_verdicts(p, c->stream));
         return VRT_OK;
     }
     p.cells = s->cells.get(); p.n_cells = s->n_cells; p.cell_size = s->bricks ? 8u : 4u;
@@ -579,6 +603,7 @@ static int launch_tags(vrt_ctx* c, const vrt_scene* s, const Launch& l, const Fr
     const bool async = c->opt.tags_async >= 2 || (c->opt.tags_async != 0 && hipStreamQuery(c->stream) == hipErrorNotReady);
     if (!async) {
         HIPCHK(launch_tile_tags(p, c->stream));
+        HIPCHK(launch_block_verdicts(p, c->stream));
         return VRT_OK;
     }
     if (!c->tag_stream) {
@@ -595,6 +620,7 @@ static int launch_tags(vrt_ctx* c, const vrt_scene* s, const Launch& l, const Fr
     if (c->tag_read_valid[b]) HIPCHK(hipStreamWaitEvent(c->tag_stream, c->tag_read[b], 0));     // the launch that last read this buffer
     if (tab >= 0) HIPCHK(hipStreamWaitEvent(c->tag_stream, c->tab_uploaded[tab], 0));            // the slots the tag kernel reads
     HIPCHK(launch_tile_tags(p, c->tag_stream));
+    HIPCHK(launch_block_verdicts(p, c->tag_stream));
     HIPCHK(hipEventRecord(c->tag_done[b], c->tag_stream));
     HIPCHK(hipStreamWaitEvent(c->stream, c->tag_done[b], 0));
     return VRT_OK;

@@ -56,12 +56,24 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 8))) voi
     // at their own word of the four only.  The megakernels keep the four single loads -- the block's own four times over where
     // the span is cut or the launch has no span path, the frame's one word without tags: with the short form their packed bounce
     // chains spill a register more, 168 / 196 B per lane against budgets of 160 / 192, tools/check_resources.py)
-    constexpr bool kOneFetch = MODE == 1;
+    // (vrt_span.h block_verdict_byte: the primary-only kernels of TABLE launches fetch neither -- k_block_verdicts, launched behind
+    // k_tile_tags, has looked at the tags, the frame's word and the box rectangle for every block of the launch, and the wave reads
+    // the ONE word that holds its span's four bytes, with one scalar load that leaves with the slot's.  Launches with their slots
+    // in the kernel arguments -- eight frames at most, one in a frame loop -- keep the one-fetch form: there a kernel more ahead of
+    // K1 costs more than the shorter preamble of so few waves returns)
+    constexpr bool kVerdict = MODE == 1 && TABLE;
+    constexpr bool kOneFetch = MODE == 1 && !kVerdict;
     typedef uint32_t span_words __attribute__((ext_vector_type(4), aligned(4)));
     span_words st;
-    uint32_t tag_all, own, tag = 0u;
-    bool span_w, wide;
-    {
+    uint32_t tag_all = 0u, own = 0u, tag = 0u, vword = 0u, role = 0u;
+    bool span_w = false, wide = false;
+    if constexpr (kVerdict) {
+        const uint32_t sh = (uint32_t)M.tile >> 4;
+        const uint32_t row8 = ((uint32_t)ty << sh) + (uint32_t)(wave >> 1), col8 = ((uint32_t)tx << sh) + (uint32_t)(wave & 1);
+        role = span_role(col8);
+        const uint32_t pitch = verdict_pitch((uint32_t)M.tiles_x << sh);
+        vword = *(const_u32_ptr)((const __attribute__((address_space(4))) char*)P.verdicts + verdict_word(row8, col8, frame, (uint32_t)M.n_frames, pitch));
+    } else {
         const_u32_ptr tg = (const_u32_ptr)(P.tile_tags + (size_t)frame * P.tags_per_frame);
         const uint32_t tags_x = P.tags_x, sh = (uint32_t)M.tile >> 4;
         const uint32_t row8 = ((uint32_t)ty << sh) + (uint32_t)(wave >> 1), col8 = ((uint32_t)tx << sh) + (uint32_t)(wave & 1);
@@ -83,13 +95,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 8))) voi
     RayGenConsts g;
     float cam_right[3];
     int shard_rank;
-    uint32_t box;
-    SlotOf<TABLE>::head(P, frame, g, cam_right, shard_rank, box);
-    asm volatile("" : "+s"(box));
+    uint32_t box = 0u;
+    if constexpr (kVerdict) SlotOf<true>::head_no_box(P, frame, g, cam_right, shard_rank);
+    else {
+        SlotOf<TABLE>::head(P, frame, g, cam_right, shard_rank, box);
+        asm volatile("" : "+s"(box));
+    }
     // (one scalar from here on, not three: past 80 scalar registers a SIMD holds 7 of these waves, not 8)
     // (bit 0: the block has no tag; bit 1: its span may take the span path; bit 2: none of the span's blocks has a tag)
-    uint32_t untagged;
-    if (kOneFetch) untagged = (uint32_t)__builtin_amdgcn_readfirstlane((int)span_verdict(st.x, st.y, st.z, st.w, own, wide, span_w, tag_all, tile_gen));
+    uint32_t untagged = 0u;
+    if (kVerdict) {}
+    else if (kOneFetch) untagged = (uint32_t)__builtin_amdgcn_readfirstlane((int)span_verdict(st.x, st.y, st.z, st.w, own, wide, span_w, tag_all, tile_gen));
     else untagged = (uint32_t)__builtin_amdgcn_readfirstlane(((tag != tile_gen && tag_all != tile_gen) ? 1 : 0) | (span_w ? 2 : 0) |
                                                              (span_untagged(st.x, st.y, st.z, st.w, tag_all, tile_gen) ? 4 : 0));
     const uint4 boxr = make_uint4(box & 0xFFu, (box >> 8) & 0xFFu, (box >> 16) & 0xFFu, box >> 24);
@@ -115,11 +131,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 8))) voi
     // (ONE rectangle test for both questions -- the span's blocks share the 32-pixel column and the row -- and one scalar from
     // here on: bit 0: the block is a skip block, bit 1: so is every block of its span)
     uint32_t verdict = 0u;
+    if (kVerdict) verdict = (uint32_t)__builtin_amdgcn_readfirstlane((int)(vword >> verdict_shift(role)));
     if (kOneFetch) verdict = (uint32_t)__builtin_amdgcn_readfirstlane((int)span_decide(untagged, box, (uint32_t)px0, (uint32_t)py0));
-    const bool span = kOneFetch ? (verdict & 2u) != 0u
+    const bool span = (kVerdict || kOneFetch) ? (verdict & 2u) != 0u
                                 : (untagged & 2u) != 0u && block_skips(box, (uint32_t)px0 & ~31u, (uint32_t)py0, (untagged & 4u) != 0u);
     int px, py;
-    span_pixel(span, span ? (uint32_t)px0 & ~31u : (uint32_t)px0, (uint32_t)py0, span_role((uint32_t)px0 >> 3), (uint32_t)lane, px, py);
+    // (with a verdict the role is at hand as col8 & 3: not derived from the block's pixel column again)
+    span_pixel(span, span ? (uint32_t)px0 & ~31u : (uint32_t)px0, (uint32_t)py0, kVerdict ? role : span_role((uint32_t)px0 >> 3), (uint32_t)lane, px, py);
     int W = M.W, H = M.H;
     if (px >= W || py >= H) return;
     // (two vector registers from here on, whatever they were made from: without this the megakernels' register allocation
@@ -134,7 +152,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 8))) voi
     // a wave whose 8x8 pixels lie outside the frame's box rectangle (FrameSlot::box, vrt_internal.h box_rect) cannot meet the
     // volume: it writes what a miss writes without testing the box (wave-uniform: the rectangle is in units of 32 pixels) --
     // and inside the rectangle neither can a wave whose block no occupied 4^3 cell of the volume projects onto (k_tile_tags)
-    const bool skip = kOneFetch ? (verdict & 1u) != 0u
+    const bool skip = (kVerdict || kOneFetch) ? (verdict & 1u) != 0u
                                 : box != 0xFF00FF00u && ((uint32_t)(px0 >> 5) < boxr.x || (uint32_t)(px0 >> 5) >= boxr.y || (uint32_t)(py0 >> 5) < boxr.z ||
                                                          (uint32_t)(py0 >> 5) >= boxr.w || (untagged & 1u) != 0u);
     // ... and of everything normalize(), atan() and asin() compute for such a pixel only the sky TEXEL is ever seen: vrt_sky.h
@@ -393,7 +411,10 @@ template <int TRAV, bool OCC_LDS, bool TABLE>
 static hipError_t launch_k1(const GeomParams& p, dim3 grid, dim3 block, size_t lds, hipStream_t s)
 {
     constexpr bool kProduct = TRAV == VRT_TRAVERSAL_DF_FAST || TRAV == VRT_TRAVERSAL_DF_FAST_CNT || TRAV == VRT_TRAVERSAL_BRICK || TRAV == VRT_TRAVERSAL_BRICK_CNT;
-    if (p.fused_shade == 1) launch_k1_map<TRAV, OCC_LDS, 1, TABLE>(p, grid, block, lds, s);
+    if (p.fused_shade == 1) {
+        if (TABLE && !p.verdicts) return hipErrorInvalidValue;    // the primary-only kernels of table launches read their blocks' verdicts (k_block_verdicts)
+        launch_k1_map<TRAV, OCC_LDS, 1, TABLE>(p, grid, block, lds, s);
+    }
     else if (p.fused_shade == 2) {
         if (p.no_bounce) launch_k1_map<TRAV, OCC_LDS, 4, TABLE>(p, grid, block, lds, s);
         else if (kProduct && p.packed_chain) {
@@ -641,6 +662,49 @@ hipError_t launch_tile_tags(const GeomParams& p, hipStream_t s)
     dim3 grid((p.n_cells + 255u) / 256u, (unsigned)p.n_frames), block(256);
     if (p.table) hipLaunchKernelGGL(k_tile_tags<true>, grid, block, 0, s, p);
     else         hipLaunchKernelGGL(k_tile_tags<false>, grid, block, 0, s, p);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------
+// Block verdicts: what a wave of the primary-only kernels does with its block -- trace it, store the miss pixel of its 8x8 pixels,
+// or of two rows of its 32x8 span -- is a function of the block's tag, its span's, the frame's word and the frame's box rectangle
+// (vrt_span.h).  One lane per block of every frame of the launch works it out, once, behind the tag kernel on the tag kernel's
+// stream, and stores it as one byte (block_verdict_byte); K1's waves read the word their span's four bytes lie in.  The lanes of
+// a 64 x 4 workgroup are 64 neighbouring blocks of four rows: their byte stores are whole 64-byte pieces of a row.
+// ---------------------------------------------------------------------------------------------
+// (table launches only: the slots are read from the table)
+__global__ __launch_bounds__(256) void k_block_verdicts(const GeomParams P)
+{
+    const uint32_t frame = blockIdx.z, col8 = blockIdx.x * 64u + threadIdx.x, row8 = blockIdx.y * 4u + threadIdx.y;
+    const uint32_t k = (uint32_t)P.tile_h >> 3;                   // block rows per workgroup tile of K1 (1 or 2)
+    const uint32_t blocks_x = (uint32_t)P.tiles_x * ((uint32_t)P.tile_w >> 3), blocks_y = (uint32_t)P.tiles_y_local * k;
+    if (col8 >= blocks_x || row8 >= blocks_y) return;
+    int shard_rank;
+    uint32_t box;
+    SlotOf<true>::rank_box(P, frame, shard_rank, box);
+    // the block's first pixel row, as K1 finds it (tile_origin: tile rows in dispatch order, bottom rows first, strip by strip)
+    const uint32_t tyl = row8 / k, t = (uint32_t)P.tiles_y_local - 1u - tyl;
+    uint32_t strip_local = 0u, within = t;
+    if (P.sh.nranks > 1) { strip_local = t / P.tps; within = t - strip_local * P.tps; }
+    const uint32_t py0 = (strip_local * (uint32_t)P.sh.nranks + (uint32_t)shard_rank) * (uint32_t)P.sh.strip_rows + within * (uint32_t)P.tile_h + (row8 - tyl * k) * 8u;
+    // the span's four tags (vrt_span.h verdict_tag: a launch without tags, columns the row does not have)
+    const uint32_t* tg = P.tile_tags + (size_t)frame * P.tags_per_frame;
+    const uint32_t gen = P.tile_gen, tags_x = P.tags_x, tag_all = tg[P.tags_per_frame - 1u];
+    uint32_t tag[4];
+#pragma unroll
+    for (uint32_t j = 0; j < 4u; j++) tag[j] = verdict_tag(tg + row8 * tags_x, (col8 & ~3u) + j, tags_x, tag_all, gen);
+    const bool span_path = (P.map.flags & VRT_MAPFLAG_SKY_SPAN) != 0u;
+    P.verdicts[verdict_offset(row8, col8, frame, (uint32_t)P.n_frames, verdict_pitch(blocks_x))] =
+        (uint8_t)block_verdict_byte(tag[0], tag[1], tag[2], tag[3], col8, span_path, (uint32_t)P.W, tag_all, gen, box, py0);
+}
+
+hipError_t launch_block_verdicts(const GeomParams& p, hipStream_t s)
+{
+    const unsigned blocks_x = (unsigned)(p.tiles_x * (p.tile_w / 8)), blocks_y = (unsigned)(p.tiles_y_local * (p.tile_h / 8));
+    if (!p.verdicts || blocks_x == 0u || blocks_y == 0u) return hipSuccess;
+    if (!p.table) return hipErrorInvalidValue;
+    dim3 grid((blocks_x + 63u) / 64u, (blocks_y + 3u) / 4u, (unsigned)p.n_frames), block(64, 4);
+    hipLaunchKernelGGL(k_block_verdicts, grid, block, 0, s, p);
     return hipGetLastError();
 }
 

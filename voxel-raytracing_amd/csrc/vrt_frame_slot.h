@@ -120,6 +120,20 @@ template <> struct SlotOf<true> {
         table_read<3>(P, frame, offsetof(FrameSlot, pc) + offsetof(vrt_push, cam_right), cam_right);
         table_read<1>(P, frame, offsetof(FrameSlot, shard_rank), &shard_rank);
     }
+    // the head without the box word: a kernel that reads its block's verdict (GeomParams::verdicts; table launches only) has no
+    // use for the rectangle
+    static __device__ __forceinline__ void head_no_box(const GeomParams& P, uint32_t frame, RayGenConsts& g, float* cam_right, int& shard_rank)
+    {
+        table_read<sizeof(RayGenConsts) / 4>(P, frame, offsetof(FrameSlot, rg), &g);
+        table_read<3>(P, frame, offsetof(FrameSlot, pc) + offsetof(vrt_push, cam_right), cam_right);
+        table_read<1>(P, frame, offsetof(FrameSlot, shard_rank), &shard_rank);
+    }
+    // the strip assignment and the box word alone (k_block_verdicts)
+    static __device__ __forceinline__ void rank_box(const GeomParams& P, uint32_t frame, int& shard_rank, uint32_t& box)
+    {
+        table_read<1>(P, frame, offsetof(FrameSlot, shard_rank), &shard_rank);
+        table_read<1>(P, frame, offsetof(FrameSlot, box), &box);
+    }
     static __device__ __forceinline__ vrt_frame planes(const GeomParams& P, uint32_t frame)
     {
         vrt_frame f;

@@ -115,6 +115,11 @@ struct vrt_ctx {
     // land in the buffer launch N reads
     vrt::DevBuf<uint32_t> tile_tags[2];
     size_t tile_tags_words[2] = {0, 0};
+    // block verdicts (k_block_verdicts: one byte per block and frame, made from the tags behind them on the same stream): buffer b
+    // goes with tag buffer b, is filled and read under the same events.  Like the tags: allocated when a table launch first takes
+    // buffer b, grown (behind a synchronise of both streams) when a launch needs more, never shrunk, released with the context
+    vrt::DevBuf<uint8_t> verdicts[2];
+    size_t verdict_bytes[2] = {0, 0};
     uint32_t tile_gen = 0;
     int tag_flip = 0;
     hipStream_t tag_stream = nullptr;

@@ -209,7 +209,13 @@ struct GeomParams {
     // (k_hit_colors) whenever the settings or the scene's sky change, as the RGBA8 the colour target stores:
     // hit_colors[material << 6 | ncode].  nullptr: every pixel computes its own.
     const uint32_t* hit_colors;
+    // Block verdicts (k_block_verdicts, launched behind k_tile_tags; vrt_span.h block_verdict_byte): one byte per 8x8 block of every
+    // frame, in the launch's local block rows like the tags (vrt_span.h verdict_offset: the layout, from what the tile map holds).
+    // nullptr: the launch's kernel works its verdicts out itself (everything but the primary-only kernels of table launches).
+    // (behind every other field, in what was padding: the argument block keeps its size and every other kernel its machine code)
+    uint8_t*   verdicts;
 };
+static_assert(sizeof(GeomParams) == 2688, "GeomParams grew: every kernel that takes it changes (tools/kernel_digest.py)");
 
 #define VRT_DENOISE_SEGS 64    // counters of redone pixels (diagnostics): a workgroup adds to counter (its index % 64)
 struct DenoiseParams {
@@ -353,6 +359,7 @@ hipError_t debug_brick_counts(unsigned long long out[4]);
 hipError_t launch_debug_sky(const DevScene& sc, const float* v, size_t n, uint32_t* out, hipStream_t s);
 hipError_t launch_open_cells(const uint8_t* vox, int W, int H, int D, uint8_t* df, size_t stride, uint8_t* tmp0, uint8_t* tmp1, hipStream_t s, int mark = 0);
 hipError_t launch_tile_tags(const GeomParams& p, hipStream_t s);
+hipError_t launch_block_verdicts(const GeomParams& p, hipStream_t s);   // (nothing where p.verdicts is NULL)
 hipError_t launch_hit_colors(const GeomParams& p, uint32_t* table, hipStream_t s);
 hipError_t launch_pad_vox(const uint8_t* vox, int W, int H, int D, uint8_t* dst, hipStream_t s);
 // scene edits: the volume and the box [lo, hi) of it that is rewritten

@@ -94,6 +94,50 @@ VRT_HD uint32_t span_decide(uint32_t verdict, uint32_t box, uint32_t px0, uint32
     return (u & 1u) | ((u & 6u) == 6u ? 2u : 0u);
 }
 
+// ---- the same rule made ONCE per launch: one byte per block (k_block_verdicts, vrt_device.hip) ----
+// (tests/test_block_verdicts_cpu.py, through tests/native/verdict_host.cpp, proves that the byte is span_verdict + span_decide's
+// answer, and block_skips / span_eligible's, for every tag pattern, role, box and width.)
+//
+// Everything above is a function of (frame, block) and known once the tags are made, yet every wave of k_primary works it out
+// again on the scalar unit.  The primary-only kernels of table launches read it instead: bit 0: the block is a skip block (block_skips); bit 1: its
+// span is eligible (span_eligible) and the launch has the span path.  The bytes lie in the launch's LOCAL block rows like the tags,
+// rows padded to a multiple of four blocks: the four bytes of a span are one 4-byte-aligned word, which a wave fetches with one
+// scalar load and takes its own byte from.
+
+// Block row r of frame f of a launch of n_frames frames is row r * n_frames + f of the buffer: a wave finds its word from what the
+// tile map holds (its frame, the launch's n_frames and block columns) and the launch needs no stride of its own in the kernel
+// arguments -- the megakernels' argument block keeps its size and they their machine code.
+
+// bytes per row of blocks_x blocks
+VRT_HD uint32_t verdict_pitch(uint32_t blocks_x) { return (blocks_x + 3u) & ~3u; }
+// byte offset of block (row8, col8) of frame `frame`
+VRT_HD uint32_t verdict_offset(uint32_t row8, uint32_t col8, uint32_t frame, uint32_t n_frames, uint32_t pitch) { return (row8 * n_frames + frame) * pitch + col8; }
+// the bit a block's byte starts at within its span's word, from its role (span_role(col8))
+VRT_HD uint32_t verdict_shift(uint32_t role) { return role << 3; }
+// ... and the byte offset of the word that holds the byte
+VRT_HD uint32_t verdict_word(uint32_t row8, uint32_t col8, uint32_t frame, uint32_t n_frames, uint32_t pitch) { return verdict_offset(row8, col8 & ~3u, frame, n_frames, pitch); }
+
+// The tag of block column c as the verdict pass sees it.  row: the block row's tags (tags_x of them).  A launch without tags
+// (tags_x = 0) has the frame's one word, which holds tile_gen: nothing is untagged and the box alone decides.  A column the row
+// does not have is part of a span the frame's right edge cuts, which is not eligible whatever its tags: a value that is no tag.
+VRT_HD uint32_t verdict_tag(const uint32_t* row, uint32_t c, uint32_t tags_x, uint32_t tag_all, uint32_t tile_gen)
+{
+    return tags_x == 0u ? tag_all : (c < tags_x ? row[c] : ~tile_gen);
+}
+
+// The byte of the block at column col8 whose first pixel row is py0.  t0 .. t3: the tags of its span's four blocks (a block the
+// frame does not have: any value -- such a span is cut and not eligible); span_path: the launch has the span path; W: the
+// frame's width.
+VRT_HD uint32_t block_verdict_byte(uint32_t t0, uint32_t t1, uint32_t t2, uint32_t t3, uint32_t col8, bool span_path, uint32_t W,
+                                   uint32_t tag_all, uint32_t tile_gen, uint32_t box, uint32_t py0)
+{
+    const uint32_t own = span_role(col8);
+    const uint32_t tag = own == 0u ? t0 : (own == 1u ? t1 : (own == 2u ? t2 : t3));
+    const bool skip = block_skips(box, col8 << 3, py0, tag != tile_gen && tag_all != tile_gen);
+    const bool span = span_path && span_eligible(t0, t1, t2, t3, tag_all, tile_gen, box, span_x0(col8), py0, W);
+    return (skip ? 1u : 0u) | (span ? 2u : 0u);
+}
+
 // lane -> pixel.  span: role k of the span at (x0, py0) owns its rows 2k and 2k + 1; otherwise the 8x8 block at (x0, py0).
 // (the terms in front of the lane's are wave-uniform: the choice costs no vector instruction)
 VRT_HD void span_pixel(bool span, uint32_t x0, uint32_t py0, uint32_t role, uint32_t lane, int& px, int& py)

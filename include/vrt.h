@@ -280,6 +280,38 @@ int  vrt_image_write_pfm(const char* path, const float* pixels, uint32_t w, uint
 int  vrt_scene_info(const vrt_scene* sc, uint32_t dims[3]);
 /* Copy the dense volume / palette back to the host (tests, oracle comparison). */
 int  vrt_scene_download(vrt_ctx* ctx, const vrt_scene* sc, uint8_t* voxels, vrt_material palette[256]);
+/* Scene read-back (no reference analogue: the reference has no editor and never writes a scene).  The definitions -- box index,
+ * record, order, tiles -- are csrc/vrt_scene_read.h's; the file's are csrc/vox_writer.cpp's.  These work on dense scenes of every
+ * field layout and on brick scenes, reserved or not; they run on the context's stream and wait for it, like
+ * vrt_scene_download: a read enqueued after an edit sees the edit.  (Their context parameter is spelled `struct vrt_ctx*`, as
+ * vrt_trace_segments': the same type.)
+ * vrt_scene_read_box: the inverse of vrt_scene_edit_box.  ids: HOST pointer to size[0]*size[1]*size[2] bytes, x fastest, which
+ * receive the voxel ids of the box [lo, lo+size); an empty brick reads as zeros.  An empty box, a box that leaves the volume, a
+ * size whose byte count overflows size_t or a NULL argument: VRT_ERR_INVALID before any device work; a box for which no staging
+ * buffer can be allocated on the device: VRT_ERR_UNSUPPORTED (read it in parts). */
+int  vrt_scene_read_box(struct vrt_ctx* ctx, const vrt_scene* scene, const int32_t lo[3], const uint32_t size[3], uint8_t* ids);
+/* The non-empty voxels (id != 0) of a box whose sides are each at most 256, compacted on the device: one uint32 per voxel,
+ * (x-lo[0]) | (y-lo[1]) << 8 | (z-lo[2]) << 16 | id << 24, in ascending order of x + y*size[0] + z*size[0]*size[1] (relative
+ * coordinates) -- the order is part of the contract: the output is a function of the scene's content alone.  records: HOST
+ * pointer to `capacity` entries.  *count always receives the number of non-empty voxels; records == NULL (capacity ignored) only
+ * counts; capacity < *count writes nothing to records and returns VRT_ERR_INVALID with *count set.  The errors of
+ * vrt_scene_read_box, and a side above 256: VRT_ERR_INVALID.  Of a brick scene an empty brick costs one read of its grid word,
+ * and a box over empty bricks only launches nothing beyond those reads. */
+int  vrt_scene_list_box(struct vrt_ctx* ctx, const vrt_scene* scene, const int32_t lo[3], const uint32_t size[3],
+                        uint32_t* records, uint64_t capacity, uint64_t* count);
+/* A dense volume (x + y*W + z*W*H, dims = W, H, D, each 1..4096) and a palette as a MagicaVoxel .vox file in malloc'd host
+ * memory (release with vrt_host_free); host only, the counterpart of vrt_vox_flatten_host.  The scene is written in tiles of at
+ * most 256 voxels per axis, one model each (csrc/vox_writer.cpp has the layout).  A scene whose palette came from bytes -- every
+ * loaded .vox -- reads back exactly (dims, voxels, every palette float, every metallic value) through this library's loader and
+ * the reference's; ANY OTHER PALETTE IS QUANTISED: a colour channel becomes the byte whose pow(c/255, 2.2) is nearest (ties to
+ * the lower byte), and id 0's alpha reads back as 0.  A file beyond the 2^32 - 1 bytes a MAIN chunk can state:
+ * VRT_ERR_UNSUPPORTED. */
+int  vrt_vox_encode_host(const uint8_t* voxels, const uint32_t dims[3], const vrt_material palette[256], void** buf, size_t* n);
+/* The same file, byte for byte, of a scene on the device -- dense or bricks -- without ever holding its dense volume: per tile
+ * one vrt_scene_list_box, then the same serialiser (peak host memory: one tile's records plus the file).  _mem: *buf is
+ * released with vrt_host_free.  _file: writes to path; a file that cannot be written: VRT_ERR_IO. */
+int  vrt_scene_save_vox_mem (struct vrt_ctx* ctx, const vrt_scene* scene, void** buf, size_t* n);
+int  vrt_scene_save_vox_file(struct vrt_ctx* ctx, const vrt_scene* scene, const char* path);
 void vrt_scene_free(vrt_ctx* ctx, vrt_scene* sc);            /* VoxelScene::destroy */
 
 /* ---- settings -------------------------------------------------------------------------------- */

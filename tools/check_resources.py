@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Register budget of the hand-scheduled kernels (csrc: the parts of vrt_device.hip, vrt_denoise.hip, vrt_scene_edit.hip, vrt_query.hip, vrt_query_seg.hip, vrt_reproject.hip, vrt_reproject_cam.hip, vrt_upsample.hip, vrt_upsample_cam.hip, vrt_rays.hip, vrt_render_rays.hip), checked
+"""Register budget of the hand-scheduled kernels (csrc: the parts of vrt_device.hip, vrt_denoise.hip, vrt_scene_edit.hip, vrt_scene_read.hip, vrt_query.hip, vrt_query_seg.hip, vrt_reproject.hip, vrt_reproject_cam.hip, vrt_upsample.hip, vrt_upsample_cam.hip, vrt_rays.hip, vrt_render_rays.hip), checked
 at build time.
 
 K1's look-up loop pins physical registers and the kernel sits at two occupancy cliffs that the compiler's own remark does
@@ -54,6 +54,15 @@ BUDGET = {
     "k_bedit_writeENS_9BrickEditE": ("brick-scene edit: the box's ids into the pool bricks of T", 64, 96, 0),
     "k_bedit_extractENS_11BrickCoarseE": ("brick-scene edit: the occupancy of E as a lattice of its own", 64, 96, 0),
     "k_bedit_copyENS_11BrickCoarseE": ("brick-scene edit: R_o into the coarse fields", 64, 96, 0),
+    # scene read-back (vrt_scene_read.hip): gathers and a ballot per wave -- no register cliff to guard, none may spill (4 .. 28 VGPRs)
+    "k_read_boxILb0EE": ("scene read-back: a box of a dense scene into the staging buffer", 32, 48, 0),
+    "k_read_boxILb1EE": ("scene read-back: a box of a brick scene through the packed entries", 32, 48, 0),
+    "k_list_bricksENS_7ReadBoxE": ("scene read-back: occupied bricks under a box", 32, 64, 0),
+    "k_list_countILb0EE": ("scene read-back: non-empty voxels per segment, dense", 32, 48, 0),
+    "k_list_countILb1EE": ("scene read-back: non-empty voxels per segment, bricks", 32, 48, 0),
+    "k_list_scanEPjj": ("scene read-back: exclusive scan of the segments' counts", 32, 48, 0),
+    "k_list_scatterILb0EE": ("scene read-back: the records to their places, dense", 32, 48, 0),
+    "k_list_scatterILb1EE": ("scene read-back: the records to their places, bricks", 32, 48, 0),
     # ray queries (vrt_query.hip): k_query<TRAV, ANYHIT, PICK>; none may spill.  The closest-hit form over the look-up loop keeps the
     # ray's direction and first mapPos across the march for the hit record: seven waves per SIMD, the others eight
     "k_queryILi7ELb0ELb0EE": ("ray query, closest hit, look-up loop", 72, 80, 0),
@@ -105,7 +114,7 @@ BUDGET = {
 
 
 # the objects that hold budgeted kernels, as the Makefile builds them: (source, extra flags); slowest first
-OBJECTS = [("vrt_device.hip", ["-DVRT_K1_PART=%d" % n]) for n in (3, 0, 1, 2)] + [("vrt_denoise.hip", []), ("vrt_scene_edit.hip", []), ("vrt_query.hip", []), ("vrt_query_seg.hip", []),
+OBJECTS = [("vrt_device.hip", ["-DVRT_K1_PART=%d" % n]) for n in (3, 0, 1, 2)] + [("vrt_denoise.hip", []), ("vrt_scene_edit.hip", []), ("vrt_scene_read.hip", []), ("vrt_query.hip", []), ("vrt_query_seg.hip", []),
                                                                                      ("vrt_reproject.hip", []), ("vrt_reproject_cam.hip", []), ("vrt_upsample.hip", []), ("vrt_upsample_cam.hip", []), ("vrt_rays.hip", []),
                                                                                      ("vrt_render_rays.hip", [])]
 

@@ -130,6 +130,11 @@ SYMBOLS = {
     "vrt_image_write_pfm": (C.c_int, [C.c_char_p, _P, C.c_uint32, C.c_uint32, C.c_uint32]),
     "vrt_scene_info": (C.c_int, [_P, C.POINTER(C.c_uint32)]),
     "vrt_scene_download": (C.c_int, [_P, _P, _P, C.POINTER(Material)]),
+    "vrt_scene_read_box": (C.c_int, [_P, _P, C.POINTER(C.c_int32), C.POINTER(C.c_uint32), _P]),
+    "vrt_scene_list_box": (C.c_int, [_P, _P, C.POINTER(C.c_int32), C.POINTER(C.c_uint32), _P, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "vrt_vox_encode_host": (C.c_int, [_P, C.POINTER(C.c_uint32), C.POINTER(Material), C.POINTER(_P), C.POINTER(C.c_size_t)]),
+    "vrt_scene_save_vox_mem": (C.c_int, [_P, _P, C.POINTER(_P), C.POINTER(C.c_size_t)]),
+    "vrt_scene_save_vox_file": (C.c_int, [_P, _P, C.c_char_p]),
     "vrt_scene_free": (None, [_P, _P]),
     "vrt_settings_default": (None, [C.POINTER(Settings)]),
     "vrt_render_geometry": (C.c_int, [_P, _P, C.POINTER(Push), C.POINTER(Settings), C.POINTER(Frame), C.POINTER(Shard)]),

@@ -1,5 +1,6 @@
 // vrt_api_scene.hip -- the scenes of the C-ABI: construction (dense and bricks), sky and noise, memory, download, edits of dense
-// scenes and of reserved brick scenes.  Host code only; the kernels are vrt_scene_build.hip and vrt_scene_edit.hip.
+// scenes and of reserved brick scenes, read-back (a box, a box's non-empty voxels, the scene as a .vox file).  Host code only;
+// the kernels are vrt_scene_build.hip, vrt_scene_edit.hip and vrt_scene_read.hip.
 //
 // Call surface mirrored from the reference (paths relative to its root):
 //   VoxelScene ctor            source/voxels/resource/voxel_scene.cpp:33-133
@@ -11,7 +12,10 @@
 
 #include "image_io.h"
 #include "vox_reader.h"
+#include "vox_writer.h"
 #include "vrt_host.h"
+#define VRT_SCENE_READ_LAUNCHERS
+#include "vrt_scene_read.h"
 
 using namespace vrt;
 
@@ -777,6 +781,177 @@ int vrt_scene_download(vrt_ctx* c, const vrt_scene* s, uint8_t* voxels, vrt_mate
     HIPCHK(hipStreamSynchronize(c->stream));
     if (voxels) HIPCHK(hipMemcpy(voxels, s->vox.get(), (size_t)s->d.vol.W * s->d.vol.H * s->d.vol.D, hipMemcpyDeviceToHost));
     if (palette) HIPCHK(hipMemcpy(palette, s->palette.get(), 256 * sizeof(vrt_material), hipMemcpyDeviceToHost));
+    return VRT_OK;
+}
+
+} // extern "C"
+
+// ---- scene read-back (vrt_scene_read_box, vrt_scene_list_box, vrt_scene_save_vox_*; csrc/vrt_scene_read.h) -------------------
+
+namespace {
+
+// the box's checks, before any device work; *count: its voxels
+int read_box_checked(const vrt_scene* s, const int32_t lo[3], const uint32_t size[3], uint32_t max_side, const std::string& name, size_t* count)
+{
+    const int32_t dim[3] = {s->d.vol.W, s->d.vol.H, s->d.vol.D};
+    switch (read_box_check(dim, lo, size, max_side, count)) {
+    case READ_BOX_OK:       return VRT_OK;
+    case READ_BOX_EMPTY:    return fail(VRT_ERR_INVALID, name + ": the box is empty");
+    case READ_BOX_OVERFLOW: return fail(VRT_ERR_INVALID, name + ": the box's voxel count overflows size_t");
+    case READ_BOX_SIDE:     return fail(VRT_ERR_INVALID, name + ": a listed box has no side above " + std::to_string(max_side) + " (a record holds a coordinate in one byte)");
+    default:                return fail(VRT_ERR_INVALID, name + ": the box leaves the volume");
+    }
+}
+
+ReadBox read_box_of(const vrt_scene* s, const int32_t lo[3], const uint32_t size[3])
+{
+    const VolumeView& d = s->d.vol;
+    ReadBox b{};
+    b.vox = s->bricks ? nullptr : s->vox.get();
+    b.bentry = s->bentry.get(); b.bpool = s->bpool.get(); b.bcap = s->bcap;
+    b.W = d.W; b.H = d.H; b.pbx = d.pbx; b.pby = d.pby;
+    for (int a = 0; a < 3; a++) { b.lo[a] = lo[a]; b.size[a] = size[a]; }
+    return b;
+}
+
+// How many non-empty voxels the (checked) box has -> *total, and in `work` every segment's first record.  A box over empty
+// bricks only ends behind the bricks' entries.  Returns when the stream is done.
+int list_count(vrt_ctx* c, const ReadBox& b, DevBuf<uint32_t>& work, uint32_t* total)
+{
+    const uint32_t nseg = list_segments(b);
+    if (work.bytes() < ((size_t)nseg + 2u) * 4u) HIPCHK(work.alloc(((size_t)nseg + 2u) * 4u));
+    *total = 0;
+    if (!b.vox) {
+        uint32_t occupied = 0;
+        HIPCHK(launch_list_bricks(b, work.get() + nseg + 1u, c->stream));
+        HIPCHK(hipMemcpyAsync(&occupied, work.get() + nseg + 1u, 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        if (!occupied) return VRT_OK;
+    }
+    HIPCHK(launch_list_count(b, work.get(), c->stream));
+    HIPCHK(hipMemcpyAsync(total, work.get() + nseg, 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return VRT_OK;
+}
+
+// ... and its `total` (> 0) records to the host
+int list_fetch(vrt_ctx* c, const ReadBox& b, const DevBuf<uint32_t>& work, uint32_t total, DevBuf<uint32_t>& dev, uint32_t* records)
+{
+    if (dev.bytes() < (size_t)total * 4u) HIPCHK(dev.alloc((size_t)total * 4u));
+    HIPCHK(launch_list_scatter(b, work.get(), total, dev.get(), c->stream));
+    HIPCHK(hipMemcpyAsync(records, dev.get(), (size_t)total * 4u, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return VRT_OK;
+}
+
+// the scene as a .vox file: per tile one listing, then vox_writer.cpp's serialiser -- the dense volume is never held
+int scene_save_vox(vrt_ctx* c, const vrt_scene* s, std::vector<uint8_t>& file)
+{
+    HIPCHK(hipSetDevice(c->device));
+    const uint32_t dims[3] = {(uint32_t)s->d.vol.W, (uint32_t)s->d.vol.H, (uint32_t)s->d.vol.D};
+    std::vector<vrt_material> palette(256);
+    HIPCHK(hipMemcpyAsync(palette.data(), s->palette.get(), 256 * sizeof(vrt_material), hipMemcpyDeviceToHost, c->stream));
+    VoxWriter w;
+    w.begin(dims);
+    DevBuf<uint32_t> work, dev;
+    std::vector<uint32_t> rec;
+    for (uint32_t t = 0; t < w.tiles() && !w.too_big(); t++) {
+        int32_t lo[3]; uint32_t size[3], total = 0;
+        w.tile_box(t, lo, size);
+        const ReadBox b = read_box_of(s, lo, size);
+        int rc = list_count(c, b, work, &total);
+        if (rc != VRT_OK) return rc;
+        rec.resize(total);
+        if (total && (rc = list_fetch(c, b, work, total, dev, rec.data())) != VRT_OK) return rc;
+        w.tile(rec.data(), total);
+    }
+    HIPCHK(hipStreamSynchronize(c->stream));
+    std::string err;
+    const int rc = w.finish(palette.data(), err);
+    if (rc != VRT_OK) return fail(rc, "vrt_scene_save_vox: " + err);
+    file.swap(w.out);
+    return VRT_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int vrt_scene_read_box(struct vrt_ctx* c, const vrt_scene* s, const int32_t lo[3], const uint32_t size[3], uint8_t* ids)
+{
+    if (!c || !s || !lo || !size || !ids) return fail(VRT_ERR_INVALID, "vrt_scene_read_box: NULL argument");
+    size_t n = 0;
+    const int rc = read_box_checked(s, lo, size, 0, "vrt_scene_read_box", &n);
+    if (rc != VRT_OK) return rc;
+    HIPCHK(hipSetDevice(c->device));
+    DevBuf<uint8_t> stage;
+    if (stage.alloc(n) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(VRT_ERR_UNSUPPORTED, "vrt_scene_read_box: no device memory for a staging buffer of " + std::to_string(n) + " bytes; read the box in parts");
+    }
+    HIPCHK(launch_read_box(read_box_of(s, lo, size), stage.get(), c->stream));
+    HIPCHK(hipMemcpyAsync(ids, stage.get(), n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return VRT_OK;
+}
+
+int vrt_scene_list_box(struct vrt_ctx* c, const vrt_scene* s, const int32_t lo[3], const uint32_t size[3], uint32_t* records, uint64_t capacity,
+                       uint64_t* count)
+{
+    if (!c || !s || !lo || !size || !count) return fail(VRT_ERR_INVALID, "vrt_scene_list_box: NULL argument");
+    size_t n = 0;
+    int rc = read_box_checked(s, lo, size, VRT_LIST_MAX_SIDE, "vrt_scene_list_box", &n);
+    if (rc != VRT_OK) return rc;
+    HIPCHK(hipSetDevice(c->device));
+    const ReadBox b = read_box_of(s, lo, size);
+    DevBuf<uint32_t> work, dev;
+    uint32_t total = 0;
+    if ((rc = list_count(c, b, work, &total)) != VRT_OK) return rc;
+    *count = total;
+    if (!records || !total) return VRT_OK;
+    if (capacity < (uint64_t)total)
+        return fail(VRT_ERR_INVALID, "vrt_scene_list_box: the box has " + std::to_string(total) + " non-empty voxels and `records` room for " + std::to_string(capacity));
+    return list_fetch(c, b, work, total, dev, records);
+}
+
+int vrt_vox_encode_host(const uint8_t* voxels, const uint32_t dims[3], const vrt_material palette[256], void** buf, size_t* n)
+{
+    if (!voxels || !dims || !palette || !buf || !n) return fail(VRT_ERR_INVALID, "vrt_vox_encode_host: NULL argument");
+    for (int a = 0; a < 3; a++)
+        if (!dims[a] || dims[a] > 4096) return fail(VRT_ERR_INVALID, "vrt_vox_encode_host: each dimension must be in 1..4096");
+    std::vector<uint8_t> file; std::string err;
+    const int rc = vox_encode(voxels, dims, palette, file, err);
+    if (rc != VRT_OK) return fail(rc, "vrt_vox_encode_host: " + err);
+    void* p = malloc(file.size());
+    if (!p) return fail(VRT_ERR_INVALID, "out of host memory");
+    memcpy(p, file.data(), file.size());
+    *buf = p; *n = file.size();
+    return VRT_OK;
+}
+
+int vrt_scene_save_vox_mem(struct vrt_ctx* c, const vrt_scene* s, void** buf, size_t* n)
+{
+    if (!c || !s || !buf || !n) return fail(VRT_ERR_INVALID, "vrt_scene_save_vox_mem: NULL argument");
+    std::vector<uint8_t> file;
+    const int rc = scene_save_vox(c, s, file);
+    if (rc != VRT_OK) return rc;
+    void* p = malloc(file.size());
+    if (!p) return fail(VRT_ERR_INVALID, "out of host memory");
+    memcpy(p, file.data(), file.size());
+    *buf = p; *n = file.size();
+    return VRT_OK;
+}
+
+int vrt_scene_save_vox_file(struct vrt_ctx* c, const vrt_scene* s, const char* path)
+{
+    if (!c || !s || !path) return fail(VRT_ERR_INVALID, "vrt_scene_save_vox_file: NULL argument");
+    std::vector<uint8_t> file;
+    const int rc = scene_save_vox(c, s, file);
+    if (rc != VRT_OK) return rc;
+    FILE* f = fopen(path, "wb");
+    if (!f) return fail(VRT_ERR_IO, std::string("Could not write voxel scene ") + path);
+    const bool ok = fwrite(file.data(), 1, file.size(), f) == file.size();
+    if (fclose(f) != 0 || !ok) return fail(VRT_ERR_IO, std::string("Could not write voxel scene ") + path);
     return VRT_OK;
 }
 

@@ -439,6 +439,51 @@ class VoxelScene:
         self._raise(lib().vrt_scene_fill_box(self.engine.ctx, self.handle, (C.c_int32 * 3)(*[int(t) for t in lo]),
                                              (C.c_uint32 * 3)(*[int(t) for t in size]), int(id)))
 
+    # ---- read-back (vrt_scene_read_box, vrt_scene_list_box, vrt_scene_save_vox_*) ---------------------------------------
+    @staticmethod
+    def _box(lo, size):
+        if any(int(t) < 0 for t in size):
+            raise ValueError("VoxelScene: negative box size")
+        return (C.c_int32 * 3)(*[int(t) for t in lo]), (C.c_uint32 * 3)(*[int(t) for t in size])
+
+    def read(self, lo, size) -> np.ndarray:
+        """The voxel ids of the box lo .. lo + size, both (x, y, z) (vrt_scene_read_box): a uint8 array indexed [z, y, x], the
+        shape `edit` takes.  Dense scenes and brick scenes alike; an empty brick reads as zeros."""
+        clo, csz = self._box(lo, size)
+        out = np.empty((int(size[2]), int(size[1]), int(size[0])), dtype=np.uint8)
+        self._raise(lib().vrt_scene_read_box(self.engine.ctx, self.handle, clo, csz, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def count(self, lo, size) -> int:
+        """Non-empty voxels of a box with no side above 256 (vrt_scene_list_box without records)."""
+        clo, csz = self._box(lo, size)
+        n = C.c_uint64()
+        self._raise(lib().vrt_scene_list_box(self.engine.ctx, self.handle, clo, csz, None, 0, C.byref(n)))
+        return int(n.value)
+
+    def voxels(self, lo, size) -> np.ndarray:
+        """The non-empty voxels of a box with no side above 256 (vrt_scene_list_box): uint32 records
+        (x - lo[0]) | (y - lo[1]) << 8 | (z - lo[2]) << 16 | id << 24, in ascending order of x + y * size[0] + z * size[0] * size[1]."""
+        clo, csz = self._box(lo, size)
+        n = C.c_uint64()
+        out = np.empty(self.count(lo, size), dtype=np.uint32)
+        self._raise(lib().vrt_scene_list_box(self.engine.ctx, self.handle, clo, csz, out.ctypes.data_as(C.c_void_p) if out.size else None,
+                                             out.size, C.byref(n)))
+        assert int(n.value) == out.size
+        return out
+
+    def to_vox_bytes(self) -> bytes:
+        """The scene as a MagicaVoxel .vox file (vrt_scene_save_vox_mem).  A palette that did not come from bytes is quantised."""
+        buf, n = C.c_void_p(), C.c_size_t()
+        self._raise(lib().vrt_scene_save_vox_mem(self.engine.ctx, self.handle, C.byref(buf), C.byref(n)))
+        data = C.string_at(buf, n.value)
+        lib().vrt_host_free(buf)
+        return data
+
+    def save(self, path) -> None:
+        """Write the scene as it stands to a .vox file (vrt_scene_save_vox_file)."""
+        self._raise(lib().vrt_scene_save_vox_file(self.engine.ctx, self.handle, os.fsencode(path)))
+
     # ---- ray queries (vrt_trace_rays, vrt_occluded_rays, vrt_pick_pixels) ----------------------------------------------
     RAY_PLANES = {"material": (np.uint8, 1), "pos": (np.float32, 3), "voxel": (np.int32, 3), "normal": (np.int8, 3)}
 
@@ -713,6 +758,21 @@ def vox_flatten_host(buf: bytes):
     arr = np.ctypeslib.as_array(C.cast(vox, C.POINTER(C.c_uint8)), shape=(D * H * W,)).copy().reshape(D, H, W)
     lib().vrt_host_free(vox)
     return arr, materials_to_numpy(pal), ninst.value, dropped.value
+
+
+def vox_encode_host(voxels: np.ndarray, palette: np.ndarray) -> bytes:
+    """Host-only .vox writer (no device; vrt_vox_encode_host): voxels uint8 [z, y, x], palette (256, 5) float32.  The inverse of
+    vox_flatten_host for palettes that came from bytes; any other palette is quantised."""
+    v = np.ascontiguousarray(voxels, dtype=np.uint8)
+    if v.ndim != 3:
+        raise ValueError("vox_encode_host: voxels must be indexed [z, y, x]")
+    D, H, W = v.shape
+    buf, n = C.c_void_p(), C.c_size_t()
+    VoxelScene._raise(lib().vrt_vox_encode_host(v.ctypes.data_as(C.c_void_p), (C.c_uint32 * 3)(W, H, D), materials_from_numpy(palette),
+                                                C.byref(buf), C.byref(n)))
+    data = C.string_at(buf, n.value)
+    lib().vrt_host_free(buf)
+    return data
 
 
 # --------------------------------------------------------------------------------------------------

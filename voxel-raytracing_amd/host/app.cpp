@@ -8,6 +8,10 @@
 // --pos / --yaw / --pitch basis, then vrt_render_rays) instead of the built-in 90-degree pinhole; with --temporal it needs --reproject
 // (the history is then kept by vrt_reproject_camera, with --upsample too at display resolution by vrt_upsample_camera); not with
 // --devices.
+// --fill X Y Z SX SY SZ ID (repeatable): the box is filled with ID (0 carves) before anything else looks at the scene
+// (VoxelScene::fill).  --save-vox OUT: the scene as it stands after that is written as a MagicaVoxel file (VoxelScene::save).
+// --read-box X Y Z SX SY SZ OUT: the ids of the box, x fastest, raw bytes (VoxelScene::read).  With either and no image output
+// (--out, --raw, --png) no frame is rendered.
 // Errors propagate as exceptions to run(), are printed, and the process exits with EXIT_FAILURE.
 #include <cstdio>
 #include <cstdlib>
@@ -59,6 +63,8 @@ int run(int argc, char** argv)
         std::vector<int> devices;                                          // --devices a,b,...: one process drives several GPUs
         int frames = 1; uint32_t windowW = 0, windowH = 0; float flyForward = 0, flyStrafe = 0, flyMouseX = 0; bool temporal = false, reproject = false, upsample = false;
         std::string dumpPushes, projection; std::vector<vrt_push> allPushes;
+        struct Box { std::array<int32_t, 3> lo; std::array<uint32_t, 3> size; uint8_t id; };
+        std::vector<Box> fills; Box readBox{}; std::string saveVox, readBoxOut;
         for (int i = 1; i < argc; i++) {
             std::string a = argv[i];
             auto next = [&]() { if (i + 1 >= argc) throw std::runtime_error("missing value for " + a); return std::string(argv[++i]); };
@@ -67,6 +73,13 @@ int run(int argc, char** argv)
             else if (a == "--sky") sky = next(); else if (a == "--noise") noise = next(); else if (a == "--png") png = next();
             else if (a == "--rays") rays = next(); else if (a == "--hits") hits = next(); else if (a == "--ray-steps") raySteps = (uint32_t)std::stoul(next());
             else if (a == "--segments") segments = true;
+            else if (a == "--fill" || a == "--read-box") {
+                Box b{};
+                for (int k = 0; k < 3; k++) b.lo[(size_t)k] = std::stoi(next());
+                for (int k = 0; k < 3; k++) b.size[(size_t)k] = (uint32_t)std::stoul(next());
+                if (a == "--fill") { b.id = (uint8_t)std::stoul(next()); fills.push_back(b); } else { readBox = b; readBoxOut = next(); }
+            }
+            else if (a == "--save-vox") saveVox = next();
             else if (a == "--width") settings->targetResolution[0] = (uint32_t)std::stoul(next());
             else if (a == "--height") settings->targetResolution[1] = (uint32_t)std::stoul(next());
             else if (a == "--pos") { pos.x = std::stof(next()); pos.y = std::stof(next()); pos.z = std::stof(next()); havePos = true; }
@@ -121,6 +134,17 @@ int run(int argc, char** argv)
         else scene = std::make_shared<VoxelScene>(engine, vox.empty() ? settings->voxPath : vox);
         if (!sky.empty()) scene->setSkybox(sky);
         if (!noise.empty()) scene->setBlueNoise(noise);
+        for (const Box& b : fills) scene->fill(b.lo, b.size, b.id);
+        if (!saveVox.empty()) scene->save(saveVox);
+        if (!readBoxOut.empty()) {
+            const std::vector<uint8_t> ids = scene->read(readBox.lo, readBox.size);
+            std::ofstream f(readBoxOut, std::ios::binary);
+            if (!f.write((const char*)ids.data(), (std::streamsize)ids.size())) throw std::runtime_error("cannot write " + readBoxOut);
+        }
+        if ((!saveVox.empty() || !readBoxOut.empty()) && out.empty() && raw.empty() && png.empty() && rays.empty() && hits.empty()) {
+            std::printf("scene %ux%ux%u written\n", scene->width, scene->height, scene->depth);
+            return EXIT_SUCCESS;
+        }
         if (!rays.empty() || !hits.empty()) {
             if (rays.empty() || hits.empty()) throw std::runtime_error("--rays and --hits go together");
             const std::vector<uint8_t> in = readFile(rays);

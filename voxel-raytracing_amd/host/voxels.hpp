@@ -158,6 +158,25 @@ public:
     void edit(const std::array<int32_t, 3>& lo, const std::array<uint32_t, 3>& size, const uint8_t* ids) { check(vrt_scene_edit_box(engine->ctx, handle, lo.data(), size.data(), ids)); }
     void fill(const std::array<int32_t, 3>& lo, const std::array<uint32_t, 3>& size, uint8_t id) { check(vrt_scene_fill_box(engine->ctx, handle, lo.data(), size.data(), id)); }
     // A brick scene becomes editable, with room for `capacity` bricks in its pool (vrt_scene_reserve_bricks); edit / fill then work on it
+    // Read-back (no reference analogue; vrt_scene_read_box / vrt_scene_list_box / vrt_scene_save_vox_file).  read: the ids of the
+    // box [lo, lo + size), x fastest -- what edit takes.  voxels: the box's non-empty voxels (no side above 256), one word each,
+    // x | y << 8 | z << 16 | id << 24 relative to lo, in ascending order of x + y * size[0] + z * size[0] * size[1].  save: the scene
+    // as it stands as a MagicaVoxel file (a palette that did not come from bytes is quantised).
+    std::vector<uint8_t> read(const std::array<int32_t, 3>& lo, const std::array<uint32_t, 3>& size) const
+    {
+        std::vector<uint8_t> ids((size_t)size[0] * size[1] * size[2]);
+        check(vrt_scene_read_box(engine->ctx, handle, lo.data(), size.data(), ids.data()));
+        return ids;
+    }
+    std::vector<uint32_t> voxels(const std::array<int32_t, 3>& lo, const std::array<uint32_t, 3>& size) const
+    {
+        uint64_t n = 0;
+        check(vrt_scene_list_box(engine->ctx, handle, lo.data(), size.data(), nullptr, 0, &n));
+        std::vector<uint32_t> rec((size_t)n);
+        if (n) check(vrt_scene_list_box(engine->ctx, handle, lo.data(), size.data(), rec.data(), n, &n));
+        return rec;
+    }
+    void save(const std::string& path) const { check(vrt_scene_save_vox_file(engine->ctx, handle, path.c_str())); }
     void reserveBricks(uint32_t capacity) { check(vrt_scene_reserve_bricks(engine->ctx, handle, capacity)); }
     void setSkybox(const float* rgba, uint32_t w, uint32_t h) { check(vrt_scene_set_sky(engine->ctx, handle, rgba, w, h)); }
     void setSkybox(const std::string& path) { check(vrt_scene_set_sky_file(engine->ctx, handle, path.c_str())); }          // Texture2D(.hdr)

@@ -312,6 +312,59 @@ int  vrt_vox_encode_host(const uint8_t* voxels, const uint32_t dims[3], const vr
  * released with vrt_host_free.  _file: writes to path; a file that cannot be written: VRT_ERR_IO. */
 int  vrt_scene_save_vox_mem (struct vrt_ctx* ctx, const vrt_scene* scene, void** buf, size_t* n);
 int  vrt_scene_save_vox_file(struct vrt_ctx* ctx, const vrt_scene* scene, const char* path);
+/* Scene brushes and stamps (no reference analogue): an edit whose ids are composed ON THE DEVICE -- paint a sphere, drag a
+ * capsule, recolour what is solid, fill what is empty, replace one material, paste a box of one scene into another -- and which
+ * rebuilds around the TIGHT box of the voxels that really change, not around the shape's bounds.  csrc/vrt_brush.h is the
+ * definition: plain integer arithmetic, no floating point, so which voxels a brush covers is the same on every machine.
+ * Shape positions are in HALF VOXELS: the centre of voxel (x, y, z) is (2x+1, 2y+1, 2z+1), so a brush can be centred on a voxel
+ * or on a voxel corner.  vrt_brush::p per shape:
+ *   VRT_BRUSH_BOX        p[0..2] = lo, p[3..5] = size, in VOXELS; lo may be negative, each size in 1..2^30
+ *   VRT_BRUSH_ELLIPSOID  p[0..2] = centre, p[3..5] = semi-axes, half voxels, each semi-axis in 1..1024 (a sphere: all equal;
+ *                        (1, 1, 1) centred on a voxel: that voxel)
+ *   VRT_BRUSH_CAPSULE    p[0..2] = a, p[3..5] = b, p[6] = radius, half voxels; radius in 1..1024, every coordinate of a and b in
+ *                        -4096..12288; a == b is a sphere
+ * (the rest of p is ignored).  A voxel INSIDE the shape becomes: VRT_BRUSH_SET id (0 carves); VRT_BRUSH_PAINT id where it was
+ * not empty (id != 0); VRT_BRUSH_ADD id where it was empty (id != 0); VRT_BRUSH_REPLACE id where it was `match` (id != match).
+ * A brush that lies partly outside the volume covers what is inside, and one that lies wholly outside changes nothing and is
+ * VRT_OK -- unlike vrt_scene_edit_box, which refuses a box that leaves the volume.
+ * result (may be NULL): how many voxels changed their id and the tight box that holds them (zeros when none did).  When
+ * changed > 0 the scene is afterwards exactly what vrt_scene_edit_box(result.lo, result.size, the box's new ids) leaves, every
+ * structure byte for byte a fresh build's.  When changed == 0 -- PAINT over air, REPLACE of an id that is not there, SET of the
+ * id already there, a brush outside the volume -- nothing is written, no edit pass runs and the count planes' second set of
+ * fields is NOT dropped.  Works on dense scenes of every field layout and on brick scenes after vrt_scene_reserve_bricks (before:
+ * VRT_ERR_UNSUPPORTED; an edit that needs more slots than are free: VRT_ERR_UNSUPPORTED and nothing changed, as
+ * vrt_scene_edit_box).  A NULL argument, an unknown shape or mode, a parameter outside its range or a broken id condition:
+ * VRT_ERR_INVALID before any device work.  Stream rules and the metallic rule are vrt_scene_edit_box's (the ids actually written
+ * decide, not the ids a shape could have written). */
+#define VRT_BRUSH_BOX       0
+#define VRT_BRUSH_ELLIPSOID 1
+#define VRT_BRUSH_CAPSULE   2
+#define VRT_BRUSH_SET       0
+#define VRT_BRUSH_PAINT     1
+#define VRT_BRUSH_ADD       2
+#define VRT_BRUSH_REPLACE   3
+typedef struct vrt_brush {
+    int32_t shape, mode;
+    int32_t p[9];
+    uint8_t id, match;
+} vrt_brush;
+typedef struct vrt_brush_result {
+    uint64_t changed;
+    int32_t  lo[3];
+    uint32_t size[3];    /* tight box of the changed voxels; zeros when changed == 0 */
+} vrt_brush_result;
+int  vrt_scene_brush(struct vrt_ctx* ctx, vrt_scene* scene, const vrt_brush* brush, vrt_brush_result* result);
+/* Paste the box [src_lo, src_lo+size) of src into dst.  The source box must lie inside src and have no side above 512
+ * (VRT_ERR_INVALID: stamp in parts); src may be dense or bricks (reserved or not), on the same device, and may be dst itself: the
+ * source is gathered before anything is written, so an overlapping stamp copies the OLD content.  orient = perm | flips << 3
+ * (the 48 symmetries of the box, 0 = identity): perm 0..5 = which source axis feeds destination x, y, z -- xyz, xzy, yxz, yzx,
+ * zxy, zyx -- and bit a of flips reverses destination axis a (csrc/vrt_brush.h: stamp_source).  The oriented box is placed with
+ * its low corner at dst_lo, which may be negative, and clipped to dst.  flags: VRT_STAMP_SKIP_EMPTY leaves the destination voxel
+ * as it is where the source id is 0.  Ids are copied verbatim; the palettes are not compared.  Result, no-op rule, brick scenes
+ * and errors as vrt_scene_brush. */
+#define VRT_STAMP_SKIP_EMPTY 1u
+int  vrt_scene_stamp(struct vrt_ctx* ctx, vrt_scene* dst, const int32_t dst_lo[3], const vrt_scene* src, const int32_t src_lo[3],
+                     const uint32_t size[3], uint32_t orient, uint32_t flags, vrt_brush_result* result);
 void vrt_scene_free(vrt_ctx* ctx, vrt_scene* sc);            /* VoxelScene::destroy */
 
 /* ---- settings -------------------------------------------------------------------------------- */

@@ -1,0 +1,64 @@
+// Host build of csrc/vrt_brush.h for tests/test_brush_cpu.py (through tests/brush_native.py): the header's functions behind a C
+// interface, and a whole brush / stamp over a numpy volume the way the kernels walk it (bounds, clip, predicate, mode).
+#include <cstdint>
+#include <cstring>
+
+#include "../../voxel-raytracing_amd/csrc/vrt_brush.h"
+
+using namespace vrt;
+
+extern "C" {
+
+int brush_shape_ok_c(int32_t shape, const int32_t* p) { return brush_shape_ok(shape, p) ? 1 : 0; }
+int brush_mode_ok_c(int32_t mode, uint32_t id, uint32_t match) { return brush_mode_ok(mode, id, match) ? 1 : 0; }
+void brush_bounds_c(int32_t shape, const int32_t* p, int64_t* lo, int64_t* hi) { brush_bounds(shape, p, lo, hi); }
+int brush_clip_c(const int64_t* lo, const int64_t* hi, const int32_t* dim, int32_t* clo, uint32_t* csize) { return brush_clip(lo, hi, dim, clo, csize) ? 1 : 0; }
+uint32_t brush_value_c(int32_t mode, uint32_t old, uint32_t id, uint32_t match) { return brush_value(mode, old, id, match); }
+
+// n voxels (x, y, z) -> out[i] = brush_inside
+void brush_inside_c(int32_t shape, const int32_t* p, size_t n, const int32_t* xyz, uint8_t* out)
+{
+    for (size_t i = 0; i < n; i++) out[i] = brush_inside(shape, p, xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2]) ? 1 : 0;
+}
+
+// bool [z, y, x] of a W x H x D volume: brush_inside of every voxel, bounds or not
+void brush_mask_c(int32_t shape, const int32_t* p, const int32_t* dim, uint8_t* mask)
+{
+    for (int32_t z = 0; z < dim[2]; z++)
+        for (int32_t y = 0; y < dim[1]; y++)
+            for (int32_t x = 0; x < dim[0]; x++) mask[(size_t)x + ((size_t)y + (size_t)z * dim[1]) * dim[0]] = brush_inside(shape, p, x, y, z) ? 1 : 0;
+}
+
+// The brush over vol (in place) as the kernels do it: only the clipped bounds are visited.  res: changed, lo[3], size[3] as
+// int64.  Returns 0, or 1 when the header refuses the brush.
+int brush_apply_c(int32_t shape, int32_t mode, const int32_t* p, uint32_t id, uint32_t match, const int32_t* dim, uint8_t* vol, int64_t* res)
+{
+    memset(res, 0, 7 * sizeof(int64_t));
+    if (!brush_shape_ok(shape, p) || !brush_mode_ok(mode, id, match)) return 1;
+    int64_t lo[3], hi[3];
+    int32_t clo[3];
+    uint32_t cs[3];
+    brush_bounds(shape, p, lo, hi);
+    if (!brush_clip(lo, hi, dim, clo, cs)) return 0;
+    int64_t n = 0, mn[3] = {INT32_MAX, INT32_MAX, INT32_MAX}, mx[3] = {INT32_MIN, INT32_MIN, INT32_MIN};
+    for (int32_t z = clo[2]; z < clo[2] + (int32_t)cs[2]; z++)
+        for (int32_t y = clo[1]; y < clo[1] + (int32_t)cs[1]; y++)
+            for (int32_t x = clo[0]; x < clo[0] + (int32_t)cs[0]; x++) {
+                uint8_t& v = vol[(size_t)x + ((size_t)y + (size_t)z * dim[1]) * dim[0]];
+                const uint32_t nw = brush_inside(shape, p, x, y, z) ? brush_value(mode, v, id, match) : v;
+                if (nw == v) continue;
+                v = (uint8_t)nw; n++;
+                const int32_t c[3] = {x, y, z};
+                for (int a = 0; a < 3; a++) { if (c[a] < mn[a]) mn[a] = c[a]; if (c[a] > mx[a]) mx[a] = c[a]; }
+            }
+    res[0] = n;
+    if (n) for (int a = 0; a < 3; a++) { res[1 + a] = mn[a]; res[4 + a] = mx[a] - mn[a] + 1; }
+    return 0;
+}
+
+int stamp_orient_ok_c(uint32_t orient) { return stamp_orient_ok(orient) ? 1 : 0; }
+void stamp_dst_size_c(uint32_t orient, const uint32_t* size, uint32_t* dsize) { stamp_dst_size(orient, size, dsize); }
+void stamp_source_c(uint32_t orient, const uint32_t* size, uint32_t dx, uint32_t dy, uint32_t dz, uint32_t* s) { stamp_source(orient, size, dx, dy, dz, s); }
+uint32_t stamp_value_c(uint32_t old, uint32_t src, int skip) { return stamp_value(old, src, skip != 0); }
+
+} // extern "C"

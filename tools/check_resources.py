@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Register budget of the hand-scheduled kernels (csrc: the parts of vrt_device.hip, vrt_denoise.hip, vrt_scene_edit.hip, vrt_scene_read.hip, vrt_query.hip, vrt_query_seg.hip, vrt_reproject.hip, vrt_reproject_cam.hip, vrt_upsample.hip, vrt_upsample_cam.hip, vrt_rays.hip, vrt_render_rays.hip), checked
+"""Register budget of the hand-scheduled kernels (csrc: the parts of vrt_device.hip, vrt_denoise.hip, vrt_scene_edit.hip, vrt_scene_read.hip, vrt_brush.hip, vrt_query.hip, vrt_query_seg.hip, vrt_reproject.hip, vrt_reproject_cam.hip, vrt_upsample.hip, vrt_upsample_cam.hip, vrt_rays.hip, vrt_render_rays.hip), checked
 at build time.
 
 K1's look-up loop pins physical registers and the kernel sits at two occupancy cliffs that the compiler's own remark does
@@ -63,6 +63,16 @@ BUDGET = {
     "k_list_scanEPjj": ("scene read-back: exclusive scan of the segments' counts", 32, 48, 0),
     "k_list_scatterILb0EE": ("scene read-back: the records to their places, dense", 32, 48, 0),
     "k_list_scatterILb1EE": ("scene read-back: the records to their places, bricks", 32, 48, 0),
+    # brushes and stamps (vrt_brush.hip): a gather, integer predicates in 64 bits and a ballot per wave -- no register cliff to guard,
+    # none may spill (16 .. 23 VGPRs, 36 .. 50 SGPRs)
+    "k_brush_extentILi0EE": ("brush: what a box changes (count, bounds, ids written)", 32, 64, 0),
+    "k_brush_extentILi1EE": ("brush: what an ellipsoid changes", 32, 64, 0),
+    "k_brush_extentILi2EE": ("brush: what a capsule changes", 32, 64, 0),
+    "k_brush_extentILi3EE": ("stamp: what the oriented source box changes", 32, 64, 0),
+    "k_brush_composeILi0EE": ("brush: the tight box's new ids into the edit scratch, box", 32, 64, 0),
+    "k_brush_composeILi1EE": ("brush: the tight box's new ids, ellipsoid", 32, 64, 0),
+    "k_brush_composeILi2EE": ("brush: the tight box's new ids, capsule", 32, 64, 0),
+    "k_brush_composeILi3EE": ("stamp: the tight box's new ids", 32, 64, 0),
     # ray queries (vrt_query.hip): k_query<TRAV, ANYHIT, PICK>; none may spill.  The closest-hit form over the look-up loop keeps the
     # ray's direction and first mapPos across the march for the hit record: seven waves per SIMD, the others eight
     "k_queryILi7ELb0ELb0EE": ("ray query, closest hit, look-up loop", 72, 80, 0),
@@ -114,7 +124,7 @@ BUDGET = {
 
 
 # the objects that hold budgeted kernels, as the Makefile builds them: (source, extra flags); slowest first
-OBJECTS = [("vrt_device.hip", ["-DVRT_K1_PART=%d" % n]) for n in (3, 0, 1, 2)] + [("vrt_denoise.hip", []), ("vrt_scene_edit.hip", []), ("vrt_scene_read.hip", []), ("vrt_query.hip", []), ("vrt_query_seg.hip", []),
+OBJECTS = [("vrt_device.hip", ["-DVRT_K1_PART=%d" % n]) for n in (3, 0, 1, 2)] + [("vrt_denoise.hip", []), ("vrt_scene_edit.hip", []), ("vrt_scene_read.hip", []), ("vrt_brush.hip", []), ("vrt_query.hip", []), ("vrt_query_seg.hip", []),
                                                                                      ("vrt_reproject.hip", []), ("vrt_reproject_cam.hip", []), ("vrt_upsample.hip", []), ("vrt_upsample_cam.hip", []), ("vrt_rays.hip", []),
                                                                                      ("vrt_render_rays.hip", [])]
 

@@ -82,6 +82,21 @@ class RayCamera(C.Structure):
     _fields_ = [("model", C.c_int32), ("basis", Push), ("tan_half", C.c_float), ("half_width", C.c_float)]
 
 
+BRUSH_BOX, BRUSH_ELLIPSOID, BRUSH_CAPSULE = 0, 1, 2                     # vrt_brush.shape
+BRUSH_SET, BRUSH_PAINT, BRUSH_ADD, BRUSH_REPLACE = 0, 1, 2, 3           # vrt_brush.mode
+STAMP_SKIP_EMPTY = 1                                                    # vrt_scene_stamp's flags
+
+
+class Brush(C.Structure):
+    """vrt_brush: a shape (positions in half voxels, csrc/vrt_brush.h), a mode and its ids."""
+    _fields_ = [("shape", C.c_int32), ("mode", C.c_int32), ("p", C.c_int32 * 9), ("id", C.c_uint8), ("match", C.c_uint8)]
+
+
+class BrushResult(C.Structure):
+    """vrt_brush_result: how many voxels changed and their tight box."""
+    _fields_ = [("changed", C.c_uint64), ("lo", C.c_int32 * 3), ("size", C.c_uint32 * 3)]
+
+
 MAX_QUERY_RAYS = 1 << 28       # rays per vrt_trace_rays / vrt_occluded_rays / vrt_pick_pixels / vrt_trace_segments / vrt_occluded_segments call
 
 assert C.sizeof(Push) == 96 and C.sizeof(Material) == 32
@@ -135,6 +150,9 @@ SYMBOLS = {
     "vrt_vox_encode_host": (C.c_int, [_P, C.POINTER(C.c_uint32), C.POINTER(Material), C.POINTER(_P), C.POINTER(C.c_size_t)]),
     "vrt_scene_save_vox_mem": (C.c_int, [_P, _P, C.POINTER(_P), C.POINTER(C.c_size_t)]),
     "vrt_scene_save_vox_file": (C.c_int, [_P, _P, C.c_char_p]),
+    "vrt_scene_brush": (C.c_int, [_P, _P, C.POINTER(Brush), C.POINTER(BrushResult)]),
+    "vrt_scene_stamp": (C.c_int, [_P, _P, C.POINTER(C.c_int32), _P, C.POINTER(C.c_int32), C.POINTER(C.c_uint32), C.c_uint32, C.c_uint32,
+                                  C.POINTER(BrushResult)]),
     "vrt_scene_free": (None, [_P, _P]),
     "vrt_settings_default": (None, [C.POINTER(Settings)]),
     "vrt_render_geometry": (C.c_int, [_P, _P, C.POINTER(Push), C.POINTER(Settings), C.POINTER(Frame), C.POINTER(Shard)]),

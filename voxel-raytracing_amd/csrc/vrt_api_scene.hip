@@ -1,6 +1,7 @@
 // vrt_api_scene.hip -- the scenes of the C-ABI: construction (dense and bricks), sky and noise, memory, download, edits of dense
-// scenes and of reserved brick scenes, read-back (a box, a box's non-empty voxels, the scene as a .vox file).  Host code only;
-// the kernels are vrt_scene_build.hip, vrt_scene_edit.hip and vrt_scene_read.hip.
+// scenes and of reserved brick scenes, read-back (a box, a box's non-empty voxels, the scene as a .vox file), brushes and stamps
+// (an edit whose ids a kernel composes).  Host code only; the kernels are vrt_scene_build.hip, vrt_scene_edit.hip,
+// vrt_scene_read.hip and vrt_brush.hip.
 //
 // Call surface mirrored from the reference (paths relative to its root):
 //   VoxelScene ctor            source/voxels/resource/voxel_scene.cpp:33-133
@@ -14,8 +15,7 @@
 #include "vox_reader.h"
 #include "vox_writer.h"
 #include "vrt_host.h"
-#define VRT_SCENE_READ_LAUNCHERS
-#include "vrt_scene_read.h"
+#include "vrt_brush_launch.h"          // (brings vrt_scene_read.h and its launchers)
 
 using namespace vrt;
 
@@ -99,6 +99,29 @@ static void note_metallic(vrt_scene* s, const uint8_t* ids, size_t nbox, uint8_t
     if (s->metallic_voxels) return;
     if (ids) { for (size_t i = 0; i < nbox && !s->metallic_voxels; i++) s->metallic_voxels = ids[i] != 0 && s->metal[ids[i]]; }
     else s->metallic_voxels = id != 0 && s->metal[id];
+}
+
+// Where the ids of an edited box come from: the host (uploaded), one id for the whole box, or -- a brush, a stamp -- a kernel
+// that composes them in the scratch memory, where the upload would have put them
+struct EditIds {
+    const uint8_t*  host = nullptr;       // the box's ids in box-index order, or
+    uint8_t         id = 0;               // (host and compose both NULL) one id for the whole box, or
+    const BrushJob* compose = nullptr;    // launch_brush_compose's job, whose box is the edit's, and
+    const uint32_t* written = nullptr;    // the set of ids it writes (BrushRecord::ids)
+    bool boxed() const { return host != nullptr || compose != nullptr; }
+};
+
+static void note_metallic(vrt_scene* s, const EditIds& src, size_t nbox)
+{
+    if (!src.compose) { note_metallic(s, src.host, nbox, src.id); return; }
+    for (int i = 1; i < 256 && !s->metallic_voxels; i++) s->metallic_voxels = ((src.written[i >> 5] >> (i & 31)) & 1u) != 0u && s->metal[i];
+}
+
+// the box's ids into the scratch memory (src.boxed())
+static hipError_t edit_ids_to_scratch(vrt_ctx* c, const EditIds& src, uint8_t* dev, size_t nbox)
+{
+    if (src.compose) return launch_brush_compose(*src.compose, dev, c->stream);
+    return hipMemcpyAsync(dev, src.host, nbox, hipMemcpyHostToDevice, c->stream);
 }
 
 // The edits' scratch memory, grown to `need` bytes (contents are not kept)
@@ -270,7 +293,7 @@ hipError_t brick_build_coarse(vrt_ctx* c, vrt_scene* s, uint8_t* tmp0, uint8_t* 
 }
 
 // vrt_scene_edit_box / vrt_scene_fill_box on a reserved brick scene; the caller checked the box, waited for the stream and holds the lock
-int brick_scene_edit(vrt_ctx* c, vrt_scene* s, const EditBox& box, const uint8_t* ids, uint8_t id, const std::string& name)
+int brick_scene_edit(vrt_ctx* c, vrt_scene* s, const EditBox& box, const EditIds& src, const std::string& name)
 {
     const VolumeView& d = s->d.vol;
     const BrickDims bd = brick_dims(s);
@@ -287,6 +310,7 @@ int brick_scene_edit(vrt_ctx* c, vrt_scene* s, const EditBox& box, const uint8_t
     }
     const bool rule = brick_edit_in_place(e.nbx, e.nby, e.nbz, box.lo, box.hi);
     // scratch: the ids | a word per brick of T from the classification | one to the write | the fine list | the coarse passes'
+    const bool ids = src.boxed();
     const size_t ids_room = ids ? round256(nbox) : 0, t_room = round256(nT * 4);
     const size_t list_max = rule ? nF : ((size_t)s->n_occ + nT < (size_t)s->bcap ? (size_t)s->n_occ + nT : (size_t)s->bcap);
     const size_t list_room = round256(list_max * 8);
@@ -297,8 +321,8 @@ int brick_scene_edit(vrt_ctx* c, vrt_scene* s, const EditBox& box, const uint8_t
     uint32_t* ptr_dev = (uint32_t*)(ids_dev + ids_room + t_room);
     uint2* list_dev = (uint2*)(ids_dev + ids_room + 2 * t_room);
     uint8_t* coarse_scr = ids_dev + ids_room + 2 * t_room + list_room;
-    if (ids) HIPCHK(hipMemcpyAsync(ids_dev, ids, nbox, hipMemcpyHostToDevice, c->stream));
-    e.ids = ids ? ids_dev : nullptr; e.id = id;
+    if (ids) HIPCHK(edit_ids_to_scratch(c, src, ids_dev, nbox));
+    e.ids = ids ? ids_dev : nullptr; e.id = src.id;
     // 1. classify, before anything is written: a refused edit leaves the scene as it was
     std::vector<uint32_t> after(nT), new_ptr(nT);
     HIPCHK(launch_bedit_classify(e, s->bgrid.get(), s->bpool.get(), after_dev, c->stream));
@@ -318,7 +342,7 @@ int brick_scene_edit(vrt_ctx* c, vrt_scene* s, const EditBox& box, const uint8_t
     if (appear > s->free_slots.size() + vanish)
         return fail(VRT_ERR_UNSUPPORTED, name + ": the edit makes " + std::to_string(appear) + " empty bricks occupied and the pool has " +
                     std::to_string(s->free_slots.size() + vanish) + " free slots; reserve more with vrt_scene_reserve_bricks");
-    note_metallic(s, ids, nbox, id);
+    note_metallic(s, src, nbox);
     // slots: the bricks that vanish give theirs back first, so an edit may move as many bricks as it likes within the reservation
     for (size_t t = 0; t < nT; t++) {
         const uint32_t pc = pc_of(t), old = s->hgrid[pc];
@@ -631,6 +655,33 @@ int vrt_scene_trim(vrt_ctx* c, vrt_scene* s)
     return VRT_OK;
 }
 
+// An edit of the box b, which lies inside the volume, with the ids of src; the caller checked that the scene is editable,
+// waited for the stream and holds the lock
+static int scene_edit_locked(vrt_ctx* c, vrt_scene* s, const EditBox& b, const EditIds& src, const std::string& name)
+{
+    if (s->bricks) return brick_scene_edit(c, s, b, src, name);
+    const VolumeView& d = s->d.vol;
+    const size_t nbox = (size_t)(b.hi[0] - b.lo[0]) * (size_t)(b.hi[1] - b.lo[1]) * (size_t)(b.hi[2] - b.lo[2]);
+    const bool ids = src.boxed();
+    note_metallic(s, src, nbox);
+    drop_count_fields(s);
+    const bool in_place = edit_in_place(d.W, d.H, d.D, b.lo, b.hi, VRT_EDIT_CAP);
+    size_t need = ids ? ((nbox + 255u) & ~(size_t)255u) : 0;
+    const size_t ids_room = need;
+    if (in_place) need += edit_scratch_bytes(b, s->open_cells);
+    HIPCHK(edit_scratch_room(s, need));
+    uint8_t* const scratch = s->edit_scratch.get();
+    if (ids) HIPCHK(edit_ids_to_scratch(c, src, scratch, nbox));
+    const size_t ndf = (size_t)d.df_stride;
+    HIPCHK(launch_edit_write(s->vox.get(), d.df_fast ? s->df + 8 * ndf : nullptr, b, ids ? scratch : nullptr, src.id, c->stream));
+    HIPCHK(launch_edit_pyramid(s->vox.get(), b, s->occ1.get(), s->occ2.get(), s->occ3.get(), c->stream));
+    if (in_place) HIPCHK(launch_edit_fields(s->vox.get(), b, s->df, ndf, scratch + ids_room, s->open_cells, c->stream));
+    else HIPCHK(build_fields(c, s, s->df, s->open_cells));
+    HIPCHK(build_cell_list(c, s));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return VRT_OK;
+}
+
 // vrt_scene_edit_box / vrt_scene_fill_box: ids == NULL fills the box with `id`
 static int scene_edit(vrt_ctx* c, vrt_scene* s, const int32_t lo[3], const uint32_t size[3], const uint8_t* ids, uint8_t id, const char* who)
 {
@@ -645,28 +696,12 @@ static int scene_edit(vrt_ctx* c, vrt_scene* s, const int32_t lo[3], const uint3
         if (lo[a] < 0 || lo[a] >= dim[a] || (uint64_t)size[a] > (uint64_t)(dim[a] - lo[a])) return fail(VRT_ERR_INVALID, name + ": the box leaves the volume");
         b.lo[a] = lo[a]; b.hi[a] = lo[a] + (int)size[a];
     }
-    const size_t nbox = (size_t)size[0] * size[1] * size[2];
     HIPCHK(hipSetDevice(c->device));
     HIPCHK(hipStreamSynchronize(c->stream));
     std::lock_guard<std::mutex> lock(s->lazy);
-    if (s->bricks) return brick_scene_edit(c, s, b, ids, id, name);
-    note_metallic(s, ids, nbox, id);
-    drop_count_fields(s);
-    const bool in_place = edit_in_place(d.W, d.H, d.D, b.lo, b.hi, VRT_EDIT_CAP);
-    size_t need = ids ? ((nbox + 255u) & ~(size_t)255u) : 0;
-    const size_t ids_room = need;
-    if (in_place) need += edit_scratch_bytes(b, s->open_cells);
-    HIPCHK(edit_scratch_room(s, need));
-    uint8_t* const scratch = s->edit_scratch.get();
-    if (ids) HIPCHK(hipMemcpyAsync(scratch, ids, nbox, hipMemcpyHostToDevice, c->stream));
-    const size_t ndf = (size_t)d.df_stride;
-    HIPCHK(launch_edit_write(s->vox.get(), d.df_fast ? s->df + 8 * ndf : nullptr, b, ids ? scratch : nullptr, id, c->stream));
-    HIPCHK(launch_edit_pyramid(s->vox.get(), b, s->occ1.get(), s->occ2.get(), s->occ3.get(), c->stream));
-    if (in_place) HIPCHK(launch_edit_fields(s->vox.get(), b, s->df, ndf, scratch + ids_room, s->open_cells, c->stream));
-    else HIPCHK(build_fields(c, s, s->df, s->open_cells));
-    HIPCHK(build_cell_list(c, s));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    return VRT_OK;
+    EditIds src;
+    src.host = ids; src.id = id;
+    return scene_edit_locked(c, s, b, src, name);
 }
 
 int vrt_scene_edit_box(vrt_ctx* c, vrt_scene* s, const int32_t lo[3], const uint32_t size[3], const uint8_t* ids)
@@ -953,6 +988,126 @@ int vrt_scene_save_vox_file(struct vrt_ctx* c, const vrt_scene* s, const char* p
     const bool ok = fwrite(file.data(), 1, file.size(), f) == file.size();
     if (fclose(f) != 0 || !ok) return fail(VRT_ERR_IO, std::string("Could not write voxel scene ") + path);
     return VRT_OK;
+}
+
+} // extern "C"
+
+// ---- brushes and stamps (vrt_scene_brush, vrt_scene_stamp; csrc/vrt_brush.h) ---------------------------------------------------
+
+static_assert(VRT_BRUSH_BOX == VRT_BRUSH_SHAPE_BOX && VRT_BRUSH_ELLIPSOID == VRT_BRUSH_SHAPE_ELLIPSOID && VRT_BRUSH_CAPSULE == VRT_BRUSH_SHAPE_CAPSULE,
+              "include/vrt.h and csrc/vrt_brush.h number the shapes differently");
+static_assert(VRT_BRUSH_SET == VRT_BRUSH_MODE_SET && VRT_BRUSH_PAINT == VRT_BRUSH_MODE_PAINT && VRT_BRUSH_ADD == VRT_BRUSH_MODE_ADD &&
+              VRT_BRUSH_REPLACE == VRT_BRUSH_MODE_REPLACE, "include/vrt.h and csrc/vrt_brush.h number the modes differently");
+
+namespace {
+
+// One brush or stamp over the clipped bounds [clo, clo + csize) of the scene j.box views: the extent kernel says what changes;
+// if anything does, the tight box of the changes is edited with the ids the compose kernel writes.  The caller checked the
+// arguments, waited for the stream and holds the scene's lock.  *out (may be NULL) holds zeros.
+int brush_run(vrt_ctx* c, vrt_scene* s, BrushJob& j, const int32_t clo[3], const uint32_t csize[3], const std::string& name, vrt_brush_result* out)
+{
+    if (!c->brush_rec) HIPCHK(c->brush_rec.alloc(sizeof(BrushRecord)));
+    BrushRecord* const rec_dev = (BrushRecord*)c->brush_rec.get();
+    const BrushRecord init = brush_record_init();
+    BrushRecord rec = init;
+    for (int a = 0; a < 3; a++) { j.box.lo[a] = clo[a]; j.box.size[a] = csize[a]; }
+    HIPCHK(hipMemcpyAsync(rec_dev, &init, sizeof init, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(launch_brush_extent(j, rec_dev, c->stream));
+    HIPCHK(hipMemcpyAsync(&rec, rec_dev, sizeof rec, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (rec.changed == 0ull) return VRT_OK;                     // nothing is written, no edit pass runs, the count planes' fields stay
+    const VolumeView& d = s->d.vol;
+    EditBox b;
+    b.W = d.W; b.H = d.H; b.D = d.D;
+    for (int a = 0; a < 3; a++) {
+        if (rec.mn[a] < clo[a] || rec.mx[a] < rec.mn[a] || (int64_t)rec.mx[a] >= (int64_t)clo[a] + (int64_t)csize[a])
+            return fail(VRT_ERR_HIP, name + ": internal error (the changed voxels' bounds leave the brush's)");
+        b.lo[a] = rec.mn[a]; b.hi[a] = rec.mx[a] + 1;
+        j.box.lo[a] = b.lo[a]; j.box.size[a] = (uint32_t)(b.hi[a] - b.lo[a]);
+    }
+    EditIds src;
+    src.compose = &j; src.written = rec.ids;
+    const int rc = scene_edit_locked(c, s, b, src, name);
+    if (rc == VRT_OK && out) {
+        out->changed = rec.changed;
+        for (int a = 0; a < 3; a++) { out->lo[a] = b.lo[a]; out->size[a] = j.box.size[a]; }
+    }
+    return rc;
+}
+
+} // namespace
+
+extern "C" {
+
+int vrt_scene_brush(struct vrt_ctx* c, vrt_scene* s, const vrt_brush* brush, vrt_brush_result* result)
+{
+    const std::string name("vrt_scene_brush");
+    if (!c || !s || !brush) return fail(VRT_ERR_INVALID, name + ": NULL argument");
+    if (brush->shape != VRT_BRUSH_BOX && brush->shape != VRT_BRUSH_ELLIPSOID && brush->shape != VRT_BRUSH_CAPSULE) return fail(VRT_ERR_INVALID, name + ": unknown shape");
+    if (!brush_shape_ok(brush->shape, brush->p))
+        return fail(VRT_ERR_INVALID, name + ": a shape parameter is outside its range (box sizes 1..2^30; semi-axes and radius 1..1024 half voxels; a capsule's end points -4096..12288)");
+    if (brush->mode < VRT_BRUSH_SET || brush->mode > VRT_BRUSH_REPLACE) return fail(VRT_ERR_INVALID, name + ": unknown mode");
+    if (!brush_mode_ok(brush->mode, brush->id, brush->match))
+        return fail(VRT_ERR_INVALID, name + (brush->mode == VRT_BRUSH_REPLACE ? ": REPLACE needs id != match" : ": PAINT and ADD need id != 0 (carve with SET)"));
+    if (result) memset(result, 0, sizeof *result);
+    if (s->bricks && !s->reserved) return fail(VRT_ERR_UNSUPPORTED, name + ": a brick scene cannot be edited before vrt_scene_reserve_bricks");
+    const int32_t dim[3] = {s->d.vol.W, s->d.vol.H, s->d.vol.D};
+    int64_t lo[3], hi[3];
+    int32_t clo[3];
+    uint32_t csize[3];
+    brush_bounds(brush->shape, brush->p, lo, hi);
+    if (!brush_clip(lo, hi, dim, clo, csize)) return VRT_OK;       // wholly outside the volume: nothing to do
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    std::lock_guard<std::mutex> lock(s->lazy);
+    BrushJob j{};
+    j.box = read_box_of(s, clo, csize);
+    j.form = brush->shape; j.mode = brush->mode;
+    for (int i = 0; i < 9; i++) j.p[i] = brush->p[i];
+    j.id = brush->id; j.match = brush->match;
+    return brush_run(c, s, j, clo, csize, name, result);
+}
+
+int vrt_scene_stamp(struct vrt_ctx* c, vrt_scene* dst, const int32_t dst_lo[3], const vrt_scene* src, const int32_t src_lo[3],
+                    const uint32_t size[3], uint32_t orient, uint32_t flags, vrt_brush_result* result)
+{
+    const std::string name("vrt_scene_stamp");
+    if (!c || !dst || !dst_lo || !src || !src_lo || !size) return fail(VRT_ERR_INVALID, name + ": NULL argument");
+    if (!stamp_orient_ok(orient)) return fail(VRT_ERR_INVALID, name + ": an orientation is perm | flips << 3 with perm in 0..5 and flips in 0..7");
+    if (flags & ~(uint32_t)VRT_STAMP_SKIP_EMPTY) return fail(VRT_ERR_INVALID, name + ": unknown flag");
+    size_t n = 0;
+    const int rc = read_box_checked(src, src_lo, size, 0, name, &n);
+    if (rc != VRT_OK) return rc;
+    for (int a = 0; a < 3; a++)
+        if (size[a] > VRT_STAMP_MAX_SIDE) return fail(VRT_ERR_INVALID, name + ": a stamp has no side above " + std::to_string(VRT_STAMP_MAX_SIDE) + "; stamp in parts");
+    if (result) memset(result, 0, sizeof *result);
+    if (dst->bricks && !dst->reserved) return fail(VRT_ERR_UNSUPPORTED, name + ": a brick scene cannot be edited before vrt_scene_reserve_bricks");
+    const int32_t dim[3] = {dst->d.vol.W, dst->d.vol.H, dst->d.vol.D};
+    uint32_t dsize[3], csize[3];
+    int64_t lo[3], hi[3];
+    int32_t clo[3];
+    stamp_dst_size(orient, size, dsize);
+    for (int a = 0; a < 3; a++) { lo[a] = (int64_t)dst_lo[a]; hi[a] = (int64_t)dst_lo[a] + (int64_t)dsize[a]; }
+    if (!brush_clip(lo, hi, dim, clo, csize)) return VRT_OK;       // wholly outside the destination
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    std::lock_guard<std::mutex> lock(dst->lazy);
+    // the source box into staging before anything is written: a stamp of a scene onto itself copies the old content
+    DevBuf<uint8_t> stage;
+    if (stage.alloc(n) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(VRT_ERR_UNSUPPORTED, name + ": no device memory for a staging buffer of " + std::to_string(n) + " bytes; stamp in parts");
+    }
+    HIPCHK(launch_read_box(read_box_of(src, src_lo, size), stage.get(), c->stream));
+    BrushJob j{};
+    j.box = read_box_of(dst, clo, csize);
+    j.form = VRT_BRUSH_FORM_STAMP;
+    j.stage = stage.get();
+    for (int a = 0; a < 3; a++) { j.dst_lo[a] = dst_lo[a]; j.src_size[a] = size[a]; }
+    j.orient = orient; j.skip_empty = (flags & VRT_STAMP_SKIP_EMPTY) ? 1u : 0u;
+    const int rcb = brush_run(c, dst, j, clo, csize, name, result);
+    HIPCHK(hipStreamSynchronize(c->stream));                       // (the staging buffer goes when this returns)
+    return rcb;
 }
 
 } // extern "C"

@@ -140,6 +140,8 @@ struct vrt_ctx {
     size_t pano_floats = 0;
     hipEvent_t pano_done = nullptr;
     bool pano_busy = false;
+    // vrt_scene_brush / vrt_scene_stamp: the record the extent kernel returns (vrt_brush_launch.h: BrushRecord), allocated by the first brush
+    vrt::DevBuf<uint8_t> brush_rec;
 };
 
 struct vrt_scene {

@@ -439,6 +439,68 @@ class VoxelScene:
         self._raise(lib().vrt_scene_fill_box(self.engine.ctx, self.handle, (C.c_int32 * 3)(*[int(t) for t in lo]),
                                              (C.c_uint32 * 3)(*[int(t) for t in size]), int(id)))
 
+    # ---- brushes and stamps (vrt_scene_brush, vrt_scene_stamp; csrc/vrt_brush.h) ------------------------------------------
+    BRUSH_SHAPES = {"box": _capi.BRUSH_BOX, "ellipsoid": _capi.BRUSH_ELLIPSOID, "capsule": _capi.BRUSH_CAPSULE}
+    BRUSH_MODES = {"set": _capi.BRUSH_SET, "paint": _capi.BRUSH_PAINT, "add": _capi.BRUSH_ADD, "replace": _capi.BRUSH_REPLACE}
+
+    @staticmethod
+    def _half_voxels(v, what):
+        """voxel units -> half voxels; only multiples of 0.5 have one"""
+        out = []
+        for t in np.atleast_1d(np.asarray(v, dtype=np.float64)).tolist():
+            h = 2.0 * t
+            if not (np.isfinite(h) and h == int(h) and abs(h) < 2 ** 31):
+                raise ValueError(f"VoxelScene: {what} = {t} is not a multiple of 0.5 voxels")
+            out.append(int(h))
+        return out
+
+    @staticmethod
+    def _brush_result(res):
+        return int(res.changed), tuple(int(t) for t in res.lo), tuple(int(t) for t in res.size)
+
+    def brush(self, shape, mode, p, id: int = 0, match: int = 0):
+        """One brush (vrt_scene_brush).  shape: "box" | "ellipsoid" | "capsule" (or its number), mode: "set" | "paint" | "add" |
+        "replace", p: the shape's integer parameters as include/vrt.h lays them out (positions of ellipsoids and capsules in HALF
+        voxels).  Returns (changed, lo, size): how many voxels changed and their tight box, zeros when none did."""
+        sh = self.BRUSH_SHAPES[shape] if isinstance(shape, str) else int(shape)
+        md = self.BRUSH_MODES[mode] if isinstance(mode, str) else int(mode)
+        p = [int(t) for t in p]
+        if len(p) > 9 or any(not -2 ** 31 <= t < 2 ** 31 for t in p) or not 0 <= int(id) <= 255 or not 0 <= int(match) <= 255:
+            raise ValueError("VoxelScene.brush: at most nine int32 parameters, ids in 0..255")
+        b = _capi.Brush(shape=sh, mode=md, id=int(id), match=int(match))
+        b.p[:len(p)] = p
+        res = _capi.BrushResult()
+        self._raise(lib().vrt_scene_brush(self.engine.ctx, self.handle, C.byref(b), C.byref(res)))
+        return self._brush_result(res)
+
+    def box(self, lo, size, id: int, mode="set", match: int = 0):
+        """A box of voxels lo .. lo + size (integers; lo may be negative, what lies outside the volume is clipped)."""
+        if any(int(t) != t for t in list(lo) + list(size)):
+            raise ValueError("VoxelScene.box: lo and size are whole voxels")
+        return self.brush("box", mode, [int(t) for t in lo] + [int(t) for t in size], id, match)
+
+    def ellipsoid(self, center, radii, id: int, mode="set", match: int = 0):
+        """An ellipsoid; center and radii in voxel units, multiples of 0.5 (voxel (x, y, z) has its centre at (x+.5, y+.5, z+.5))."""
+        return self.brush("ellipsoid", mode, self._half_voxels(center, "center") + self._half_voxels(radii, "radius"), id, match)
+
+    def sphere(self, center, radius, id: int, mode="set", match: int = 0):
+        return self.ellipsoid(center, (radius, radius, radius), id, mode, match)
+
+    def capsule(self, a, b, radius, id: int, mode="set", match: int = 0):
+        """Every voxel whose centre lies within `radius` of the segment a .. b (voxel units, multiples of 0.5): a dragged sphere."""
+        return self.brush("capsule", mode, self._half_voxels(a, "a") + self._half_voxels(b, "b") + self._half_voxels(radius, "radius"), id, match)
+
+    def stamp(self, dst_lo, src: "VoxelScene", src_lo, size, orient: int = 0, skip_empty: bool = False):
+        """Paste the box src_lo .. src_lo + size of src (which may be this scene) at dst_lo, oriented by orient = perm | flips << 3
+        (vrt_scene_stamp).  Returns (changed, lo, size) like brush."""
+        if any(int(t) < 0 for t in size) or not 0 <= int(orient) <= 0xFFFFFFFF:
+            raise ValueError("VoxelScene.stamp: negative size or orientation")
+        res = _capi.BrushResult()
+        self._raise(lib().vrt_scene_stamp(self.engine.ctx, self.handle, (C.c_int32 * 3)(*[int(t) for t in dst_lo]), src.handle,
+                                          (C.c_int32 * 3)(*[int(t) for t in src_lo]), (C.c_uint32 * 3)(*[int(t) for t in size]), int(orient),
+                                          _capi.STAMP_SKIP_EMPTY if skip_empty else 0, C.byref(res)))
+        return self._brush_result(res)
+
     # ---- read-back (vrt_scene_read_box, vrt_scene_list_box, vrt_scene_save_vox_*) ---------------------------------------
     @staticmethod
     def _box(lo, size):

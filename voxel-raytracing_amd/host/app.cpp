@@ -9,7 +9,10 @@
 // (the history is then kept by vrt_reproject_camera, with --upsample too at display resolution by vrt_upsample_camera); not with
 // --devices.
 // --fill X Y Z SX SY SZ ID (repeatable): the box is filled with ID (0 carves) before anything else looks at the scene
-// (VoxelScene::fill).  --save-vox OUT: the scene as it stands after that is written as a MagicaVoxel file (VoxelScene::save).
+// (VoxelScene::fill).  --brush SHAPE:MODE:PARAMS:ID[:MATCH] (repeatable; applied in command-line order together with --fill):
+// SHAPE box | sphere | ellipsoid | capsule, MODE set | paint | add | replace, PARAMS comma-separated in VOXEL units -- box
+// x,y,z,sx,sy,sz (whole voxels); sphere cx,cy,cz,r; ellipsoid cx,cy,cz,rx,ry,rz; capsule ax,ay,az,bx,by,bz,r (multiples of 0.5;
+// voxel (x, y, z) has its centre at x+.5, y+.5, z+.5) -- e.g. --brush sphere:paint:16,16,16,5.5:9 (VoxelScene::brush).  --save-vox OUT: the scene as it stands after that is written as a MagicaVoxel file (VoxelScene::save).
 // --read-box X Y Z SX SY SZ OUT: the ids of the box, x fastest, raw bytes (VoxelScene::read).  With either and no image output
 // (--out, --raw, --png) no frame is rendered.
 // Errors propagate as exceptions to run(), are printed, and the process exits with EXIT_FAILURE.
@@ -54,6 +57,41 @@ std::shared_ptr<VoxelScene> loadDense(const std::shared_ptr<Engine>& engine, con
     return scene;
 }
 
+// --brush SHAPE:MODE:PARAMS:ID[:MATCH]
+vrt_brush parseBrush(const std::string& spec)
+{
+    auto split = [](const std::string& t, char sep) {
+        std::vector<std::string> out; size_t at = 0;
+        for (;;) { const size_t e = t.find(sep, at); out.push_back(t.substr(at, e == std::string::npos ? e : e - at)); if (e == std::string::npos) break; at = e + 1; }
+        return out;
+    };
+    const std::vector<std::string> f = split(spec, ':');
+    if (f.size() != 4 && f.size() != 5) throw std::runtime_error("--brush wants SHAPE:MODE:PARAMS:ID[:MATCH], got " + spec);
+    vrt_brush b{};
+    std::vector<double> v;
+    for (const std::string& t : split(f[2], ',')) v.push_back(std::stod(t));
+    auto want = [&](size_t n) { if (v.size() != n) throw std::runtime_error("--brush " + f[0] + " takes " + std::to_string(n) + " parameters"); };
+    if (f[0] == "box") {
+        want(6); b.shape = VRT_BRUSH_BOX;
+        for (size_t a = 0; a < 6; a++) { if (v[a] != (double)(int32_t)v[a]) throw std::runtime_error("--brush box takes whole voxels"); b.p[a] = (int32_t)v[a]; }
+    } else if (f[0] == "sphere") {
+        want(4); b.shape = VRT_BRUSH_ELLIPSOID;
+        for (size_t a = 0; a < 3; a++) { b.p[a] = VoxelScene::halfVoxels(v[a]); b.p[3 + a] = VoxelScene::halfVoxels(v[3]); }
+    } else if (f[0] == "ellipsoid") {
+        want(6); b.shape = VRT_BRUSH_ELLIPSOID;
+        for (size_t a = 0; a < 6; a++) b.p[a] = VoxelScene::halfVoxels(v[a]);
+    } else if (f[0] == "capsule") {
+        want(7); b.shape = VRT_BRUSH_CAPSULE;
+        for (size_t a = 0; a < 7; a++) b.p[a] = VoxelScene::halfVoxels(v[a]);
+    } else throw std::runtime_error("--brush: unknown shape " + f[0]);
+    if (f[1] == "set") b.mode = VRT_BRUSH_SET; else if (f[1] == "paint") b.mode = VRT_BRUSH_PAINT; else if (f[1] == "add") b.mode = VRT_BRUSH_ADD;
+    else if (f[1] == "replace") b.mode = VRT_BRUSH_REPLACE; else throw std::runtime_error("--brush: unknown mode " + f[1]);
+    const unsigned long id = std::stoul(f[3]), match = f.size() == 5 ? std::stoul(f[4]) : 0ul;
+    if (id > 255 || match > 255) throw std::runtime_error("--brush: ids are 0..255");
+    b.id = (uint8_t)id; b.match = (uint8_t)match;
+    return b;
+}
+
 int run(int argc, char** argv)
 {
     try {
@@ -64,7 +102,8 @@ int run(int argc, char** argv)
         int frames = 1; uint32_t windowW = 0, windowH = 0; float flyForward = 0, flyStrafe = 0, flyMouseX = 0; bool temporal = false, reproject = false, upsample = false;
         std::string dumpPushes, projection; std::vector<vrt_push> allPushes;
         struct Box { std::array<int32_t, 3> lo; std::array<uint32_t, 3> size; uint8_t id; };
-        std::vector<Box> fills; Box readBox{}; std::string saveVox, readBoxOut;
+        struct SceneOp { bool isBrush; Box box; vrt_brush brush; };                    // --fill and --brush, in the order given
+        std::vector<SceneOp> sceneOps; Box readBox{}; std::string saveVox, readBoxOut;
         for (int i = 1; i < argc; i++) {
             std::string a = argv[i];
             auto next = [&]() { if (i + 1 >= argc) throw std::runtime_error("missing value for " + a); return std::string(argv[++i]); };
@@ -77,8 +116,9 @@ int run(int argc, char** argv)
                 Box b{};
                 for (int k = 0; k < 3; k++) b.lo[(size_t)k] = std::stoi(next());
                 for (int k = 0; k < 3; k++) b.size[(size_t)k] = (uint32_t)std::stoul(next());
-                if (a == "--fill") { b.id = (uint8_t)std::stoul(next()); fills.push_back(b); } else { readBox = b; readBoxOut = next(); }
+                if (a == "--fill") { b.id = (uint8_t)std::stoul(next()); sceneOps.push_back(SceneOp{false, b, vrt_brush{}}); } else { readBox = b; readBoxOut = next(); }
             }
+            else if (a == "--brush") sceneOps.push_back(SceneOp{true, Box{}, parseBrush(next())});
             else if (a == "--save-vox") saveVox = next();
             else if (a == "--width") settings->targetResolution[0] = (uint32_t)std::stoul(next());
             else if (a == "--height") settings->targetResolution[1] = (uint32_t)std::stoul(next());
@@ -134,7 +174,11 @@ int run(int argc, char** argv)
         else scene = std::make_shared<VoxelScene>(engine, vox.empty() ? settings->voxPath : vox);
         if (!sky.empty()) scene->setSkybox(sky);
         if (!noise.empty()) scene->setBlueNoise(noise);
-        for (const Box& b : fills) scene->fill(b.lo, b.size, b.id);
+        for (const SceneOp& op : sceneOps) {
+            if (!op.isBrush) { scene->fill(op.box.lo, op.box.size, op.box.id); continue; }
+            const vrt_brush_result r = scene->brush(op.brush);
+            std::printf("brush: %llu voxels changed, box %d %d %d + %u %u %u\n", (unsigned long long)r.changed, r.lo[0], r.lo[1], r.lo[2], r.size[0], r.size[1], r.size[2]);
+        }
         if (!saveVox.empty()) scene->save(saveVox);
         if (!readBoxOut.empty()) {
             const std::vector<uint8_t> ids = scene->read(readBox.lo, readBox.size);

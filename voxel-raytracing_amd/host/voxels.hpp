@@ -157,6 +157,48 @@ public:
     // Rewrite the box [lo, lo + size) (no reference analogue; vrt_scene_edit_box / vrt_scene_fill_box): ids x-fastest, 0 = empty
     void edit(const std::array<int32_t, 3>& lo, const std::array<uint32_t, 3>& size, const uint8_t* ids) { check(vrt_scene_edit_box(engine->ctx, handle, lo.data(), size.data(), ids)); }
     void fill(const std::array<int32_t, 3>& lo, const std::array<uint32_t, 3>& size, uint8_t id) { check(vrt_scene_fill_box(engine->ctx, handle, lo.data(), size.data(), id)); }
+    // Brushes and stamps (no reference analogue; vrt_scene_brush / vrt_scene_stamp): an edit composed on the device, rebuilt around
+    // the tight box of what changed, which is what they return (changed == 0: nothing was written).  brush takes the C structure;
+    // the helpers take voxel units that are multiples of 0.5 -- voxel (x, y, z) has its centre at (x + .5, y + .5, z + .5) -- and
+    // refuse anything else.  mode: VRT_BRUSH_SET, _PAINT, _ADD, _REPLACE.  A shape partly outside the volume is clipped.
+    vrt_brush_result brush(const vrt_brush& b) { vrt_brush_result r{}; check(vrt_scene_brush(engine->ctx, handle, &b, &r)); return r; }
+    static int32_t halfVoxels(double v)
+    {
+        const double h = 2.0 * v;
+        if (!(h >= -2147483648.0 && h <= 2147483647.0) || h != (double)(int64_t)h) throw std::runtime_error("a brush position must be a multiple of 0.5 voxels");
+        return (int32_t)h;
+    }
+    vrt_brush_result box(const std::array<int32_t, 3>& lo, const std::array<int32_t, 3>& size, uint8_t id, int32_t mode = VRT_BRUSH_SET, uint8_t match = 0)
+    {
+        vrt_brush b{}; b.shape = VRT_BRUSH_BOX; b.mode = mode; b.id = id; b.match = match;
+        for (size_t a = 0; a < 3; a++) { b.p[a] = lo[a]; b.p[3 + a] = size[a]; }
+        return brush(b);
+    }
+    vrt_brush_result ellipsoid(const std::array<double, 3>& center, const std::array<double, 3>& radii, uint8_t id, int32_t mode = VRT_BRUSH_SET, uint8_t match = 0)
+    {
+        vrt_brush b{}; b.shape = VRT_BRUSH_ELLIPSOID; b.mode = mode; b.id = id; b.match = match;
+        for (size_t a = 0; a < 3; a++) { b.p[a] = halfVoxels(center[a]); b.p[3 + a] = halfVoxels(radii[a]); }
+        return brush(b);
+    }
+    vrt_brush_result sphere(const std::array<double, 3>& center, double radius, uint8_t id, int32_t mode = VRT_BRUSH_SET, uint8_t match = 0)
+    {
+        return ellipsoid(center, {radius, radius, radius}, id, mode, match);
+    }
+    vrt_brush_result capsule(const std::array<double, 3>& a0, const std::array<double, 3>& b0, double radius, uint8_t id, int32_t mode = VRT_BRUSH_SET, uint8_t match = 0)
+    {
+        vrt_brush b{}; b.shape = VRT_BRUSH_CAPSULE; b.mode = mode; b.id = id; b.match = match;
+        for (size_t a = 0; a < 3; a++) { b.p[a] = halfVoxels(a0[a]); b.p[3 + a] = halfVoxels(b0[a]); }
+        b.p[6] = halfVoxels(radius);
+        return brush(b);
+    }
+    // the box [srcLo, srcLo + size) of src (which may be this scene) pasted at dstLo under orient = perm | flips << 3
+    vrt_brush_result stamp(const std::array<int32_t, 3>& dstLo, const VoxelScene& src, const std::array<int32_t, 3>& srcLo, const std::array<uint32_t, 3>& size,
+                           uint32_t orient = 0, bool skipEmpty = false)
+    {
+        vrt_brush_result r{};
+        check(vrt_scene_stamp(engine->ctx, handle, dstLo.data(), src.handle, srcLo.data(), size.data(), orient, skipEmpty ? VRT_STAMP_SKIP_EMPTY : 0u, &r));
+        return r;
+    }
     // A brick scene becomes editable, with room for `capacity` bricks in its pool (vrt_scene_reserve_bricks); edit / fill then work on it
     // Read-back (no reference analogue; vrt_scene_read_box / vrt_scene_list_box / vrt_scene_save_vox_file).  read: the ids of the
     // box [lo, lo + size), x fastest -- what edit takes.  voxels: the box's non-empty voxels (no side above 256), one word each,

@@ -365,6 +365,44 @@ int  vrt_scene_brush(struct vrt_ctx* ctx, vrt_scene* scene, const vrt_brush* bru
 #define VRT_STAMP_SKIP_EMPTY 1u
 int  vrt_scene_stamp(struct vrt_ctx* ctx, vrt_scene* dst, const int32_t dst_lo[3], const vrt_scene* src, const int32_t src_lo[3],
                      const uint32_t size[3], uint32_t orient, uint32_t flags, vrt_brush_result* result);
+/* Flood fill (no reference analogue): select voxels by CONNECTIVITY on the device and rewrite them -- fill a closed cavity,
+ * recolour or delete one object, or (VRT_FLOOD_MEASURE) ask how large the thing at the seed is.  csrc/vrt_flood.h is the
+ * definition.  The bounds [lo, lo+size) are in voxels; lo may be negative, each size in 1..2^30; they are clipped to the volume and
+ * the clipped bounds may have no side above 512 (VRT_ERR_INVALID: flood in parts).  A voxel PASSES under VRT_FLOOD_SAME iff its id
+ * equals the id of the seed voxel (0 included: the cavity fill), under VRT_FLOOD_SOLID iff its id != 0.  The REGION is the
+ * connected component of the seed among the passing voxels of the clipped bounds, joined through faces (VRT_FLOOD_FACES) or
+ * through faces, edges and corners (VRT_FLOOD_CORNERS); a seed that does not pass has the empty region.  Every voxel of the region
+ * becomes `id`.  result (not NULL): the region's voxel count and tight box (zeros when empty), the id found at the seed, and, as
+ * vrt_scene_brush's result, how many voxels changed their id and their tight box.  Bounds wholly outside the volume or a seed
+ * outside the clipped bounds change nothing and are VRT_OK with a zero result.  When edit.changed == 0 -- SAME with the id already
+ * there, SOLID on an empty seed -- nothing is written, no edit pass runs and the count planes' second set of fields is kept.
+ * flags: VRT_FLOOD_MEASURE writes nothing and reports the region only (edit stays zeros); it works on every scene, brick scenes
+ * that were never reserved included.  Otherwise brick scenes, slot exhaustion (VRT_ERR_UNSUPPORTED, nothing changed), stream rules
+ * and the metallic rule are vrt_scene_brush's.  A NULL argument, an unknown match, connectivity or flag, a size of 0 or above
+ * 2^30: VRT_ERR_INVALID before any device work.  The masks the search needs (2 bits per voxel of the clipped bounds) are kept with
+ * the scene between calls: vrt_scene_memory counts them, vrt_scene_trim drops them; VRT_ERR_UNSUPPORTED if they cannot be had. */
+#define VRT_FLOOD_SAME    0
+#define VRT_FLOOD_SOLID   1
+#define VRT_FLOOD_FACES   6
+#define VRT_FLOOD_CORNERS 26
+#define VRT_FLOOD_MEASURE 1u   /* flags: write nothing, report the region only */
+typedef struct vrt_flood {
+    int32_t  seed[3], lo[3];
+    uint32_t size[3];
+    int32_t  match, connectivity;
+    uint32_t flags;
+    uint8_t  id;
+} vrt_flood;
+typedef struct vrt_flood_result {
+    uint64_t region;
+    int32_t  region_lo[3];
+    uint32_t region_size[3];   /* the component and its tight box; zeros when empty */
+    uint32_t seed_id;          /* the id found at the seed */
+    vrt_brush_result edit;     /* as vrt_scene_brush's; zeros under VRT_FLOOD_MEASURE */
+} vrt_flood_result;
+int  vrt_scene_flood(struct vrt_ctx* ctx, vrt_scene* scene, const vrt_flood* flood, vrt_flood_result* result);
+/* (diagnostics) how many rounds of its tile kernel the scene's latest flood ran */
+int  vrt_debug_flood_rounds(const vrt_scene* scene, uint32_t* rounds);
 void vrt_scene_free(vrt_ctx* ctx, vrt_scene* sc);            /* VoxelScene::destroy */
 
 /* ---- settings -------------------------------------------------------------------------------- */

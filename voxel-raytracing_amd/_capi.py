@@ -97,6 +97,22 @@ class BrushResult(C.Structure):
     _fields_ = [("changed", C.c_uint64), ("lo", C.c_int32 * 3), ("size", C.c_uint32 * 3)]
 
 
+FLOOD_SAME, FLOOD_SOLID = 0, 1                                          # vrt_flood.match
+FLOOD_FACES, FLOOD_CORNERS = 6, 26                                      # vrt_flood.connectivity
+FLOOD_MEASURE = 1                                                       # vrt_flood.flags
+
+
+class Flood(C.Structure):
+    """vrt_flood: a seed, the bounds the search stays in, a predicate, a connectivity and the id the region becomes (csrc/vrt_flood.h)."""
+    _fields_ = [("seed", C.c_int32 * 3), ("lo", C.c_int32 * 3), ("size", C.c_uint32 * 3), ("match", C.c_int32), ("connectivity", C.c_int32),
+                ("flags", C.c_uint32), ("id", C.c_uint8)]
+
+
+class FloodResult(C.Structure):
+    """vrt_flood_result: the region and its tight box, the id found at the seed, and the edit as vrt_scene_brush reports one."""
+    _fields_ = [("region", C.c_uint64), ("region_lo", C.c_int32 * 3), ("region_size", C.c_uint32 * 3), ("seed_id", C.c_uint32), ("edit", BrushResult)]
+
+
 MAX_QUERY_RAYS = 1 << 28       # rays per vrt_trace_rays / vrt_occluded_rays / vrt_pick_pixels / vrt_trace_segments / vrt_occluded_segments call
 
 assert C.sizeof(Push) == 96 and C.sizeof(Material) == 32
@@ -153,6 +169,8 @@ SYMBOLS = {
     "vrt_scene_brush": (C.c_int, [_P, _P, C.POINTER(Brush), C.POINTER(BrushResult)]),
     "vrt_scene_stamp": (C.c_int, [_P, _P, C.POINTER(C.c_int32), _P, C.POINTER(C.c_int32), C.POINTER(C.c_uint32), C.c_uint32, C.c_uint32,
                                   C.POINTER(BrushResult)]),
+    "vrt_scene_flood": (C.c_int, [_P, _P, C.POINTER(Flood), C.POINTER(FloodResult)]),
+    "vrt_debug_flood_rounds": (C.c_int, [_P, C.POINTER(C.c_uint32)]),
     "vrt_scene_free": (None, [_P, _P]),
     "vrt_settings_default": (None, [C.POINTER(Settings)]),
     "vrt_render_geometry": (C.c_int, [_P, _P, C.POINTER(Push), C.POINTER(Settings), C.POINTER(Frame), C.POINTER(Shard)]),

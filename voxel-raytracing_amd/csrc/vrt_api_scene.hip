@@ -1,7 +1,7 @@
 // vrt_api_scene.hip -- the scenes of the C-ABI: construction (dense and bricks), sky and noise, memory, download, edits of dense
 // scenes and of reserved brick scenes, read-back (a box, a box's non-empty voxels, the scene as a .vox file), brushes and stamps
 // (an edit whose ids a kernel composes).  Host code only; the kernels are vrt_scene_build.hip, vrt_scene_edit.hip,
-// vrt_scene_read.hip and vrt_brush.hip.
+// vrt_scene_read.hip, vrt_brush.hip and vrt_flood.hip (flood fills: vrt_scene_flood, whose loop over rounds lives here).
 //
 // Call surface mirrored from the reference (paths relative to its root):
 //   VoxelScene ctor            source/voxels/resource/voxel_scene.cpp:33-133
@@ -16,6 +16,7 @@
 #include "vox_writer.h"
 #include "vrt_host.h"
 #include "vrt_brush_launch.h"          // (brings vrt_scene_read.h and its launchers)
+#include "vrt_flood_launch.h"
 
 using namespace vrt;
 
@@ -101,19 +102,20 @@ static void note_metallic(vrt_scene* s, const uint8_t* ids, size_t nbox, uint8_t
     else s->metallic_voxels = id != 0 && s->metal[id];
 }
 
-// Where the ids of an edited box come from: the host (uploaded), one id for the whole box, or -- a brush, a stamp -- a kernel
-// that composes them in the scratch memory, where the upload would have put them
+// Where the ids of an edited box come from: the host (uploaded), one id for the whole box, or -- a brush, a stamp, a flood -- a
+// kernel that composes them in the scratch memory, where the upload would have put them
 struct EditIds {
     const uint8_t*  host = nullptr;       // the box's ids in box-index order, or
-    uint8_t         id = 0;               // (host and compose both NULL) one id for the whole box, or
-    const BrushJob* compose = nullptr;    // launch_brush_compose's job, whose box is the edit's, and
-    const uint32_t* written = nullptr;    // the set of ids it writes (BrushRecord::ids)
-    bool boxed() const { return host != nullptr || compose != nullptr; }
+    uint8_t         id = 0;               // (host, compose and flood all NULL) one id for the whole box, or
+    const BrushJob* compose = nullptr;    // launch_brush_compose's job, whose box is the edit's, or
+    const FloodJob* flood = nullptr;      // launch_flood_compose's, likewise, and
+    const uint32_t* written = nullptr;    // the set of ids the kernel writes (BrushRecord::ids)
+    bool boxed() const { return host != nullptr || compose != nullptr || flood != nullptr; }
 };
 
 static void note_metallic(vrt_scene* s, const EditIds& src, size_t nbox)
 {
-    if (!src.compose) { note_metallic(s, src.host, nbox, src.id); return; }
+    if (!src.compose && !src.flood) { note_metallic(s, src.host, nbox, src.id); return; }
     for (int i = 1; i < 256 && !s->metallic_voxels; i++) s->metallic_voxels = ((src.written[i >> 5] >> (i & 31)) & 1u) != 0u && s->metal[i];
 }
 
@@ -121,6 +123,7 @@ static void note_metallic(vrt_scene* s, const EditIds& src, size_t nbox)
 static hipError_t edit_ids_to_scratch(vrt_ctx* c, const EditIds& src, uint8_t* dev, size_t nbox)
 {
     if (src.compose) return launch_brush_compose(*src.compose, dev, c->stream);
+    if (src.flood) return launch_flood_compose(*src.flood, dev, c->stream);
     return hipMemcpyAsync(dev, src.host, nbox, hipMemcpyHostToDevice, c->stream);
 }
 
@@ -247,7 +250,7 @@ uint64_t brick_scene_bytes(const vrt_scene* s)
 {
     const BrickDims b = brick_dims(s);
     return b.npad * 8ull + (uint64_t)s->bcap * 512ull * 9ull + 256 * sizeof(vrt_material) + (uint64_t)s->cells_room * 4ull +
-           b.npad * 4ull + b.n + 8ull * b.cstride + s->edit_scratch_bytes;
+           b.npad * 4ull + b.n + 8ull * b.cstride + s->edit_scratch_bytes + s->flood_scratch_bytes;
 }
 
 uint32_t brick_cell_code(uint32_t pc, int pbx, int pby)
@@ -651,6 +654,11 @@ int vrt_scene_trim(vrt_ctx* c, vrt_scene* s)
         s->edit_scratch.reset();
         s->bytes -= s->edit_scratch_bytes;
         s->edit_scratch_bytes = 0;
+    }
+    if (s->flood_scratch) {                                      // (a flood takes it again)
+        s->flood_scratch.reset();
+        s->bytes -= s->flood_scratch_bytes;
+        s->flood_scratch_bytes = 0;
     }
     return VRT_OK;
 }
@@ -1108,6 +1116,143 @@ int vrt_scene_stamp(struct vrt_ctx* c, vrt_scene* dst, const int32_t dst_lo[3], 
     const int rcb = brush_run(c, dst, j, clo, csize, name, result);
     HIPCHK(hipStreamSynchronize(c->stream));                       // (the staging buffer goes when this returns)
     return rcb;
+}
+
+} // extern "C"
+
+// ---- flood fills (vrt_scene_flood; csrc/vrt_flood.h) ---------------------------------------------------------------------------
+
+static_assert(VRT_FLOOD_SAME == VRT_FLOOD_MATCH_SAME && VRT_FLOOD_SOLID == VRT_FLOOD_MATCH_SOLID && VRT_FLOOD_FACES == VRT_FLOOD_CONN_FACES &&
+              VRT_FLOOD_CORNERS == VRT_FLOOD_CONN_CORNERS && VRT_FLOOD_MEASURE == VRT_FLOOD_FLAG_MEASURE,
+              "include/vrt.h and csrc/vrt_flood.h number the predicates, connectivities or flags differently");
+
+namespace {
+
+const uint32_t kFloodBatchMax = 32;     // rounds enqueued between two reads of the counters
+
+// The flood's scratch memory: passable mask | reached mask | two sets of activity flags | the rounds' counters | the record
+struct FloodScratch { uint8_t *passable, *reached; uint32_t *act[2], *counters; FloodRecord* rec; size_t zero_bytes; };
+
+bool flood_scratch_room(vrt_scene* s, size_t ntiles, FloodScratch* out)
+{
+    const size_t mask = ntiles * VRT_FLOOD_TILE_BYTES, flags = round256(ntiles * 4), counters = round256(kFloodBatchMax * 4), rec = round256(sizeof(FloodRecord));
+    const size_t need = 2 * mask + 2 * flags + counters + rec;
+    if (need > s->flood_scratch_bytes) {
+        if (s->flood_scratch) { s->flood_scratch.reset(); s->bytes -= s->flood_scratch_bytes; }
+        s->flood_scratch_bytes = 0;
+        if (s->flood_scratch.alloc(need) != hipSuccess) { (void)hipGetLastError(); return false; }
+        s->flood_scratch_bytes = need; s->bytes += need;
+    }
+    uint8_t* p = s->flood_scratch.get();
+    out->passable = p; out->reached = p + mask;
+    out->act[0] = (uint32_t*)(p + 2 * mask); out->act[1] = (uint32_t*)(p + 2 * mask + flags);
+    out->counters = (uint32_t*)(p + 2 * mask + 2 * flags);
+    out->rec = (FloodRecord*)(p + 2 * mask + 2 * flags + counters);
+    out->zero_bytes = 2 * mask + 2 * flags;
+    return true;
+}
+
+} // namespace
+
+extern "C" {
+
+int vrt_scene_flood(struct vrt_ctx* c, vrt_scene* s, const vrt_flood* flood, vrt_flood_result* result)
+{
+    const std::string name("vrt_scene_flood");
+    if (!c || !s || !flood || !result) return fail(VRT_ERR_INVALID, name + ": NULL argument");
+    if (flood->match != VRT_FLOOD_SAME && flood->match != VRT_FLOOD_SOLID) return fail(VRT_ERR_INVALID, name + ": unknown match (VRT_FLOOD_SAME or VRT_FLOOD_SOLID)");
+    if (flood->connectivity != VRT_FLOOD_FACES && flood->connectivity != VRT_FLOOD_CORNERS)
+        return fail(VRT_ERR_INVALID, name + ": connectivity is VRT_FLOOD_FACES (6) or VRT_FLOOD_CORNERS (26)");
+    if (flood->flags & ~(uint32_t)VRT_FLOOD_MEASURE) return fail(VRT_ERR_INVALID, name + ": unknown flag");
+    if (!flood_args_ok(flood->match, flood->connectivity, flood->flags, flood->size)) return fail(VRT_ERR_INVALID, name + ": each size of the bounds is in 1..2^30");
+    const bool measure = (flood->flags & VRT_FLOOD_MEASURE) != 0u;
+    const int32_t dim[3] = {s->d.vol.W, s->d.vol.H, s->d.vol.D};
+    int64_t lo[3], hi[3];
+    int32_t clo[3];
+    uint32_t csize[3];
+    for (int a = 0; a < 3; a++) { lo[a] = (int64_t)flood->lo[a]; hi[a] = (int64_t)flood->lo[a] + (int64_t)flood->size[a]; }
+    const bool any = brush_clip(lo, hi, dim, clo, csize);
+    if (any && !flood_sides_ok(csize))
+        return fail(VRT_ERR_INVALID, name + ": the bounds inside the volume have no side above " + std::to_string(VRT_FLOOD_MAX_SIDE) + "; flood in parts");
+    memset(result, 0, sizeof *result);
+    if (!measure && s->bricks && !s->reserved) return fail(VRT_ERR_UNSUPPORTED, name + ": a brick scene cannot be edited before vrt_scene_reserve_bricks");
+    if (!any || !flood_seed_inside(flood->seed, clo, csize)) return VRT_OK;      // bounds wholly outside the volume, or the seed outside them: nothing to do
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    std::lock_guard<std::mutex> lock(s->lazy);
+    FloodJob j{};
+    j.box = read_box_of(s, clo, csize);
+    flood_tiles(csize, j.nt);
+    for (int a = 0; a < 3; a++) { j.clo[a] = clo[a]; j.seed[a] = flood->seed[a]; }
+    j.match = flood->match; j.connectivity = flood->connectivity; j.id = flood->id;
+    const size_t ntiles = flood_tile_count(j.nt);
+    FloodScratch scr;
+    if (!flood_scratch_room(s, ntiles, &scr))
+        return fail(VRT_ERR_UNSUPPORTED, name + ": no device memory for the masks of " + std::to_string(ntiles) + " tiles; flood in parts");
+    j.passable = scr.passable; j.reached = scr.reached;
+    const FloodRecord init = flood_record_init();
+    FloodRecord rec = init;
+    HIPCHK(hipMemsetAsync(scr.passable, 0, scr.zero_bytes, c->stream));
+    HIPCHK(hipMemcpyAsync(scr.rec, &init, sizeof init, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(launch_flood_pass(j, scr.act[0], scr.rec, c->stream));
+    // the rounds, in batches: one read of the batch's counters each.  Every round that marked a tile gained a bit, so more of them
+    // than flood_round_bound cannot be
+    const uint64_t bound = flood_round_bound(csize);
+    uint64_t round = 0;
+    uint32_t batch = 4, marked[kFloodBatchMax];
+    for (bool done = false; !done;) {
+        HIPCHK(hipMemsetAsync(scr.counters, 0, batch * 4, c->stream));
+        for (uint32_t i = 0; i < batch; i++)
+            HIPCHK(launch_flood_round(j, scr.act[(round + i) & 1u], scr.act[(round + i + 1u) & 1u], i ? scr.counters + i - 1u : nullptr, scr.counters + i, c->stream));
+        HIPCHK(hipMemcpyAsync(marked, scr.counters, batch * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        for (uint32_t i = 0; i < batch && !done; i++) {
+            round++;
+            done = marked[i] == 0u;
+        }
+        if (!done && round > bound) return fail(VRT_ERR_HIP, name + ": internal error (more rounds than the bounds have voxels)");
+        batch = batch * 2u < kFloodBatchMax ? batch * 2u : kFloodBatchMax;
+    }
+    s->flood_rounds = (uint32_t)(round < 0xFFFFFFFFull ? round : 0xFFFFFFFFull);
+    HIPCHK(launch_flood_extent(j, scr.rec, c->stream));
+    HIPCHK(hipMemcpyAsync(&rec, scr.rec, sizeof rec, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    vrt_flood_result out{};
+    out.seed_id = rec.seed_id;
+    out.region = rec.region;
+    if (rec.region != 0ull) {
+        for (int a = 0; a < 3; a++) {
+            if (rec.mn[a] < clo[a] || rec.mx[a] < rec.mn[a] || (int64_t)rec.mx[a] >= (int64_t)clo[a] + (int64_t)csize[a])
+                return fail(VRT_ERR_HIP, name + ": internal error (the region's bounds leave the flood's)");
+            out.region_lo[a] = rec.mn[a]; out.region_size[a] = (uint32_t)(rec.mx[a] - rec.mn[a] + 1);
+        }
+    }
+    if (!measure && rec.edit.changed != 0ull) {                  // (else: nothing is written, no edit pass runs, the count planes' fields stay)
+        const VolumeView& d = s->d.vol;
+        EditBox b;
+        b.W = d.W; b.H = d.H; b.D = d.D;
+        for (int a = 0; a < 3; a++) {
+            if (rec.edit.mn[a] < clo[a] || rec.edit.mx[a] < rec.edit.mn[a] || (int64_t)rec.edit.mx[a] >= (int64_t)clo[a] + (int64_t)csize[a])
+                return fail(VRT_ERR_HIP, name + ": internal error (the changed voxels' bounds leave the flood's)");
+            b.lo[a] = rec.edit.mn[a]; b.hi[a] = rec.edit.mx[a] + 1;
+            j.box.lo[a] = b.lo[a]; j.box.size[a] = (uint32_t)(b.hi[a] - b.lo[a]);
+        }
+        EditIds src;
+        src.flood = &j; src.written = rec.edit.ids;
+        const int rc = scene_edit_locked(c, s, b, src, name);
+        if (rc != VRT_OK) return rc;
+        out.edit.changed = rec.edit.changed;
+        for (int a = 0; a < 3; a++) { out.edit.lo[a] = b.lo[a]; out.edit.size[a] = j.box.size[a]; }
+    }
+    *result = out;
+    return VRT_OK;
+}
+
+int vrt_debug_flood_rounds(const vrt_scene* s, uint32_t* rounds)
+{
+    if (!s || !rounds) return fail(VRT_ERR_INVALID, "vrt_debug_flood_rounds: NULL argument");
+    *rounds = s->flood_rounds;
+    return VRT_OK;
 }
 
 } // extern "C"

@@ -191,7 +191,12 @@ struct vrt_scene {
     bool metal[256] = {};
     vrt::DevBuf<uint8_t> edit_scratch;
     size_t edit_scratch_bytes = 0;
-    uint64_t shade_gen = 0;            // changes whenever something a hit's colour depends on does (creation, vrt_scene_set_sky)
+    // flood fills (vrt_scene_flood): the two masks, the activity flags, the rounds' counters and the record (vrt_flood_launch.h), kept
+    // from flood to flood, counted in `bytes`, dropped by vrt_scene_trim; and how many rounds the latest flood ran
+    vrt::DevBuf<uint8_t> flood_scratch;
+    size_t flood_scratch_bytes = 0;
+    uint32_t flood_rounds = 0;
+    uint64_t shade_gen = 0;           // changes whenever something a hit's colour depends on does (creation, vrt_scene_set_sky)
 };
 
 namespace vrt {

@@ -501,6 +501,42 @@ class VoxelScene:
                                           _capi.STAMP_SKIP_EMPTY if skip_empty else 0, C.byref(res)))
         return self._brush_result(res)
 
+    # ---- flood fills (vrt_scene_flood; csrc/vrt_flood.h) ---------------------------------------------------------------------
+    FLOOD_MATCHES = {"same": _capi.FLOOD_SAME, "solid": _capi.FLOOD_SOLID}
+
+    def _flood(self, seed, id, match, connectivity, bounds, flags):
+        mt = self.FLOOD_MATCHES[match] if isinstance(match, str) else int(match)
+        lo, size = ((0, 0, 0), (self.width, self.height, self.depth)) if bounds is None else bounds
+        if any(int(t) < 0 for t in size) or not 0 <= int(id) <= 255:
+            raise ValueError("VoxelScene.flood: negative size or id outside 0..255")
+        f = _capi.Flood(match=mt, connectivity=int(connectivity), flags=flags, id=int(id))
+        f.seed[:], f.lo[:], f.size[:] = [int(t) for t in seed], [int(t) for t in lo], [int(t) for t in size]
+        res = _capi.FloodResult()
+        self._raise(lib().vrt_scene_flood(self.engine.ctx, self.handle, C.byref(f), C.byref(res)))
+        return res
+
+    def flood(self, seed, id: int, match="same", connectivity: int = 6, bounds=None):
+        """Every voxel connected to `seed` becomes `id` (vrt_scene_flood).  match: "same" (voxels with the seed's id, 0 included:
+        the cavity fill) | "solid" (non-empty voxels); connectivity: 6 (faces) | 26 (faces, edges, corners); bounds: (lo, size)
+        the search stays in, None = the whole volume (no side of it inside the volume above 512).  Returns a dict: region (its
+        voxel count), region_lo, region_size, seed_id, and changed, lo, size as brush returns them."""
+        res = self._flood(seed, id, match, connectivity, bounds, 0)
+        return {"region": int(res.region), "region_lo": tuple(int(t) for t in res.region_lo), "region_size": tuple(int(t) for t in res.region_size),
+                "seed_id": int(res.seed_id), "changed": int(res.edit.changed), "lo": tuple(int(t) for t in res.edit.lo),
+                "size": tuple(int(t) for t in res.edit.size)}
+
+    def region(self, seed, match="same", connectivity: int = 6, bounds=None):
+        """How large the thing at `seed` is: (count, lo, size) of the region flood would rewrite; nothing is written
+        (VRT_FLOOD_MEASURE).  Works on every scene, brick scenes that were never reserved included."""
+        res = self._flood(seed, 0, match, connectivity, bounds, _capi.FLOOD_MEASURE)
+        return int(res.region), tuple(int(t) for t in res.region_lo), tuple(int(t) for t in res.region_size)
+
+    def flood_rounds(self) -> int:
+        """(diagnostics) rounds of the tile kernel the latest flood of this scene ran"""
+        n = C.c_uint32()
+        check(lib().vrt_debug_flood_rounds(self.handle, C.byref(n)))
+        return int(n.value)
+
     # ---- read-back (vrt_scene_read_box, vrt_scene_list_box, vrt_scene_save_vox_*) ---------------------------------------
     @staticmethod
     def _box(lo, size):

@@ -13,6 +13,9 @@
 // SHAPE box | sphere | ellipsoid | capsule, MODE set | paint | add | replace, PARAMS comma-separated in VOXEL units -- box
 // x,y,z,sx,sy,sz (whole voxels); sphere cx,cy,cz,r; ellipsoid cx,cy,cz,rx,ry,rz; capsule ax,ay,az,bx,by,bz,r (multiples of 0.5;
 // voxel (x, y, z) has its centre at x+.5, y+.5, z+.5) -- e.g. --brush sphere:paint:16,16,16,5.5:9 (VoxelScene::brush).  --save-vox OUT: the scene as it stands after that is written as a MagicaVoxel file (VoxelScene::save).
+// --flood X,Y,Z:MATCH:CONN:ID[:LOX,LOY,LOZ:SX,SY,SZ] (repeatable, in command-line order with --fill and --brush): every voxel connected
+// to the seed X,Y,Z becomes ID -- MATCH same | solid, CONN 6 | 26, inside the bounds if given, else in the whole volume
+// (VoxelScene::flood); e.g. --flood 16,16,16:same:6:9 fills the cavity around (16, 16, 16).
 // --read-box X Y Z SX SY SZ OUT: the ids of the box, x fastest, raw bytes (VoxelScene::read).  With either and no image output
 // (--out, --raw, --png) no frame is rendered.
 // Errors propagate as exceptions to run(), are printed, and the process exits with EXIT_FAILURE.
@@ -92,6 +95,39 @@ vrt_brush parseBrush(const std::string& spec)
     return b;
 }
 
+// --flood X,Y,Z:MATCH:CONN:ID[:LOX,LOY,LOZ:SX,SY,SZ]; without bounds size[0] stays 0 and the scene's dimensions are taken
+vrt_flood parseFlood(const std::string& spec)
+{
+    auto split = [](const std::string& t, char sep) {
+        std::vector<std::string> out; size_t at = 0;
+        for (;;) { const size_t e = t.find(sep, at); out.push_back(t.substr(at, e == std::string::npos ? e : e - at)); if (e == std::string::npos) break; at = e + 1; }
+        return out;
+    };
+    const std::vector<std::string> f = split(spec, ':');
+    if (f.size() != 4 && f.size() != 6) throw std::runtime_error("--flood wants X,Y,Z:MATCH:CONN:ID[:LOX,LOY,LOZ:SX,SY,SZ], got " + spec);
+    auto three = [&](const std::string& t) {
+        const std::vector<std::string> v = split(t, ',');
+        if (v.size() != 3) throw std::runtime_error("--flood: three comma-separated whole voxels, got " + t);
+        return std::array<long long, 3>{std::stoll(v[0]), std::stoll(v[1]), std::stoll(v[2])};
+    };
+    vrt_flood fl{};
+    const std::array<long long, 3> seed = three(f[0]);
+    for (size_t a = 0; a < 3; a++) fl.seed[a] = (int32_t)seed[a];
+    if (f[1] == "same") fl.match = VRT_FLOOD_SAME; else if (f[1] == "solid") fl.match = VRT_FLOOD_SOLID; else throw std::runtime_error("--flood: unknown match " + f[1]);
+    fl.connectivity = std::stoi(f[2]);
+    const unsigned long id = std::stoul(f[3]);
+    if (id > 255) throw std::runtime_error("--flood: ids are 0..255");
+    fl.id = (uint8_t)id;
+    if (f.size() == 6) {
+        const std::array<long long, 3> lo = three(f[4]), size = three(f[5]);
+        for (size_t a = 0; a < 3; a++) {
+            if (size[a] < 1 || size[a] > 0xFFFFFFFFll) throw std::runtime_error("--flood: a size of the bounds is outside 1..2^32-1");
+            fl.lo[a] = (int32_t)lo[a]; fl.size[a] = (uint32_t)size[a];
+        }
+    }
+    return fl;
+}
+
 int run(int argc, char** argv)
 {
     try {
@@ -102,7 +138,7 @@ int run(int argc, char** argv)
         int frames = 1; uint32_t windowW = 0, windowH = 0; float flyForward = 0, flyStrafe = 0, flyMouseX = 0; bool temporal = false, reproject = false, upsample = false;
         std::string dumpPushes, projection; std::vector<vrt_push> allPushes;
         struct Box { std::array<int32_t, 3> lo; std::array<uint32_t, 3> size; uint8_t id; };
-        struct SceneOp { bool isBrush; Box box; vrt_brush brush; };                    // --fill and --brush, in the order given
+        struct SceneOp { bool isBrush; Box box; vrt_brush brush; bool isFlood = false; vrt_flood flood{}; };   // --fill, --brush and --flood, in the order given
         std::vector<SceneOp> sceneOps; Box readBox{}; std::string saveVox, readBoxOut;
         for (int i = 1; i < argc; i++) {
             std::string a = argv[i];
@@ -119,6 +155,7 @@ int run(int argc, char** argv)
                 if (a == "--fill") { b.id = (uint8_t)std::stoul(next()); sceneOps.push_back(SceneOp{false, b, vrt_brush{}}); } else { readBox = b; readBoxOut = next(); }
             }
             else if (a == "--brush") sceneOps.push_back(SceneOp{true, Box{}, parseBrush(next())});
+            else if (a == "--flood") { SceneOp op{false, Box{}, vrt_brush{}}; op.isFlood = true; op.flood = parseFlood(next()); sceneOps.push_back(op); }
             else if (a == "--save-vox") saveVox = next();
             else if (a == "--width") settings->targetResolution[0] = (uint32_t)std::stoul(next());
             else if (a == "--height") settings->targetResolution[1] = (uint32_t)std::stoul(next());
@@ -175,6 +212,14 @@ int run(int argc, char** argv)
         if (!sky.empty()) scene->setSkybox(sky);
         if (!noise.empty()) scene->setBlueNoise(noise);
         for (const SceneOp& op : sceneOps) {
+            if (op.isFlood) {
+                vrt_flood fl = op.flood;
+                if (fl.size[0] == 0u) { fl.size[0] = scene->width; fl.size[1] = scene->height; fl.size[2] = scene->depth; }
+                const vrt_flood_result r = scene->flood(fl);
+                std::printf("flood: region of %llu voxels (id %u at the seed), %llu changed, box %d %d %d + %u %u %u\n", (unsigned long long)r.region, r.seed_id,
+                            (unsigned long long)r.edit.changed, r.edit.lo[0], r.edit.lo[1], r.edit.lo[2], r.edit.size[0], r.edit.size[1], r.edit.size[2]);
+                continue;
+            }
             if (!op.isBrush) { scene->fill(op.box.lo, op.box.size, op.box.id); continue; }
             const vrt_brush_result r = scene->brush(op.brush);
             std::printf("brush: %llu voxels changed, box %d %d %d + %u %u %u\n", (unsigned long long)r.changed, r.lo[0], r.lo[1], r.lo[2], r.size[0], r.size[1], r.size[2]);

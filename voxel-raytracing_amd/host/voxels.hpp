@@ -199,6 +199,39 @@ public:
         check(vrt_scene_stamp(engine->ctx, handle, dstLo.data(), src.handle, srcLo.data(), size.data(), orient, skipEmpty ? VRT_STAMP_SKIP_EMPTY : 0u, &r));
         return r;
     }
+    // Flood fills (no reference analogue; vrt_scene_flood): every voxel connected to `seed` becomes `id`.  match VRT_FLOOD_SAME (the
+    // seed's id, 0 included) | VRT_FLOOD_SOLID; connectivity VRT_FLOOD_FACES | VRT_FLOOD_CORNERS; the search stays in [lo, lo + size),
+    // without bounds in the whole volume.  flood takes the C structure; region measures and writes nothing (VRT_FLOOD_MEASURE).
+    vrt_flood_result flood(const vrt_flood& f) { vrt_flood_result r{}; check(vrt_scene_flood(engine->ctx, handle, &f, &r)); return r; }
+    vrt_flood floodOf(const std::array<int32_t, 3>& seed, uint8_t id, int32_t match, int32_t connectivity, uint32_t flags) const
+    {
+        vrt_flood f{};
+        for (size_t a = 0; a < 3; a++) f.seed[a] = seed[a];
+        f.size[0] = width; f.size[1] = height; f.size[2] = depth;
+        f.match = match; f.connectivity = connectivity; f.flags = flags; f.id = id;
+        return f;
+    }
+    vrt_flood_result flood(const std::array<int32_t, 3>& seed, uint8_t id, int32_t match = VRT_FLOOD_SAME, int32_t connectivity = VRT_FLOOD_FACES)
+    {
+        return flood(floodOf(seed, id, match, connectivity, 0u));
+    }
+    vrt_flood_result flood(const std::array<int32_t, 3>& seed, uint8_t id, int32_t match, int32_t connectivity, const std::array<int32_t, 3>& lo,
+                           const std::array<uint32_t, 3>& size)
+    {
+        vrt_flood f = floodOf(seed, id, match, connectivity, 0u);
+        for (size_t a = 0; a < 3; a++) { f.lo[a] = lo[a]; f.size[a] = size[a]; }
+        return flood(f);
+    }
+    vrt_flood_result region(const std::array<int32_t, 3>& seed, int32_t match = VRT_FLOOD_SAME, int32_t connectivity = VRT_FLOOD_FACES)
+    {
+        return flood(floodOf(seed, 0, match, connectivity, VRT_FLOOD_MEASURE));
+    }
+    vrt_flood_result region(const std::array<int32_t, 3>& seed, int32_t match, int32_t connectivity, const std::array<int32_t, 3>& lo, const std::array<uint32_t, 3>& size)
+    {
+        vrt_flood f = floodOf(seed, 0, match, connectivity, VRT_FLOOD_MEASURE);
+        for (size_t a = 0; a < 3; a++) { f.lo[a] = lo[a]; f.size[a] = size[a]; }
+        return flood(f);
+    }
     // A brick scene becomes editable, with room for `capacity` bricks in its pool (vrt_scene_reserve_bricks); edit / fill then work on it
     // Read-back (no reference analogue; vrt_scene_read_box / vrt_scene_list_box / vrt_scene_save_vox_file).  read: the ids of the
     // box [lo, lo + size), x fastest -- what edit takes.  voxels: the box's non-empty voxels (no side above 256), one word each,

@@ -403,6 +403,40 @@ typedef struct vrt_flood_result {
 int  vrt_scene_flood(struct vrt_ctx* ctx, vrt_scene* scene, const vrt_flood* flood, vrt_flood_result* result);
 /* (diagnostics) how many rounds of its tile kernel the scene's latest flood ran */
 int  vrt_debug_flood_rounds(const vrt_scene* scene, uint32_t* rounds);
+/* Mesh voxelization (no reference analogue): compose a triangle mesh into the scene on the device.  csrc/vrt_voxelize.h is the
+ * definition; it uses integers only, so which voxels a mesh covers is the same on every machine.  vertices: host int32[nv][3] in
+ * SIXTEENTHS of a voxel (voxel (x, y, z) is the closed cube [16x, 16x+16]^3), every coordinate in -65536..131072; triangles: host
+ * uint32[nt][3], indices into vertices; nt in 1..2^20, nv in 1..2^24.  fill: VRT_VOXELIZE_SURFACE covers every voxel whose closed
+ * cube meets a triangle (conservative, the 13-axis test with closed comparisons; degenerate triangles included),
+ * VRT_VOXELIZE_SOLID every voxel whose centre lies inside the mesh by parity along +x (an odd number of triangles cross the ray
+ * from the centre towards +x; top-left rule on the yz-projection, so a closed mesh fills the same voxels whatever the order,
+ * winding or subdivision of its triangles); both bits: the union.  The bounds [lo, lo+size) are in voxels; lo may be negative,
+ * each size in 1..2^30; they are clipped to the volume and the clipped bounds may have no side above 512 (VRT_ERR_INVALID:
+ * voxelize in parts).  Voxels outside the bounds never change, but triangles outside them still count for the parity: a solid
+ * voxelized in parts gives the same voxels as in one piece.  A covered voxel becomes `id` under mode VRT_BRUSH_SET, PAINT, ADD or
+ * REPLACE(match), with vrt_scene_brush's conditions on the ids.  result (not NULL): how many voxels of the bounds the mesh covers,
+ * and, as vrt_scene_brush's result, how many changed their id and their tight box.  Bounds wholly outside the volume: VRT_OK with
+ * a zero result.  When edit.changed == 0 nothing is written, no edit pass runs and the count planes' second set of fields is kept.
+ * Brick scenes, slot exhaustion (VRT_ERR_UNSUPPORTED, nothing changed), stream rules and the metallic rule are vrt_scene_brush's.
+ * A NULL argument, a zero count or one above its limit, an index >= nv, a coordinate out of range, an unknown mode or fill bit, a
+ * fill of 0, a size of 0 or above 2^30: VRT_ERR_INVALID before any device work.  A call that would test more than 2^31 candidate
+ * voxels (the triangles' bounding boxes cut to the bounds, summed): VRT_ERR_UNSUPPORTED, nothing changed.  The masks (1 or 2 bits
+ * per voxel of the clipped bounds) are kept with the scene between calls: vrt_scene_memory counts them, vrt_scene_trim drops
+ * them; VRT_ERR_UNSUPPORTED if they or the mesh's device copy cannot be had. */
+#define VRT_VOXELIZE_SURFACE 1u
+#define VRT_VOXELIZE_SOLID   2u
+typedef struct vrt_voxelize {
+    int32_t  lo[3]; uint32_t size[3];      /* bounds, voxels */
+    int32_t  mode; uint32_t fill;          /* VRT_BRUSH_* ; VRT_VOXELIZE_SURFACE | VRT_VOXELIZE_SOLID */
+    uint8_t  id, match;
+} vrt_voxelize;
+typedef struct vrt_voxelize_result { uint64_t covered; vrt_brush_result edit; } vrt_voxelize_result;
+int  vrt_scene_voxelize(struct vrt_ctx* ctx, vrt_scene* scene, const int32_t* vertices, uint32_t nv,
+                        const uint32_t* triangles, uint32_t nt, const vrt_voxelize* job, vrt_voxelize_result* result);
+/* (diagnostics) rows per work item of this scene's voxelizations from now on (0: the default), and how many work items the
+ * latest one launched (surface + solid) */
+int  vrt_debug_voxelize_item_rows(vrt_scene* scene, uint32_t rows);
+int  vrt_debug_voxelize_items(const vrt_scene* scene, uint32_t* items);
 void vrt_scene_free(vrt_ctx* ctx, vrt_scene* sc);            /* VoxelScene::destroy */
 
 /* ---- settings -------------------------------------------------------------------------------- */

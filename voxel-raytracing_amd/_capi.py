@@ -113,6 +113,20 @@ class FloodResult(C.Structure):
     _fields_ = [("region", C.c_uint64), ("region_lo", C.c_int32 * 3), ("region_size", C.c_uint32 * 3), ("seed_id", C.c_uint32), ("edit", BrushResult)]
 
 
+VOXELIZE_SURFACE, VOXELIZE_SOLID = 1, 2                                 # vrt_voxelize.fill (a bit set)
+VOXELIZE_UNIT = 16                                                      # mesh positions are in sixteenths of a voxel
+
+
+class Voxelize(C.Structure):
+    """vrt_voxelize: the bounds in voxels, the brush mode, which sets to cover, the id and REPLACE's match (csrc/vrt_voxelize.h)."""
+    _fields_ = [("lo", C.c_int32 * 3), ("size", C.c_uint32 * 3), ("mode", C.c_int32), ("fill", C.c_uint32), ("id", C.c_uint8), ("match", C.c_uint8)]
+
+
+class VoxelizeResult(C.Structure):
+    """vrt_voxelize_result: the voxels of the bounds the mesh covers, and the edit as vrt_scene_brush reports one."""
+    _fields_ = [("covered", C.c_uint64), ("edit", BrushResult)]
+
+
 MAX_QUERY_RAYS = 1 << 28       # rays per vrt_trace_rays / vrt_occluded_rays / vrt_pick_pixels / vrt_trace_segments / vrt_occluded_segments call
 
 assert C.sizeof(Push) == 96 and C.sizeof(Material) == 32
@@ -171,6 +185,9 @@ SYMBOLS = {
                                   C.POINTER(BrushResult)]),
     "vrt_scene_flood": (C.c_int, [_P, _P, C.POINTER(Flood), C.POINTER(FloodResult)]),
     "vrt_debug_flood_rounds": (C.c_int, [_P, C.POINTER(C.c_uint32)]),
+    "vrt_scene_voxelize": (C.c_int, [_P, _P, _P, C.c_uint32, _P, C.c_uint32, C.POINTER(Voxelize), C.POINTER(VoxelizeResult)]),
+    "vrt_debug_voxelize_item_rows": (C.c_int, [_P, C.c_uint32]),
+    "vrt_debug_voxelize_items": (C.c_int, [_P, C.POINTER(C.c_uint32)]),
     "vrt_scene_free": (None, [_P, _P]),
     "vrt_settings_default": (None, [C.POINTER(Settings)]),
     "vrt_render_geometry": (C.c_int, [_P, _P, C.POINTER(Push), C.POINTER(Settings), C.POINTER(Frame), C.POINTER(Shard)]),

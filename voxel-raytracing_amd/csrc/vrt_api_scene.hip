@@ -1,7 +1,8 @@
 // vrt_api_scene.hip -- the scenes of the C-ABI: construction (dense and bricks), sky and noise, memory, download, edits of dense
 // scenes and of reserved brick scenes, read-back (a box, a box's non-empty voxels, the scene as a .vox file), brushes and stamps
 // (an edit whose ids a kernel composes).  Host code only; the kernels are vrt_scene_build.hip, vrt_scene_edit.hip,
-// vrt_scene_read.hip, vrt_brush.hip and vrt_flood.hip (flood fills: vrt_scene_flood, whose loop over rounds lives here).
+// vrt_scene_read.hip, vrt_brush.hip, vrt_flood.hip (flood fills: vrt_scene_flood, whose loop over rounds lives here) and
+// vrt_voxelize.hip (mesh voxelization: vrt_scene_voxelize, whose cut of the triangles into work items lives here).
 //
 // Call surface mirrored from the reference (paths relative to its root):
 //   VoxelScene ctor            source/voxels/resource/voxel_scene.cpp:33-133
@@ -17,6 +18,7 @@
 #include "vrt_host.h"
 #include "vrt_brush_launch.h"          // (brings vrt_scene_read.h and its launchers)
 #include "vrt_flood_launch.h"
+#include "vrt_voxelize_launch.h"
 
 using namespace vrt;
 
@@ -108,14 +110,15 @@ struct EditIds {
     const uint8_t*  host = nullptr;       // the box's ids in box-index order, or
     uint8_t         id = 0;               // (host, compose and flood all NULL) one id for the whole box, or
     const BrushJob* compose = nullptr;    // launch_brush_compose's job, whose box is the edit's, or
-    const FloodJob* flood = nullptr;      // launch_flood_compose's, likewise, and
+    const FloodJob* flood = nullptr;      // launch_flood_compose's, likewise, or
+    const VoxJob*   voxelize = nullptr;   // launch_vox_compose's, likewise, and
     const uint32_t* written = nullptr;    // the set of ids the kernel writes (BrushRecord::ids)
-    bool boxed() const { return host != nullptr || compose != nullptr || flood != nullptr; }
+    bool boxed() const { return host != nullptr || compose != nullptr || flood != nullptr || voxelize != nullptr; }
 };
 
 static void note_metallic(vrt_scene* s, const EditIds& src, size_t nbox)
 {
-    if (!src.compose && !src.flood) { note_metallic(s, src.host, nbox, src.id); return; }
+    if (!src.compose && !src.flood && !src.voxelize) { note_metallic(s, src.host, nbox, src.id); return; }
     for (int i = 1; i < 256 && !s->metallic_voxels; i++) s->metallic_voxels = ((src.written[i >> 5] >> (i & 31)) & 1u) != 0u && s->metal[i];
 }
 
@@ -124,6 +127,7 @@ static hipError_t edit_ids_to_scratch(vrt_ctx* c, const EditIds& src, uint8_t* d
 {
     if (src.compose) return launch_brush_compose(*src.compose, dev, c->stream);
     if (src.flood) return launch_flood_compose(*src.flood, dev, c->stream);
+    if (src.voxelize) return launch_vox_compose(*src.voxelize, dev, c->stream);
     return hipMemcpyAsync(dev, src.host, nbox, hipMemcpyHostToDevice, c->stream);
 }
 
@@ -250,7 +254,7 @@ uint64_t brick_scene_bytes(const vrt_scene* s)
 {
     const BrickDims b = brick_dims(s);
     return b.npad * 8ull + (uint64_t)s->bcap * 512ull * 9ull + 256 * sizeof(vrt_material) + (uint64_t)s->cells_room * 4ull +
-           b.npad * 4ull + b.n + 8ull * b.cstride + s->edit_scratch_bytes + s->flood_scratch_bytes;
+           b.npad * 4ull + b.n + 8ull * b.cstride + s->edit_scratch_bytes + s->flood_scratch_bytes + s->voxelize_scratch_bytes;
 }
 
 uint32_t brick_cell_code(uint32_t pc, int pbx, int pby)
@@ -659,6 +663,11 @@ int vrt_scene_trim(vrt_ctx* c, vrt_scene* s)
         s->flood_scratch.reset();
         s->bytes -= s->flood_scratch_bytes;
         s->flood_scratch_bytes = 0;
+    }
+    if (s->voxelize_scratch) {                                   // (a voxelization takes it again)
+        s->voxelize_scratch.reset();
+        s->bytes -= s->voxelize_scratch_bytes;
+        s->voxelize_scratch_bytes = 0;
     }
     return VRT_OK;
 }
@@ -1252,6 +1261,163 @@ int vrt_debug_flood_rounds(const vrt_scene* s, uint32_t* rounds)
 {
     if (!s || !rounds) return fail(VRT_ERR_INVALID, "vrt_debug_flood_rounds: NULL argument");
     *rounds = s->flood_rounds;
+    return VRT_OK;
+}
+
+} // extern "C"
+
+// ---- mesh voxelization (vrt_scene_voxelize; csrc/vrt_voxelize.h) -----------------------------------------------------------------
+
+static_assert(VRT_VOXELIZE_SURFACE == VRT_VOXELIZE_FILL_SURFACE && VRT_VOXELIZE_SOLID == VRT_VOXELIZE_FILL_SOLID,
+              "include/vrt.h and csrc/vrt_voxelize.h number the fills differently");
+static_assert(VRT_BRUSH_SET == 0 && VRT_BRUSH_PAINT == 1 && VRT_BRUSH_ADD == 2 && VRT_BRUSH_REPLACE == 3, "vox_job_ok spells the modes as numbers");
+
+namespace {
+
+// The voxelization's scratch memory: coverage mask | toggle mask | the record
+struct VoxScratch { unsigned long long *cover, *toggle; VoxRecord* rec; size_t zero_bytes; };
+
+bool vox_scratch_room(vrt_scene* s, const uint32_t csize[3], bool solid, VoxScratch* out)
+{
+    const size_t rows = (size_t)csize[1] * csize[2];
+    const size_t cover = round256(rows * vox_cover_words(csize[0]) * 8u), toggle = solid ? round256(rows * vox_toggle_words(csize[0]) * 8u) : 0u;
+    const size_t need = cover + toggle + round256(sizeof(VoxRecord));
+    if (need > s->voxelize_scratch_bytes) {
+        if (s->voxelize_scratch) { s->voxelize_scratch.reset(); s->bytes -= s->voxelize_scratch_bytes; }
+        s->voxelize_scratch_bytes = 0;
+        if (s->voxelize_scratch.alloc(need) != hipSuccess) { (void)hipGetLastError(); return false; }
+        s->voxelize_scratch_bytes = need; s->bytes += need;
+    }
+    uint8_t* p = s->voxelize_scratch.get();
+    out->cover = (unsigned long long*)p;
+    out->toggle = solid ? (unsigned long long*)(p + cover) : nullptr;
+    out->rec = (VoxRecord*)(p + cover + toggle);
+    out->zero_bytes = cover + toggle;
+    return true;
+}
+
+} // namespace
+
+extern "C" {
+
+int vrt_scene_voxelize(struct vrt_ctx* c, vrt_scene* s, const int32_t* vertices, uint32_t nv, const uint32_t* triangles, uint32_t nt,
+                       const vrt_voxelize* job, vrt_voxelize_result* result)
+{
+    const std::string name("vrt_scene_voxelize");
+    if (!c || !s || !vertices || !triangles || !job || !result) return fail(VRT_ERR_INVALID, name + ": NULL argument");
+    if (nt < 1u || nt > VRT_VOXELIZE_MAX_TRIANGLES) return fail(VRT_ERR_INVALID, name + ": 1..2^20 triangles a call");
+    if (nv < 1u || nv > VRT_VOXELIZE_MAX_VERTICES) return fail(VRT_ERR_INVALID, name + ": 1..2^24 vertices a call");
+    if (job->mode < VRT_BRUSH_SET || job->mode > VRT_BRUSH_REPLACE) return fail(VRT_ERR_INVALID, name + ": unknown mode");
+    if (job->fill == 0u || (job->fill & ~(uint32_t)(VRT_VOXELIZE_SURFACE | VRT_VOXELIZE_SOLID)) != 0u)
+        return fail(VRT_ERR_INVALID, name + ": fill is VRT_VOXELIZE_SURFACE, VRT_VOXELIZE_SOLID or both");
+    if (!brush_mode_ok(job->mode, job->id, job->match))
+        return fail(VRT_ERR_INVALID, name + (job->mode == VRT_BRUSH_REPLACE ? ": REPLACE needs id != match" : ": PAINT and ADD need id != 0 (carve with SET)"));
+    if (!vox_job_ok(job->mode, job->id, job->match, job->fill, job->size)) return fail(VRT_ERR_INVALID, name + ": each size of the bounds is in 1..2^30");
+    for (size_t i = 0; i < (size_t)nv * 3u; i++)
+        if (!vox_coord_ok(vertices[i]))
+            return fail(VRT_ERR_INVALID, name + ": coordinate " + std::to_string(vertices[i]) + " of vertex " + std::to_string(i / 3u) + " is outside -65536..131072 (sixteenths of a voxel)");
+    for (size_t i = 0; i < (size_t)nt * 3u; i++)
+        if (triangles[i] >= nv) return fail(VRT_ERR_INVALID, name + ": triangle " + std::to_string(i / 3u) + " names vertex " + std::to_string(triangles[i]) + " of " + std::to_string(nv));
+    const int32_t dim[3] = {s->d.vol.W, s->d.vol.H, s->d.vol.D};
+    int64_t lo[3], hi[3];
+    int32_t clo[3];
+    uint32_t csize[3];
+    for (int a = 0; a < 3; a++) { lo[a] = (int64_t)job->lo[a]; hi[a] = (int64_t)job->lo[a] + (int64_t)job->size[a]; }
+    const bool any = brush_clip(lo, hi, dim, clo, csize);
+    if (any && !vox_sides_ok(csize))
+        return fail(VRT_ERR_INVALID, name + ": the bounds inside the volume have no side above " + std::to_string(VRT_VOXELIZE_MAX_SIDE) + "; voxelize in parts");
+    memset(result, 0, sizeof *result);
+    if (s->bricks && !s->reserved) return fail(VRT_ERR_UNSUPPORTED, name + ": a brick scene cannot be edited before vrt_scene_reserve_bricks");
+    if (!any) return VRT_OK;                                     // bounds wholly outside the volume: nothing to do
+    // the work items: every triangle's clipped box cut into slabs of rows (SURFACE) and of columns (SOLID)
+    const bool surface = (job->fill & VRT_VOXELIZE_SURFACE) != 0u, solid = (job->fill & VRT_VOXELIZE_SOLID) != 0u;
+    const uint32_t item_rows = s->voxelize_item_rows ? s->voxelize_item_rows : VRT_VOXELIZE_ITEM_ROWS;
+    std::vector<VoxItem> items[2];
+    uint64_t candidates = 0;
+    for (uint32_t t = 0; t < nt; t++) {
+        VoxTri T;
+        int32_t blo[3], bhi[3];
+        vox_tri_setup(vertices + 3u * (size_t)triangles[3u * (size_t)t], vertices + 3u * (size_t)triangles[3u * (size_t)t + 1u],
+                      vertices + 3u * (size_t)triangles[3u * (size_t)t + 2u], T);
+        for (int k = 0; k < 2; k++) {
+            if (!(k == 0 ? surface : solid) || !vox_tri_box(T, k == 1, clo, csize, blo, bhi)) continue;
+            const uint32_t rows = (uint32_t)(bhi[1] - blo[1] + 1) * (uint32_t)(bhi[2] - blo[2] + 1), step = k == 0 ? item_rows : item_rows * 64u;
+            candidates += k == 0 ? (uint64_t)rows * (uint64_t)(bhi[0] - blo[0] + 1) : (uint64_t)rows;
+            for (uint32_t f = 0; f < rows; f += step) items[k].push_back(VoxItem{t, f, rows - f < step ? rows - f : step});
+        }
+        if (candidates > VRT_VOXELIZE_MAX_CANDIDATES || items[0].size() + items[1].size() > VRT_VOXELIZE_MAX_ITEMS)
+            return fail(VRT_ERR_UNSUPPORTED, name + ": more than 2^31 candidate voxels or 2^24 work items (the triangles' boxes cut to the bounds); voxelize in parts");
+    }
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    std::lock_guard<std::mutex> lock(s->lazy);
+    VoxJob j{};
+    j.box = read_box_of(s, clo, csize);
+    for (int a = 0; a < 3; a++) { j.clo[a] = clo[a]; j.csize[a] = csize[a]; }
+    j.mode = job->mode; j.id = job->id; j.match = job->match;
+    VoxScratch scr;
+    if (!vox_scratch_room(s, csize, solid, &scr)) return fail(VRT_ERR_UNSUPPORTED, name + ": no device memory for the masks; voxelize in parts");
+    j.cover = scr.cover; j.toggle = scr.toggle;
+    // the mesh and the items, uploaded on the context's stream; they go when this returns
+    const size_t vbytes = (size_t)nv * 12u, tbytes = (size_t)nt * 12u, ibytes[2] = {items[0].size() * sizeof(VoxItem), items[1].size() * sizeof(VoxItem)};
+    const size_t voff = 0, toff = round256(vbytes), ioff0 = toff + round256(tbytes), ioff1 = ioff0 + round256(ibytes[0]);
+    DevBuf<uint8_t> mesh;
+    if (mesh.alloc(ioff1 + round256(ibytes[1]) + 256u) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(VRT_ERR_UNSUPPORTED, name + ": no device memory for the mesh and its work items");
+    }
+    HIPCHK(hipMemcpyAsync(mesh.get() + voff, vertices, vbytes, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(mesh.get() + toff, triangles, tbytes, hipMemcpyHostToDevice, c->stream));
+    if (ibytes[0]) HIPCHK(hipMemcpyAsync(mesh.get() + ioff0, items[0].data(), ibytes[0], hipMemcpyHostToDevice, c->stream));
+    if (ibytes[1]) HIPCHK(hipMemcpyAsync(mesh.get() + ioff1, items[1].data(), ibytes[1], hipMemcpyHostToDevice, c->stream));
+    j.vertices = (const int32_t*)(mesh.get() + voff); j.triangles = (const uint32_t*)(mesh.get() + toff);
+    const VoxRecord init = vox_record_init();
+    VoxRecord rec = init;
+    HIPCHK(hipMemsetAsync(scr.cover, 0, scr.zero_bytes, c->stream));
+    HIPCHK(hipMemcpyAsync(scr.rec, &init, sizeof init, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(launch_vox_surface(j, (const VoxItem*)(mesh.get() + ioff0), (uint32_t)items[0].size(), c->stream));
+    if (solid) {
+        HIPCHK(launch_vox_cross(j, (const VoxItem*)(mesh.get() + ioff1), (uint32_t)items[1].size(), c->stream));
+        HIPCHK(launch_vox_scan(j, c->stream));
+    }
+    s->voxelize_items = (uint32_t)(items[0].size() + items[1].size());
+    HIPCHK(launch_vox_extent(j, scr.rec, c->stream));
+    HIPCHK(hipMemcpyAsync(&rec, scr.rec, sizeof rec, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));                     // (the mesh's device copy is read no more)
+    vrt_voxelize_result out{};
+    out.covered = rec.covered;
+    if (rec.edit.changed != 0ull) {                              // (else: nothing is written, no edit pass runs, the count planes' fields stay)
+        const VolumeView& d = s->d.vol;
+        EditBox b;
+        b.W = d.W; b.H = d.H; b.D = d.D;
+        for (int a = 0; a < 3; a++) {
+            if (rec.edit.mn[a] < clo[a] || rec.edit.mx[a] < rec.edit.mn[a] || (int64_t)rec.edit.mx[a] >= (int64_t)clo[a] + (int64_t)csize[a])
+                return fail(VRT_ERR_HIP, name + ": internal error (the changed voxels' bounds leave the call's)");
+            b.lo[a] = rec.edit.mn[a]; b.hi[a] = rec.edit.mx[a] + 1;
+            j.box.lo[a] = b.lo[a]; j.box.size[a] = (uint32_t)(b.hi[a] - b.lo[a]);
+        }
+        EditIds src;
+        src.voxelize = &j; src.written = rec.edit.ids;
+        const int rc = scene_edit_locked(c, s, b, src, name);
+        if (rc != VRT_OK) return rc;
+        out.edit.changed = rec.edit.changed;
+        for (int a = 0; a < 3; a++) { out.edit.lo[a] = b.lo[a]; out.edit.size[a] = j.box.size[a]; }
+    }
+    *result = out;
+    return VRT_OK;
+}
+
+int vrt_debug_voxelize_item_rows(vrt_scene* s, uint32_t rows)
+{
+    if (!s) return fail(VRT_ERR_INVALID, "vrt_debug_voxelize_item_rows: NULL argument");
+    s->voxelize_item_rows = rows;
+    return VRT_OK;
+}
+
+int vrt_debug_voxelize_items(const vrt_scene* s, uint32_t* items)
+{
+    if (!s || !items) return fail(VRT_ERR_INVALID, "vrt_debug_voxelize_items: NULL argument");
+    *items = s->voxelize_items;
     return VRT_OK;
 }
 

@@ -196,6 +196,11 @@ struct vrt_scene {
     vrt::DevBuf<uint8_t> flood_scratch;
     size_t flood_scratch_bytes = 0;
     uint32_t flood_rounds = 0;
+    // mesh voxelization (vrt_scene_voxelize): the coverage and toggle masks and the record (vrt_voxelize_launch.h), kept, counted and
+    // dropped as the flood's; rows per work item (0: VRT_VOXELIZE_ITEM_ROWS) and how many items the latest call launched
+    vrt::DevBuf<uint8_t> voxelize_scratch;
+    size_t voxelize_scratch_bytes = 0;
+    uint32_t voxelize_item_rows = 0, voxelize_items = 0;
     uint64_t shade_gen = 0;           // changes whenever something a hit's colour depends on does (creation, vrt_scene_set_sky)
 };
 

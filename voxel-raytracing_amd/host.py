@@ -537,6 +537,45 @@ class VoxelScene:
         check(lib().vrt_debug_flood_rounds(self.handle, C.byref(n)))
         return int(n.value)
 
+    # ---- mesh voxelization (vrt_scene_voxelize; csrc/vrt_voxelize.h) ------------------------------------------------------
+    VOXELIZE_FILLS = {"surface": _capi.VOXELIZE_SURFACE, "solid": _capi.VOXELIZE_SOLID, "both": _capi.VOXELIZE_SURFACE | _capi.VOXELIZE_SOLID}
+
+    def voxelize(self, vertices, triangles, id: int, mode="set", fill="surface", bounds=None, match: int = 0):
+        """A triangle mesh composed into the scene (vrt_scene_voxelize).  vertices: integers [nv][3] in SIXTEENTHS of a voxel
+        (mesh_units converts floats in voxels); triangles: [nt][3] indices.  fill: "surface" (every voxel a triangle touches) |
+        "solid" (every voxel whose centre is inside the mesh, parity along +x) | "both"; mode as brush; bounds: (lo, size) in
+        voxels that may change, None = the mesh's own voxel bounds (no side of them inside the volume above 512).  Returns a dict:
+        covered (voxels of the bounds the mesh covers), and changed, lo, size as brush returns them."""
+        v = np.ascontiguousarray(np.asarray(vertices), np.int64).reshape(-1, 3)
+        t = np.ascontiguousarray(np.asarray(triangles), np.int64).reshape(-1, 3)
+        if v.size and (v.min() < -2 ** 31 or v.max() >= 2 ** 31) or t.size and (t.min() < 0 or t.max() >= 2 ** 32):
+            raise ValueError("VoxelScene.voxelize: vertices are int32, indices uint32")
+        if not 0 <= int(id) <= 255 or not 0 <= int(match) <= 255:
+            raise ValueError("VoxelScene.voxelize: ids in 0..255")
+        v32, t32 = np.ascontiguousarray(v, np.int32), np.ascontiguousarray(t, np.uint32)
+        md = self.BRUSH_MODES[mode] if isinstance(mode, str) else int(mode)
+        fl = self.VOXELIZE_FILLS[fill] if isinstance(fill, str) else int(fill)
+        lo, size = mesh_voxel_bounds(v32) if bounds is None else bounds
+        if any(int(s) < 0 for s in size):
+            raise ValueError("VoxelScene.voxelize: negative size")
+        job = _capi.Voxelize(mode=md, fill=fl, id=int(id), match=int(match))
+        job.lo[:], job.size[:] = [int(s) for s in lo], [int(s) for s in size]
+        res = _capi.VoxelizeResult()
+        self._raise(lib().vrt_scene_voxelize(self.engine.ctx, self.handle, v32.ctypes.data if v32.size else None, v32.shape[0],
+                                             t32.ctypes.data if t32.size else None, t32.shape[0], C.byref(job), C.byref(res)))
+        return {"covered": int(res.covered), "changed": int(res.edit.changed), "lo": tuple(int(s) for s in res.edit.lo),
+                "size": tuple(int(s) for s in res.edit.size)}
+
+    def voxelize_item_rows(self, rows: int):
+        """(diagnostics) rows per work item of this scene's voxelizations from now on; 0: the default"""
+        check(lib().vrt_debug_voxelize_item_rows(self.handle, int(rows)))
+
+    def voxelize_items(self) -> int:
+        """(diagnostics) work items the latest voxelization of this scene launched"""
+        n = C.c_uint32()
+        check(lib().vrt_debug_voxelize_items(self.handle, C.byref(n)))
+        return int(n.value)
+
     # ---- read-back (vrt_scene_read_box, vrt_scene_list_box, vrt_scene_save_vox_*) ---------------------------------------
     @staticmethod
     def _box(lo, size):
@@ -813,6 +852,48 @@ class VoxelScene:
             self.destroy()
         except Exception:
             pass
+
+
+def mesh_units(float_vertices) -> np.ndarray:
+    """Positions in voxels -> the integers vrt_scene_voxelize takes (sixteenths of a voxel): np.rint(np.float32(v) * 16) as int32.
+    The multiplication by 16 is exact in float32 (a power of two) and the rounding is to nearest, ties to even; this is the only
+    place floating point enters a voxelization."""
+    v = np.asarray(float_vertices, np.float32) * np.float32(_capi.VOXELIZE_UNIT)
+    return np.rint(v).astype(np.int32).reshape(-1, 3)
+
+
+def mesh_voxel_bounds(vertices):
+    """(lo, size) of the voxels whose closed cube [16x, 16x+16]^3 a mesh's vertices (sixteenths of a voxel) can touch"""
+    v = np.asarray(vertices, np.int64).reshape(-1, 3)
+    if v.size == 0:
+        return (0, 0, 0), (1, 1, 1)
+    lo = [-((-int(v[:, a].min())) // 16) - 1 for a in range(3)]
+    hi = [int(v[:, a].max()) // 16 for a in range(3)]
+    return tuple(lo), tuple(hi[a] - lo[a] + 1 for a in range(3))
+
+
+def read_obj(path):
+    """A minimal Wavefront OBJ reader -> (vertices in mesh units [nv][3] int32, triangles [nt][3] uint32): `v` and `f` lines only,
+    polygons as fans around their first corner, negative (relative) indices, everything after a `/` in a corner ignored.
+    Coordinates are taken as voxels and converted by mesh_units."""
+    verts, tris = [], []
+    with open(path, "r") as f:
+        for line in f:
+            w = line.split("#", 1)[0].split()
+            if not w:
+                continue
+            if w[0] == "v" and len(w) >= 4:
+                verts.append([float(w[1]), float(w[2]), float(w[3])])
+            elif w[0] == "f" and len(w) >= 4:
+                idx = []
+                for corner in w[1:]:
+                    i = int(corner.split("/", 1)[0])
+                    i = i - 1 if i > 0 else len(verts) + i
+                    if not 0 <= i < len(verts):
+                        raise ValueError(f"read_obj: {path}: face corner {corner} names no vertex read so far")
+                    idx.append(i)
+                tris.extend([idx[0], idx[k], idx[k + 1]] for k in range(1, len(idx) - 1))
+    return mesh_units(np.asarray(verts, np.float32).reshape(-1, 3)), np.asarray(tris, np.uint32).reshape(-1, 3)
 
 
 def load_image(path):

@@ -16,6 +16,10 @@
 // --flood X,Y,Z:MATCH:CONN:ID[:LOX,LOY,LOZ:SX,SY,SZ] (repeatable, in command-line order with --fill and --brush): every voxel connected
 // to the seed X,Y,Z becomes ID -- MATCH same | solid, CONN 6 | 26, inside the bounds if given, else in the whole volume
 // (VoxelScene::flood); e.g. --flood 16,16,16:same:6:9 fills the cavity around (16, 16, 16).
+// --voxelize FILE.obj:ID[:FILL[:MODE]] (repeatable, in command-line order with the others): the triangle mesh of a Wavefront OBJ file
+// becomes ID -- FILL surface (default) | solid | both, MODE set (default) | paint | add -- inside the mesh's own bounds
+// (VoxelScene::voxelize).  The reader is minimal: `v` and `f` lines, polygons as fans, negative indices, everything after a `/`
+// ignored; coordinates are voxels.
 // --read-box X Y Z SX SY SZ OUT: the ids of the box, x fastest, raw bytes (VoxelScene::read).  With either and no image output
 // (--out, --raw, --png) no frame is rendered.
 // Errors propagate as exceptions to run(), are printed, and the process exits with EXIT_FAILURE.
@@ -24,6 +28,7 @@
 #include <cstring>
 #include <fstream>
 #include <iostream>
+#include <sstream>
 
 #include "voxels.hpp"
 
@@ -128,6 +133,46 @@ vrt_flood parseFlood(const std::string& spec)
     return fl;
 }
 
+// --voxelize FILE.obj:ID[:FILL[:MODE]]
+struct VoxelizeOp { std::vector<int32_t> vertices; std::vector<uint32_t> triangles; uint8_t id = 0; uint32_t fill = VRT_VOXELIZE_SURFACE; int32_t mode = VRT_BRUSH_SET; };
+
+VoxelizeOp parseVoxelize(const std::string& spec)
+{
+    std::vector<std::string> f; size_t at = 0;
+    for (;;) { const size_t e = spec.find(':', at); f.push_back(spec.substr(at, e == std::string::npos ? e : e - at)); if (e == std::string::npos) break; at = e + 1; }
+    if (f.size() < 2 || f.size() > 4) throw std::runtime_error("--voxelize wants FILE.obj:ID[:FILL[:MODE]], got " + spec);
+    VoxelizeOp op;
+    const unsigned long id = std::stoul(f[1]);
+    if (id > 255) throw std::runtime_error("--voxelize: ids are 0..255");
+    op.id = (uint8_t)id;
+    if (f.size() > 2) { if (f[2] == "surface") op.fill = VRT_VOXELIZE_SURFACE; else if (f[2] == "solid") op.fill = VRT_VOXELIZE_SOLID; else if (f[2] == "both") op.fill = VRT_VOXELIZE_SURFACE | VRT_VOXELIZE_SOLID; else throw std::runtime_error("--voxelize: unknown fill " + f[2]); }
+    if (f.size() > 3) { if (f[3] == "set") op.mode = VRT_BRUSH_SET; else if (f[3] == "paint") op.mode = VRT_BRUSH_PAINT; else if (f[3] == "add") op.mode = VRT_BRUSH_ADD; else throw std::runtime_error("--voxelize: unknown mode " + f[3]); }
+    std::ifstream in(f[0]);
+    if (!in) throw std::runtime_error("--voxelize: cannot open " + f[0]);
+    std::string line;
+    while (std::getline(in, line)) {
+        const size_t hash = line.find('#');
+        if (hash != std::string::npos) line.resize(hash);
+        std::istringstream ls(line);
+        std::string key, w;
+        if (!(ls >> key)) continue;
+        if (key == "v") {
+            for (int a = 0; a < 3; a++) { if (!(ls >> w)) throw std::runtime_error("--voxelize: a vertex needs three coordinates: " + line); op.vertices.push_back(VoxelScene::meshUnits((float)std::stod(w))); }
+        } else if (key == "f") {
+            std::vector<uint32_t> idx;
+            const long long nv = (long long)(op.vertices.size() / 3);
+            while (ls >> w) {
+                const long long i = std::stoll(w.substr(0, w.find('/')));
+                const long long k = i > 0 ? i - 1 : nv + i;
+                if (k < 0 || k >= nv) throw std::runtime_error("--voxelize: face corner " + w + " names no vertex read so far");
+                idx.push_back((uint32_t)k);
+            }
+            for (size_t k = 1; k + 1 < idx.size(); k++) { op.triangles.push_back(idx[0]); op.triangles.push_back(idx[k]); op.triangles.push_back(idx[k + 1]); }
+        }
+    }
+    return op;
+}
+
 int run(int argc, char** argv)
 {
     try {
@@ -138,7 +183,7 @@ int run(int argc, char** argv)
         int frames = 1; uint32_t windowW = 0, windowH = 0; float flyForward = 0, flyStrafe = 0, flyMouseX = 0; bool temporal = false, reproject = false, upsample = false;
         std::string dumpPushes, projection; std::vector<vrt_push> allPushes;
         struct Box { std::array<int32_t, 3> lo; std::array<uint32_t, 3> size; uint8_t id; };
-        struct SceneOp { bool isBrush; Box box; vrt_brush brush; bool isFlood = false; vrt_flood flood{}; };   // --fill, --brush and --flood, in the order given
+        struct SceneOp { bool isBrush; Box box; vrt_brush brush; bool isFlood = false; vrt_flood flood{}; bool isVoxelize = false; VoxelizeOp voxelize{}; };   // --fill, --brush, --flood and --voxelize, in the order given
         std::vector<SceneOp> sceneOps; Box readBox{}; std::string saveVox, readBoxOut;
         for (int i = 1; i < argc; i++) {
             std::string a = argv[i];
@@ -156,6 +201,7 @@ int run(int argc, char** argv)
             }
             else if (a == "--brush") sceneOps.push_back(SceneOp{true, Box{}, parseBrush(next())});
             else if (a == "--flood") { SceneOp op{false, Box{}, vrt_brush{}}; op.isFlood = true; op.flood = parseFlood(next()); sceneOps.push_back(op); }
+            else if (a == "--voxelize") { SceneOp op{false, Box{}, vrt_brush{}}; op.isVoxelize = true; op.voxelize = parseVoxelize(next()); sceneOps.push_back(op); }
             else if (a == "--save-vox") saveVox = next();
             else if (a == "--width") settings->targetResolution[0] = (uint32_t)std::stoul(next());
             else if (a == "--height") settings->targetResolution[1] = (uint32_t)std::stoul(next());
@@ -212,6 +258,12 @@ int run(int argc, char** argv)
         if (!sky.empty()) scene->setSkybox(sky);
         if (!noise.empty()) scene->setBlueNoise(noise);
         for (const SceneOp& op : sceneOps) {
+            if (op.isVoxelize) {
+                const vrt_voxelize_result r = scene->voxelize(op.voxelize.vertices, op.voxelize.triangles, op.voxelize.id, op.voxelize.fill, op.voxelize.mode);
+                std::printf("voxelize: %llu voxels covered, %llu changed, box %d %d %d + %u %u %u\n", (unsigned long long)r.covered, (unsigned long long)r.edit.changed,
+                            r.edit.lo[0], r.edit.lo[1], r.edit.lo[2], r.edit.size[0], r.edit.size[1], r.edit.size[2]);
+                continue;
+            }
             if (op.isFlood) {
                 vrt_flood fl = op.flood;
                 if (fl.size[0] == 0u) { fl.size[0] = scene->width; fl.size[1] = scene->height; fl.size[2] = scene->depth; }

@@ -11,6 +11,7 @@
 //   Engine                                                             source/engine/engine.hpp:71-76 (device + stream only)
 #pragma once
 
+#include <algorithm>
 #include <array>
 #include <cmath>
 #include <cstdint>
@@ -231,6 +232,29 @@ public:
         vrt_flood f = floodOf(seed, 0, match, connectivity, VRT_FLOOD_MEASURE);
         for (size_t a = 0; a < 3; a++) { f.lo[a] = lo[a]; f.size[a] = size[a]; }
         return flood(f);
+    }
+    // Mesh voxelization (no reference analogue; vrt_scene_voxelize): a triangle mesh composed into the scene.  vertices: three int32
+    // per vertex in SIXTEENTHS of a voxel (meshUnits converts a position in voxels: nearest, ties to even, of float(v) * 16);
+    // triangles: three indices each.  fill VRT_VOXELIZE_SURFACE | VRT_VOXELIZE_SOLID, mode VRT_BRUSH_*; without bounds the mesh's own.
+    static int32_t meshUnits(float voxels) { return (int32_t)std::nearbyintf(voxels * 16.0f); }
+    vrt_voxelize_result voxelize(const std::vector<int32_t>& vertices, const std::vector<uint32_t>& triangles, const vrt_voxelize& job)
+    {
+        vrt_voxelize_result r{};
+        check(vrt_scene_voxelize(engine->ctx, handle, vertices.data(), (uint32_t)(vertices.size() / 3), triangles.data(), (uint32_t)(triangles.size() / 3), &job, &r));
+        return r;
+    }
+    vrt_voxelize_result voxelize(const std::vector<int32_t>& vertices, const std::vector<uint32_t>& triangles, uint8_t id, uint32_t fill = VRT_VOXELIZE_SURFACE,
+                                 int32_t mode = VRT_BRUSH_SET, uint8_t match = 0)
+    {
+        vrt_voxelize job{};
+        job.mode = mode; job.fill = fill; job.id = id; job.match = match;
+        for (size_t a = 0; a < 3 && vertices.size() >= 3; a++) {      // the voxels whose closed cube [16x, 16x+16] the vertices can touch
+            int32_t m = vertices[a], M = vertices[a];
+            for (size_t i = a; i < vertices.size(); i += 3) { m = std::min(m, vertices[i]); M = std::max(M, vertices[i]); }
+            const int32_t lo = (m + 15 >= 0 ? (m + 15) / 16 : -((-m) / 16)) - 1, hi = M >= 0 ? M / 16 : -((15 - M) / 16);
+            job.lo[a] = lo; job.size[a] = (uint32_t)(hi - lo + 1);
+        }
+        return voxelize(vertices, triangles, job);
     }
     // A brick scene becomes editable, with room for `capacity` bricks in its pool (vrt_scene_reserve_bricks); edit / fill then work on it
     // Read-back (no reference analogue; vrt_scene_read_box / vrt_scene_list_box / vrt_scene_save_vox_file).  read: the ids of the

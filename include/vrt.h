@@ -312,6 +312,49 @@ int  vrt_vox_encode_host(const uint8_t* voxels, const uint32_t dims[3], const vr
  * released with vrt_host_free.  _file: writes to path; a file that cannot be written: VRT_ERR_IO. */
 int  vrt_scene_save_vox_mem (struct vrt_ctx* ctx, const vrt_scene* scene, void** buf, size_t* n);
 int  vrt_scene_save_vox_file(struct vrt_ctx* ctx, const vrt_scene* scene, const char* path);
+/* Surface extraction (no reference analogue): the read-side twin of vrt_scene_voxelize.  csrc/vrt_faces.h is the definition,
+ * in plain integers.  Directions d: 0 = -x, 1 = +x, 2 = -y, 3 = +y, 4 = -z, 5 = +z.  Face d of a voxel of the box [lo, lo+size)
+ * with id != 0 is EXPOSED iff the voxel across it is empty; a neighbour outside the volume is empty, a neighbour outside the box
+ * but inside the volume is read from the scene (a scene extracted in parts gives exactly the faces of the scene extracted whole),
+ * unless VRT_FACES_CLOSED is set: then every voxel outside the box counts as empty and the box's faces are a closed surface.
+ * Without VRT_FACES_RUNS every exposed face is a record of length 1; with it, exposed faces of the same d and id that follow
+ * each other along the run axis (y for d = 0, 1; x otherwise) merge into a run, which also ends where the box-relative
+ * coordinate along that axis reaches a multiple of 64 (length 1 .. 64).  A record is one uint64: the vrt_scene_list_box word of
+ * the run's lowest voxel in bits 0 .. 31, length - 1 in bits 32 .. 37, d in bits 40 .. 42, every other bit 0.  Order: ascending d,
+ * within a d ascending key of the first voxel, the run axis fastest (d >= 2: x + y*size[0] + z*size[0]*size[1]; d < 2:
+ * y + (x + z*size[0])*size[1], relative coordinates) -- part of the contract, as vrt_scene_list_box's.
+ * records: HOST pointer to `capacity` entries.  counts[d] always receives the number of records of direction d; records == NULL
+ * (capacity ignored) only counts; a capacity below their sum writes nothing to records and returns VRT_ERR_INVALID with the
+ * counts set.  The errors of vrt_scene_list_box, or an unknown flag: VRT_ERR_INVALID before any device work; scan words or a
+ * staging buffer that cannot be allocated on the device (a 256^3 checkerboard has 50 M records): VRT_ERR_UNSUPPORTED, list the
+ * box in parts.  Dense scenes of every field layout and brick scenes, reserved or not; runs on the context's stream and waits
+ * for it, so a call enqueued after an edit sees the edit. */
+#define VRT_FACES_RUNS   1u
+#define VRT_FACES_CLOSED 2u
+int  vrt_scene_list_faces(struct vrt_ctx* ctx, const vrt_scene* scene, const int32_t lo[3], const uint32_t size[3], uint32_t flags,
+                          uint64_t* records, uint64_t capacity, uint64_t counts[6]);
+/* n records of a box at lo as quads (host only; no device needed).  The quad of a record lies in the plane axis(d) = coordinate
+ * (+ 1 for odd d), is `length` long along the run axis and 1 along the third; its corners start at the one with the lowest
+ * coordinates and run counter-clockwise seen from the empty side.  *vertices: int32 [*nv][3] in SIXTEENTHS OF A VOXEL, the unit
+ * vrt_scene_voxelize takes, volume coordinates, welded in order of first appearance; *quads: uint32 [n][4] indices into them;
+ * *ids: uint8 [n].  Release the three with vrt_host_free.  A word that is no record, or a NULL argument: VRT_ERR_INVALID. */
+int  vrt_faces_mesh_host(const uint64_t* records, uint64_t n, const int32_t lo[3], int32_t** vertices, uint64_t* nv,
+                         uint32_t** quads, uint8_t** ids);
+/* The same quads as a Wavefront OBJ and its material library, both in malloc'd host memory (vrt_host_free; host only).  The OBJ:
+ * `mtllib <mtl_name>`, the vertices as `v x y z` in integer VOXEL coordinates, then the quads as `f a b c d` under
+ * `usemtl id_<N>`, ascending N, within an N in the records' order.  The library: `newmtl id_<N>` and `Kd r g b` (the palette's
+ * diffuse colour, each float printed %.9g) for every id used, ascending. */
+int  vrt_faces_obj_host(const uint64_t* records, uint64_t n, const int32_t lo[3], const vrt_material palette[256],
+                        const char* mtl_name, void** obj, size_t* nobj, void** mtl, size_t* nmtl);
+/* A scene's whole surface as such an OBJ -- dense or bricks -- without ever holding its dense volume: the scene is cut into the
+ * tiles of vrt_scene_save_vox_*, x fastest, then y, then z; per tile one vrt_scene_list_faces with `flags`, then the tile's
+ * vertices and its groups as above (welded within a tile only; indices run on through the file).  flags: 0 or VRT_FACES_RUNS;
+ * VRT_FACES_CLOSED is refused with VRT_ERR_INVALID (the tiles would get seams).  _file: writes path and beside it the library,
+ * path with its extension replaced by .mtl, which the OBJ names without its directory; a file that cannot be written:
+ * VRT_ERR_IO. */
+int  vrt_scene_save_obj_mem (struct vrt_ctx* ctx, const vrt_scene* scene, const char* mtl_name, uint32_t flags, void** obj,
+                             size_t* nobj, void** mtl, size_t* nmtl);
+int  vrt_scene_save_obj_file(struct vrt_ctx* ctx, const vrt_scene* scene, const char* path, uint32_t flags);
 /* Scene brushes and stamps (no reference analogue): an edit whose ids are composed ON THE DEVICE -- paint a sphere, drag a
  * capsule, recolour what is solid, fill what is empty, replace one material, paste a box of one scene into another -- and which
  * rebuilds around the TIGHT box of the voxels that really change, not around the shape's bounds.  csrc/vrt_brush.h is the

@@ -7,7 +7,8 @@ from ._capi import (TRAVERSAL_AUTO, TRAVERSAL_DENSE, TRAVERSAL_BITMASK, TRAVERSA
                     DENOISE_CANONICAL, DENOISE_AS_SHIPPED, DENOISE_FAST, VrtError, lib)
 from .host import (AmbientOcclusionSettings, BlitStage, CameraController, CameraKey, DenoiserSettings, DenoiserStage, Engine,
                    FsrScaling, FsrSettings, GeometryBuffer, GeometryStage, LightSettings, RayCamera, ReprojectSettings, TraceSettings,
-                   UpscalerStage, camera_path,                   VoxelRenderSettings, VoxelRenderer, VoxelScene, load_image, make_push, make_shard, mesh_units, mesh_voxel_bounds, read_obj, vox_encode_host, vox_flatten_host,
+                   UpscalerStage, camera_path, faces_mesh, faces_obj_host, quads_to_triangles,
+                   VoxelRenderSettings, VoxelRenderer, VoxelScene, load_image, make_push, make_shard, mesh_units, mesh_voxel_bounds, read_obj, vox_encode_host, vox_flatten_host,
                    write_image)
 from . import synthetic
 from . import distributed

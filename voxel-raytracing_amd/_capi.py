@@ -115,6 +115,7 @@ class FloodResult(C.Structure):
 
 VOXELIZE_SURFACE, VOXELIZE_SOLID = 1, 2                                 # vrt_voxelize.fill (a bit set)
 VOXELIZE_UNIT = 16                                                      # mesh positions are in sixteenths of a voxel
+FACES_RUNS, FACES_CLOSED = 1, 2                                         # vrt_scene_list_faces' flags
 
 
 class Voxelize(C.Structure):
@@ -180,6 +181,12 @@ SYMBOLS = {
     "vrt_vox_encode_host": (C.c_int, [_P, C.POINTER(C.c_uint32), C.POINTER(Material), C.POINTER(_P), C.POINTER(C.c_size_t)]),
     "vrt_scene_save_vox_mem": (C.c_int, [_P, _P, C.POINTER(_P), C.POINTER(C.c_size_t)]),
     "vrt_scene_save_vox_file": (C.c_int, [_P, _P, C.c_char_p]),
+    "vrt_scene_list_faces": (C.c_int, [_P, _P, C.POINTER(C.c_int32), C.POINTER(C.c_uint32), C.c_uint32, _P, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "vrt_faces_mesh_host": (C.c_int, [_P, C.c_uint64, C.POINTER(C.c_int32), C.POINTER(_P), C.POINTER(C.c_uint64), C.POINTER(_P), C.POINTER(_P)]),
+    "vrt_faces_obj_host": (C.c_int, [_P, C.c_uint64, C.POINTER(C.c_int32), C.POINTER(Material), C.c_char_p, C.POINTER(_P), C.POINTER(C.c_size_t),
+                                     C.POINTER(_P), C.POINTER(C.c_size_t)]),
+    "vrt_scene_save_obj_mem": (C.c_int, [_P, _P, C.c_char_p, C.c_uint32, C.POINTER(_P), C.POINTER(C.c_size_t), C.POINTER(_P), C.POINTER(C.c_size_t)]),
+    "vrt_scene_save_obj_file": (C.c_int, [_P, _P, C.c_char_p, C.c_uint32]),
     "vrt_scene_brush": (C.c_int, [_P, _P, C.POINTER(Brush), C.POINTER(BrushResult)]),
     "vrt_scene_stamp": (C.c_int, [_P, _P, C.POINTER(C.c_int32), _P, C.POINTER(C.c_int32), C.POINTER(C.c_uint32), C.c_uint32, C.c_uint32,
                                   C.POINTER(BrushResult)]),

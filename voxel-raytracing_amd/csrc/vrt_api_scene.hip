@@ -840,9 +840,9 @@ int vrt_scene_download(vrt_ctx* c, const vrt_scene* s, uint8_t* voxels, vrt_mate
 
 // ---- scene read-back (vrt_scene_read_box, vrt_scene_list_box, vrt_scene_save_vox_*; csrc/vrt_scene_read.h) -------------------
 
-namespace {
+namespace vrt {
 
-// the box's checks, before any device work; *count: its voxels
+// the box's checks, before any device work; *count: its voxels (vrt_host.h: vrt_api_faces.hip makes them too)
 int read_box_checked(const vrt_scene* s, const int32_t lo[3], const uint32_t size[3], uint32_t max_side, const std::string& name, size_t* count)
 {
     const int32_t dim[3] = {s->d.vol.W, s->d.vol.H, s->d.vol.D};
@@ -865,6 +865,10 @@ ReadBox read_box_of(const vrt_scene* s, const int32_t lo[3], const uint32_t size
     for (int a = 0; a < 3; a++) { b.lo[a] = lo[a]; b.size[a] = size[a]; }
     return b;
 }
+
+} // namespace vrt
+
+namespace {
 
 // How many non-empty voxels the (checked) box has -> *total, and in `work` every segment's first record.  A box over empty
 // bricks only ends behind the bricks' entries.  Returns when the stream is done.

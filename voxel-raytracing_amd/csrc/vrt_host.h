@@ -213,6 +213,13 @@ int check_device_ptrs(vrt_ctx* c, int slot, const void* const* ptrs, int n, cons
 // vrt_api_scene.hip: the fields a launch that writes count planes marches through, built on first use
 int fields_for_counts(vrt_ctx* c, const vrt_scene* s, const uint8_t** out);
 
+// vrt_api_scene.hip: what the read-back calls make of a box before any device work (vrt_scene_read.h: read_box_check; the message
+// names `name`; *count: the box's voxels), and the checked box as the kernels take it.  ReadBox is vrt_scene_read.h's, for the
+// files that define VRT_SCENE_READ_LAUNCHERS.
+int read_box_checked(const vrt_scene* s, const int32_t lo[3], const uint32_t size[3], uint32_t max_side, const std::string& name, size_t* count);
+struct ReadBox;
+ReadBox read_box_of(const vrt_scene* s, const int32_t lo[3], const uint32_t size[3]);
+
 // May the kernels divide by W and H with a multiplication (screen_div_exact)?  The context remembers the last size examined.
 inline int screen_div_ok(vrt_ctx* c, int W, int H)
 {

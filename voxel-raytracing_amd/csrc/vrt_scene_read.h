@@ -96,6 +96,16 @@ struct ReadBox {
     int32_t         lo[3];
     uint32_t        size[3];
 };
+// the id of volume voxel (x, y, z), which lies inside the volume
+template <bool BRICK>
+__device__ __forceinline__ uint32_t read_voxel(const ReadBox& B, int x, int y, int z)
+{
+    if (!BRICK) return B.vox[(size_t)x + ((size_t)y + (size_t)z * (size_t)B.H) * (size_t)B.W];
+    const size_t pc = (size_t)((x >> 3) + 1) + ((size_t)((y >> 3) + 1) + (size_t)((z >> 3) + 1) * (size_t)B.pby) * (size_t)B.pbx;
+    const uint32_t ptr = ((const uint32_t*)B.bentry)[2u * pc] & 0xFFFFFFu;          // the entry's low word: pointer | open bits << 24
+    if (ptr == 0u || ptr > B.bcap) return 0u;                                      // empty (a border entry, 0xFFFFFF, cannot lie under a box inside the volume)
+    return B.bpool[(size_t)(ptr - 1u) * 512u + (size_t)((x & 7) | ((y & 7) << 3) | ((z & 7) << 6))];
+}
 // ids[read_box_index] of every voxel of the box (device memory, size[0] * size[1] * size[2] bytes)
 hipError_t launch_read_box(const ReadBox& b, uint8_t* ids, hipStream_t s);
 // bricks: how many of the bricks the box meets are occupied -> *occupied (device)
@@ -104,6 +114,8 @@ hipError_t launch_list_bricks(const ReadBox& b, uint32_t* occupied, hipStream_t 
 // work[segments] the number of records; launch_list_scatter then writes the `total` records (nothing at or beyond total).
 uint32_t   list_segments(const ReadBox& b);
 hipError_t launch_list_count(const ReadBox& b, uint32_t* work, hipStream_t s);
+// the scan alone: work[0 .. n) -> its exclusive scan in place, work[n] = the total (vrt_faces.hip scans its own counts with it)
+hipError_t launch_list_scan(uint32_t* work, uint32_t n, hipStream_t s);
 hipError_t launch_list_scatter(const ReadBox& b, const uint32_t* work, uint32_t total, uint32_t* records, hipStream_t s);
 #endif
 

@@ -12,16 +12,6 @@
 
 namespace vrt {
 
-template <bool BRICK>
-__device__ __forceinline__ uint32_t read_voxel(const ReadBox& B, int x, int y, int z)
-{
-    if (!BRICK) return B.vox[(size_t)x + ((size_t)y + (size_t)z * (size_t)B.H) * (size_t)B.W];
-    const size_t pc = (size_t)((x >> 3) + 1) + ((size_t)((y >> 3) + 1) + (size_t)((z >> 3) + 1) * (size_t)B.pby) * (size_t)B.pbx;
-    const uint32_t ptr = ((const uint32_t*)B.bentry)[2u * pc] & 0xFFFFFFu;          // the entry's low word: pointer | open bits << 24
-    if (ptr == 0u || ptr > B.bcap) return 0u;                                      // empty (a border entry, 0xFFFFFF, cannot lie under a box inside the volume)
-    return B.bpool[(size_t)(ptr - 1u) * 512u + (size_t)((x & 7) | ((y & 7) << 3) | ((z & 7) << 6))];
-}
-
 // blockIdx.y / .z: y and z within the box
 template <bool BRICK>
 __global__ __launch_bounds__(256) void k_read_box(const ReadBox B, uint8_t* __restrict__ ids)
@@ -146,6 +136,11 @@ hipError_t launch_list_count(const ReadBox& b, uint32_t* work, hipStream_t s)
     const uint32_t n = list_segments(b);
     if (b.vox) hipLaunchKernelGGL(k_list_count<false>, dim3((n + 3u) / 4u), dim3(256), 0, s, b, work);
     else       hipLaunchKernelGGL(k_list_count<true>, dim3((n + 3u) / 4u), dim3(256), 0, s, b, work);
+    return launch_list_scan(work, n, s);
+}
+
+hipError_t launch_list_scan(uint32_t* work, uint32_t n, hipStream_t s)
+{
     hipLaunchKernelGGL(k_list_scan, dim3(1), dim3(1024), 0, s, work, n);
     return hipGetLastError();
 }

@@ -621,6 +621,47 @@ class VoxelScene:
         """Write the scene as it stands to a .vox file (vrt_scene_save_vox_file)."""
         self._raise(lib().vrt_scene_save_vox_file(self.engine.ctx, self.handle, os.fsencode(path)))
 
+    # ---- surface extraction (vrt_scene_list_faces, vrt_scene_save_obj_*; csrc/vrt_faces.h) ------------------------------------
+    @staticmethod
+    def _face_flags(runs, closed):
+        return (_capi.FACES_RUNS if runs else 0) | (_capi.FACES_CLOSED if closed else 0)
+
+    def face_count(self, lo, size, runs=True, closed=False) -> np.ndarray:
+        """Records per direction (-x, +x, -y, +y, -z, +z) of a box with no side above 256 (vrt_scene_list_faces without records)."""
+        clo, csz = self._box(lo, size)
+        counts = (C.c_uint64 * 6)()
+        self._raise(lib().vrt_scene_list_faces(self.engine.ctx, self.handle, clo, csz, self._face_flags(runs, closed), None, 0, counts))
+        return np.array(counts[:], dtype=np.uint64)
+
+    def faces(self, lo, size, runs=True, closed=False):
+        """The exposed faces of a box with no side above 256 (vrt_scene_list_faces) -> (records, counts): uint64 records
+        list-box word | (length - 1) << 32 | d << 40 in ascending d and, within a d, ascending order key; counts uint64 (6,).
+        runs: faces of one id in a row along the run axis merge (up to 64); closed: every voxel outside the box is empty."""
+        clo, csz = self._box(lo, size)
+        flags = self._face_flags(runs, closed)
+        counts = (C.c_uint64 * 6)()
+        out = np.empty(int(self.face_count(lo, size, runs, closed).sum()), dtype=np.uint64)
+        self._raise(lib().vrt_scene_list_faces(self.engine.ctx, self.handle, clo, csz, flags, out.ctypes.data_as(C.c_void_p) if out.size else None,
+                                               out.size, counts))
+        got = np.array(counts[:], dtype=np.uint64)
+        assert int(got.sum()) == out.size
+        return out, got
+
+    def to_obj_bytes(self, mtl_name="scene.mtl", runs=True):
+        """The scene's surface as (OBJ bytes, MTL bytes) (vrt_scene_save_obj_mem); the OBJ names its library mtl_name."""
+        obj, mtl, nobj, nmtl = C.c_void_p(), C.c_void_p(), C.c_size_t(), C.c_size_t()
+        self._raise(lib().vrt_scene_save_obj_mem(self.engine.ctx, self.handle, os.fsencode(mtl_name), self._face_flags(runs, False), C.byref(obj),
+                                                 C.byref(nobj), C.byref(mtl), C.byref(nmtl)))
+        data = C.string_at(obj, nobj.value), C.string_at(mtl, nmtl.value)
+        lib().vrt_host_free(obj)
+        lib().vrt_host_free(mtl)
+        return data
+
+    def save_obj(self, path, runs=True) -> None:
+        """Write the scene's surface to a Wavefront OBJ and, beside it, its .mtl (vrt_scene_save_obj_file): quads in integer
+        voxel coordinates, grouped by id; read_obj reads the file back into mesh units."""
+        self._raise(lib().vrt_scene_save_obj_file(self.engine.ctx, self.handle, os.fsencode(path), self._face_flags(runs, False)))
+
     # ---- ray queries (vrt_trace_rays, vrt_occluded_rays, vrt_pick_pixels) ----------------------------------------------
     RAY_PLANES = {"material": (np.uint8, 1), "pos": (np.float32, 3), "voxel": (np.int32, 3), "normal": (np.int8, 3)}
 
@@ -894,6 +935,43 @@ def read_obj(path):
                     idx.append(i)
                 tris.extend([idx[0], idx[k], idx[k + 1]] for k in range(1, len(idx) - 1))
     return mesh_units(np.asarray(verts, np.float32).reshape(-1, 3)), np.asarray(tris, np.uint32).reshape(-1, 3)
+
+
+def faces_mesh(records, lo):
+    """Records of VoxelScene.faces for a box at lo -> (vertices int32 (nv, 3) in mesh units, welded in order of first appearance,
+    quads uint32 (n, 4), ids uint8 (n,)) (vrt_faces_mesh_host; host only).  A quad's corners start at its lowest corner and run
+    counter-clockwise seen from the empty side."""
+    r = np.ascontiguousarray(records, dtype=np.uint64).reshape(-1)
+    v, q, i, nv = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_uint64()
+    clo = (C.c_int32 * 3)(*[int(t) for t in lo])
+    VoxelScene._raise(lib().vrt_faces_mesh_host(r.ctypes.data_as(C.c_void_p) if r.size else None, r.size, clo, C.byref(v), C.byref(nv), C.byref(q), C.byref(i)))
+    n = int(nv.value)
+    verts = np.ctypeslib.as_array(C.cast(v, C.POINTER(C.c_int32)), shape=(max(n * 3, 1),))[:n * 3].copy().reshape(n, 3)
+    quads = np.ctypeslib.as_array(C.cast(q, C.POINTER(C.c_uint32)), shape=(max(r.size * 4, 1),))[:r.size * 4].copy().reshape(r.size, 4)
+    ids = np.ctypeslib.as_array(C.cast(i, C.POINTER(C.c_uint8)), shape=(max(r.size, 1),))[:r.size].copy()
+    for p in (v, q, i):
+        lib().vrt_host_free(p)
+    return verts, quads, ids
+
+
+def quads_to_triangles(quads) -> np.ndarray:
+    """Quads (n, 4) as fans around their first corner -> triangles uint32 (2n, 3): (a, b, c), (a, c, d), the quad's orientation kept"""
+    q = np.asarray(quads, np.uint32).reshape(-1, 4)
+    return np.stack([q[:, [0, 1, 2]], q[:, [0, 2, 3]]], axis=1).reshape(-1, 3)
+
+
+def faces_obj_host(records, lo, palette, mtl_name="scene.mtl"):
+    """Records of a box at lo -> (OBJ bytes, MTL bytes) (vrt_faces_obj_host; host only): what VoxelScene.save_obj writes for a
+    scene of one tile.  palette (256, 5) float32."""
+    r = np.ascontiguousarray(records, dtype=np.uint64).reshape(-1)
+    obj, mtl, nobj, nmtl = C.c_void_p(), C.c_void_p(), C.c_size_t(), C.c_size_t()
+    clo = (C.c_int32 * 3)(*[int(t) for t in lo])
+    VoxelScene._raise(lib().vrt_faces_obj_host(r.ctypes.data_as(C.c_void_p) if r.size else None, r.size, clo, materials_from_numpy(palette),
+                                               os.fsencode(mtl_name), C.byref(obj), C.byref(nobj), C.byref(mtl), C.byref(nmtl)))
+    data = C.string_at(obj, nobj.value), C.string_at(mtl, nmtl.value)
+    lib().vrt_host_free(obj)
+    lib().vrt_host_free(mtl)
+    return data
 
 
 def load_image(path):

@@ -20,7 +20,9 @@
 // becomes ID -- FILL surface (default) | solid | both, MODE set (default) | paint | add -- inside the mesh's own bounds
 // (VoxelScene::voxelize).  The reader is minimal: `v` and `f` lines, polygons as fans, negative indices, everything after a `/`
 // ignored; coordinates are voxels.
-// --read-box X Y Z SX SY SZ OUT: the ids of the box, x fastest, raw bytes (VoxelScene::read).  With either and no image output
+// --save-obj OUT.obj: the surface of the scene as it stands after the edits as a Wavefront OBJ of quads in voxel coordinates, grouped
+// by id, with its .mtl beside it (VoxelScene::saveObj).
+// --read-box X Y Z SX SY SZ OUT: the ids of the box, x fastest, raw bytes (VoxelScene::read).  With any of these and no image output
 // (--out, --raw, --png) no frame is rendered.
 // Errors propagate as exceptions to run(), are printed, and the process exits with EXIT_FAILURE.
 #include <cstdio>
@@ -184,7 +186,7 @@ int run(int argc, char** argv)
         std::string dumpPushes, projection; std::vector<vrt_push> allPushes;
         struct Box { std::array<int32_t, 3> lo; std::array<uint32_t, 3> size; uint8_t id; };
         struct SceneOp { bool isBrush; Box box; vrt_brush brush; bool isFlood = false; vrt_flood flood{}; bool isVoxelize = false; VoxelizeOp voxelize{}; };   // --fill, --brush, --flood and --voxelize, in the order given
-        std::vector<SceneOp> sceneOps; Box readBox{}; std::string saveVox, readBoxOut;
+        std::vector<SceneOp> sceneOps; Box readBox{}; std::string saveVox, saveObj, readBoxOut;
         for (int i = 1; i < argc; i++) {
             std::string a = argv[i];
             auto next = [&]() { if (i + 1 >= argc) throw std::runtime_error("missing value for " + a); return std::string(argv[++i]); };
@@ -203,6 +205,7 @@ int run(int argc, char** argv)
             else if (a == "--flood") { SceneOp op{false, Box{}, vrt_brush{}}; op.isFlood = true; op.flood = parseFlood(next()); sceneOps.push_back(op); }
             else if (a == "--voxelize") { SceneOp op{false, Box{}, vrt_brush{}}; op.isVoxelize = true; op.voxelize = parseVoxelize(next()); sceneOps.push_back(op); }
             else if (a == "--save-vox") saveVox = next();
+            else if (a == "--save-obj") saveObj = next();
             else if (a == "--width") settings->targetResolution[0] = (uint32_t)std::stoul(next());
             else if (a == "--height") settings->targetResolution[1] = (uint32_t)std::stoul(next());
             else if (a == "--pos") { pos.x = std::stof(next()); pos.y = std::stof(next()); pos.z = std::stof(next()); havePos = true; }
@@ -277,12 +280,13 @@ int run(int argc, char** argv)
             std::printf("brush: %llu voxels changed, box %d %d %d + %u %u %u\n", (unsigned long long)r.changed, r.lo[0], r.lo[1], r.lo[2], r.size[0], r.size[1], r.size[2]);
         }
         if (!saveVox.empty()) scene->save(saveVox);
+        if (!saveObj.empty()) scene->saveObj(saveObj);
         if (!readBoxOut.empty()) {
             const std::vector<uint8_t> ids = scene->read(readBox.lo, readBox.size);
             std::ofstream f(readBoxOut, std::ios::binary);
             if (!f.write((const char*)ids.data(), (std::streamsize)ids.size())) throw std::runtime_error("cannot write " + readBoxOut);
         }
-        if ((!saveVox.empty() || !readBoxOut.empty()) && out.empty() && raw.empty() && png.empty() && rays.empty() && hits.empty()) {
+        if ((!saveVox.empty() || !saveObj.empty() || !readBoxOut.empty()) && out.empty() && raw.empty() && png.empty() && rays.empty() && hits.empty()) {
             std::printf("scene %ux%ux%u written\n", scene->width, scene->height, scene->depth);
             return EXIT_SUCCESS;
         }

@@ -276,6 +276,22 @@ public:
         return rec;
     }
     void save(const std::string& path) const { check(vrt_scene_save_vox_file(engine->ctx, handle, path.c_str())); }
+    // Surface extraction (vrt_scene_list_faces / vrt_scene_save_obj_file; include/vrt.h has the record and the order).  faces: the
+    // exposed faces of a box (no side above 256) as records, flags = VRT_FACES_RUNS | VRT_FACES_CLOSED; counts (if given): records
+    // per direction.  saveObj: the whole surface as a Wavefront OBJ of quads and, beside it, its .mtl.
+    std::vector<uint64_t> faces(const std::array<int32_t, 3>& lo, const std::array<uint32_t, 3>& size, uint32_t flags = VRT_FACES_RUNS,
+                                std::array<uint64_t, 6>* counts = nullptr) const
+    {
+        std::array<uint64_t, 6> c{};
+        check(vrt_scene_list_faces(engine->ctx, handle, lo.data(), size.data(), flags, nullptr, 0, c.data()));
+        uint64_t n = 0;
+        for (const uint64_t k : c) n += k;
+        std::vector<uint64_t> rec((size_t)n);
+        if (n) check(vrt_scene_list_faces(engine->ctx, handle, lo.data(), size.data(), flags, rec.data(), n, c.data()));
+        if (counts) *counts = c;
+        return rec;
+    }
+    void saveObj(const std::string& path, bool runs = true) const { check(vrt_scene_save_obj_file(engine->ctx, handle, path.c_str(), runs ? VRT_FACES_RUNS : 0u)); }
     void reserveBricks(uint32_t capacity) { check(vrt_scene_reserve_bricks(engine->ctx, handle, capacity)); }
     void setSkybox(const float* rgba, uint32_t w, uint32_t h) { check(vrt_scene_set_sky(engine->ctx, handle, rgba, w, h)); }
     void setSkybox(const std::string& path) { check(vrt_scene_set_sky_file(engine->ctx, handle, path.c_str())); }          // Texture2D(.hdr)

@@ -25,6 +25,7 @@ def brush_host():
     l.brush_bounds_c.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     l.brush_bounds_c.restype = None
     l.brush_clip_c.argtypes = [C.c_void_p] * 5
+    l.brush_extent_ok_c.argtypes = [C.c_void_p] * 4
     l.brush_value_c.argtypes = [C.c_int32, C.c_uint32, C.c_uint32, C.c_uint32]
     l.brush_value_c.restype = C.c_uint32
     l.brush_inside_c.argtypes = [C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
@@ -69,6 +70,11 @@ def clip(lo, hi, dims):
     if not brush_host().brush_clip_c(lo.ctypes.data, hi.ctypes.data, dim.ctypes.data, clo.ctypes.data, cs.ctypes.data):
         return None
     return [int(v) for v in clo], [int(v) for v in cs]
+
+
+def extent_ok(mn, mx, clo, csize):
+    mn, mx, clo, cs = np.asarray(mn, np.int32), np.asarray(mx, np.int32), np.asarray(clo, np.int32), np.asarray(csize, np.uint32)
+    return bool(brush_host().brush_extent_ok_c(mn.ctypes.data, mx.ctypes.data, clo.ctypes.data, cs.ctypes.data))
 
 
 def inside(shape, p, xyz):

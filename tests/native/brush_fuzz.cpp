@@ -111,6 +111,13 @@ static int one_shape(int32_t shape, const int32_t p[9])
     if (brush_clip(lo, hi, dim, clo, cs))
         for (int a = 0; a < 3; a++)
             if (clo[a] < 0 || cs[a] == 0u || (int64_t)clo[a] + cs[a] > dim[a] || clo[a] < lo[a] || (int64_t)clo[a] + cs[a] > hi[a]) { fprintf(stderr, "clip leaves the volume or the bounds\n"); bad++; }
+    // the extent check: any int32 bounds against any clipped bounds up to the largest size, without overflow; the extremes both ways
+    const int32_t mn[3] = {(int32_t)rnd(), (int32_t)rnd(), (int32_t)rnd()}, mx[3] = {(int32_t)rnd(), (int32_t)rnd(), (int32_t)rnd()};
+    const int32_t top[3] = {INT32_MAX, INT32_MAX, INT32_MAX}, bot[3] = {INT32_MIN, INT32_MIN, INT32_MIN};
+    const uint32_t one[3] = {1u, 1u, 1u}, big[3] = {1u << 30, 1u << 30, 1u << 30};
+    (void)brush_extent_ok(mn, mx, mn, big);
+    (void)brush_extent_ok(mn, mx, top, big);
+    if (!brush_extent_ok(top, top, top, one) || !brush_extent_ok(bot, bot, bot, big) || brush_extent_ok(top, bot, bot, big)) { fprintf(stderr, "extent check at the extremes\n"); bad++; }
     return bad;
 }
 

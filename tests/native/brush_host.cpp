@@ -13,6 +13,7 @@ int brush_shape_ok_c(int32_t shape, const int32_t* p) { return brush_shape_ok(sh
 int brush_mode_ok_c(int32_t mode, uint32_t id, uint32_t match) { return brush_mode_ok(mode, id, match) ? 1 : 0; }
 void brush_bounds_c(int32_t shape, const int32_t* p, int64_t* lo, int64_t* hi) { brush_bounds(shape, p, lo, hi); }
 int brush_clip_c(const int64_t* lo, const int64_t* hi, const int32_t* dim, int32_t* clo, uint32_t* csize) { return brush_clip(lo, hi, dim, clo, csize) ? 1 : 0; }
+int brush_extent_ok_c(const int32_t* mn, const int32_t* mx, const int32_t* clo, const uint32_t* csize) { return brush_extent_ok(mn, mx, clo, csize) ? 1 : 0; }
 uint32_t brush_value_c(int32_t mode, uint32_t old, uint32_t id, uint32_t match) { return brush_value(mode, old, id, match); }
 
 // n voxels (x, y, z) -> out[i] = brush_inside

@@ -164,9 +164,9 @@ def _render(out, settings="default", res=BIG, scene="s", planes="gbuffer", **pos
 
 
 A = Case("A", "scene lifecycle",
-         "vrt_scene_set_sky / set_blue_noise: plain hipMemcpy behind their leading synchronise (vrt_api_scene.hip:37, :61); the build's cell "
-         "list (:165); the hit-colour table made at the first primary-only launch and made again after each sky (vrt_api.hip:647-653); "
-         "vrt_scene_download's plain D2H (:778)",
+         "vrt_scene_set_sky / set_blue_noise: plain hipMemcpy behind their leading synchronise (vrt_api_scene.hip:33, :57); the build's cell "
+         "list (:149); the hit-colour table made at the first primary-only launch and made again after each sky (vrt_api.hip:647-653); "
+         "vrt_scene_download's plain D2H (vrt_api_scene.hip:468)",
          [],
          [S("vrt_scene_from_dense", scene="s", volume="cubes32"),
           _render("a0", "primary_only", frame=1),
@@ -181,7 +181,7 @@ A = Case("A", "scene lifecycle",
          behind=1)        # the build waits for its own copies: what it enqueued before that wait is what the stall holds
 
 B = Case("B", "dense edits",
-         "the edit's hipMemcpyAsync from caller memory; the cell list's plain hipMemcpy (:165) between kernels; fields_for_counts "
+         "the edit's hipMemcpyAsync from caller memory; the cell list's plain hipMemcpy (vrt_api_scene.hip:149) between kernels; fields_for_counts "
          "building the count planes' fields after an edit dropped them",
          [S("vrt_scene_from_dense", scene="s", volume="sparse40")] + _textured() + [_render("w0", frame=1), _render("w1", frame=1)],
          [_render("b0", frame=1),
@@ -193,8 +193,8 @@ B = Case("B", "dense edits",
          behind=2)        # b0 (tag buffers made in SETUP) and the edit, which waits for b0 at entry
 
 C = Case("C", "brick edits",
-         "ptr_dev and list_dev (plain hipMemcpy between kernels, :337, :352); the device-to-device pool copies of "
-         "vrt_scene_reserve_bricks (:420-:421); brick_upload_cells (:253); the build's cell list (:590)",
+         "ptr_dev and list_dev (plain hipMemcpy between kernels, vrt_api_edit.hip:203, :218); the device-to-device pool copies of "
+         "vrt_scene_reserve_bricks (:380-:381); brick_upload_cells (:118); the build's cell list (vrt_api_scene.hip:334)",
          [],
          [S("vrt_scene_from_bricks", scene="s", volume="cubes48")] + _textured() +
          [_render("c0", frame=1),

@@ -207,6 +207,35 @@ def test_clipping():
     assert 0 < res[0] < 40 and res[1] == [0, 0, 0]
 
 
+def test_extent_check_at_its_edges():
+    """brush_extent_ok, the check between an extent kernel's record and the edit made from it, against its restatement in Python
+    integers: per axis (mn, mx, clo, csize) at each edge, the other two axes inside, so each axis in turn is the only failing one"""
+    def ok(mn, mx, clo, cs):
+        return all(mn[a] >= clo[a] and mx[a] >= mn[a] and mx[a] < clo[a] + cs[a] for a in range(3))
+
+    I32_MAX, I32_MIN = 2 ** 31 - 1, -2 ** 31
+    edges = [                                                   # (mn, mx, clo, csize) of one axis, and what the check makes of it
+        ((5, 11, 5, 7), True),                                  # mn == clo and mx == clo + csize - 1
+        ((5, 12, 5, 7), False),                                 # mx == clo + csize
+        ((4, 11, 5, 7), False),                                 # mn == clo - 1
+        ((9, 8, 5, 7), False),                                  # mx == mn - 1
+        ((I32_MAX, I32_MIN, 5, 7), False),                      # the record nothing touched
+        ((4095, 4095, 4095, 1), True),                          # the top of the largest volume
+        ((0, 2 ** 30 - 1, 0, 2 ** 30), True),                   # the 64-bit sum ...
+        ((0, 2 ** 30, 0, 2 ** 30), False),
+        ((I32_MAX, I32_MAX, I32_MAX, 1), True),                 # ... which a 32-bit one would wrap
+        ((I32_MAX, I32_MAX, I32_MAX - 1, 1), False),
+    ]
+    inside = (6, 9, 5, 7)
+    assert N.extent_ok(*([v] * 3 for v in inside)) and ok(*([v] * 3 for v in inside))
+    for a in range(3):
+        for edge, exp in edges:
+            args = [[edge[i] if b == a else inside[i] for b in range(3)] for i in range(4)]
+            assert ok(*args) == exp, (a, edge)
+            assert N.extent_ok(*args) == exp, (a, edge)
+    assert not N.extent_ok([I32_MAX] * 3, [I32_MIN] * 3, [0, 0, 0], [37, 29, 40])       # brush_record_init() on every axis
+
+
 def test_orientations_are_the_48_symmetries():
     size = (5, 3, 2)                                                                         # asymmetric: no two orientations coincide
     src = np.arange(1, 31, dtype=np.uint8).reshape(2, 3, 5)                                  # [z, y, x], every voxel its own id

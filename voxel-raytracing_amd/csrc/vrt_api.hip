@@ -1,6 +1,6 @@
 // vrt_api.hip -- the C-ABI of libvrt_hip.so (include/vrt.h): the error string, contexts and their options, device memory, the
 // host-only calls (settings defaults, images, .vox flattening, jitter), the geometry stage (vrt_render_rays included) and the instrumentation.  Scenes are in
-// vrt_api_scene.hip, the denoiser / strip packing / presentation / reprojection in vrt_api_post.hip, the ray queries in
+// vrt_api_scene.hip, their edits in vrt_api_edit.hip, the denoiser / strip packing / presentation / reprojection in vrt_api_post.hip, the ray queries in
 // vrt_api_query.hip, ray generation in vrt_api_rays.hip, RCCL in vrt_api_comm.hip; vrt_host.h is what they share.  Host code only; kernels live in the other .hip files.
 //
 // Call surface mirrored from the reference (paths relative to its root):

@@ -1,6 +1,6 @@
 // vrt_brick_edit.h -- which bytes of a brick scene an edit of a box of voxels can change (vrt_scene_edit_box on a scene that
 // vrt_scene_reserve_bricks made editable).  Plain integer arithmetic, compiled for the device (vrt_scene_edit.hip), the host
-// (vrt_api_scene.hip) and the tests (tests/native/brick_edit_host.cpp, which checks every statement below against a brute-force build).
+// (vrt_api_edit.hip) and the tests (tests/native/brick_edit_host.cpp, which checks every statement below against a brute-force build).
 //
 // The volume is a lattice of 8^3 bricks.  For an edit of the voxel box B = [lo, hi):
 //   T    the bricks B meets: the only bricks whose ids, pool slot and occupancy can change.

@@ -1,6 +1,6 @@
 // vrt_brush.h -- which voxels a brush covers and what they become (vrt_scene_brush), and how a stamp maps a box of one scene onto
 // another (vrt_scene_stamp).  Plain integer arithmetic, no floating point anywhere: coverage is a function of integers, so the
-// device (vrt_brush.hip), the host (vrt_api_scene.hip) and the tests (tests/native/brush_host.cpp, brush_fuzz.cpp, held against
+// device (vrt_brush.hip), the host (vrt_api_edit.hip) and the tests (tests/native/brush_host.cpp, brush_fuzz.cpp, held against
 // Python integers) agree bit for bit by construction.
 //
 // UNITS.  Shape positions are in HALF VOXELS (int32): the centre of voxel (x, y, z) is P = (2x+1, 2y+1, 2z+1), so a brush can
@@ -58,7 +58,7 @@
 #define VRT_BRUSH_HD inline
 #endif
 
-// (include/vrt.h has the same values for the C-ABI; vrt_api_scene.hip asserts that they agree)
+// (include/vrt.h has the same values for the C-ABI; vrt_api_edit.hip asserts that they agree)
 #define VRT_BRUSH_SHAPE_BOX 0
 #define VRT_BRUSH_SHAPE_ELLIPSOID 1
 #define VRT_BRUSH_SHAPE_CAPSULE 2
@@ -140,6 +140,15 @@ VRT_BRUSH_HD bool brush_clip(const int64_t lo[3], const int64_t hi[3], const int
         any = any && h > l;
     }
     return any;
+}
+
+// do the bounds [mn, mx] (max inclusive) that an extent kernel reports lie inside the clipped bounds [clo, clo + csize)?  A record
+// nothing touched (mn = INT32_MAX, mx = INT32_MIN) does not.  (Hidden: an out-of-line copy stays out of libvrt_hip.so's dynamic symbols.)
+__attribute__((visibility("hidden"))) VRT_BRUSH_HD bool brush_extent_ok(const int32_t mn[3], const int32_t mx[3], const int32_t clo[3], const uint32_t csize[3])
+{
+    for (int a = 0; a < 3; a++)
+        if (mn[a] < clo[a] || mx[a] < mn[a] || (int64_t)mx[a] >= (int64_t)clo[a] + (int64_t)csize[a]) return false;
+    return true;
 }
 
 // is voxel (x, y, z) inside the (checked) shape?

@@ -1,4 +1,4 @@
-// vrt_brush_launch.h -- what vrt_brush.hip's kernels are handed and their launchers, for vrt_brush.hip and vrt_api_scene.hip
+// vrt_brush_launch.h -- what vrt_brush.hip's kernels are handed and their launchers, for vrt_brush.hip and vrt_api_edit.hip
 // (behind <hip/hip_runtime.h>).  vrt_brush.h has the definitions.
 #pragma once
 

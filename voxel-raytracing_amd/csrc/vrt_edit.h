@@ -1,5 +1,5 @@
 // vrt_edit.h -- which bytes of a dense scene's clearance fields an edit of a box of voxels can change (vrt_scene_edit_box).
-// Plain integer arithmetic, compiled for the device (vrt_scene_edit.hip), the host (vrt_api_scene.hip) and the tests
+// Plain integer arithmetic, compiled for the device (vrt_scene_edit.hip), the host (vrt_api_edit.hip) and the tests
 // (tests/native/edit_host.cpp, which checks every statement below against a brute-force rebuild).
 //
 // Octant o has the signs s = (bit 0: +x, bit 1: +y, bit 2: +z; a clear bit: -).  c_o(p) = min(cap, distance in the octant's

@@ -1,5 +1,5 @@
 // vrt_flood.h -- which voxels a flood fill selects (vrt_scene_flood) and how the device finds them.  Plain integer arithmetic,
-// compiled for the device (vrt_flood.hip), the host (vrt_api_scene.hip) and the tests (tests/native/flood_host.cpp,
+// compiled for the device (vrt_flood.hip), the host (vrt_api_edit.hip) and the tests (tests/native/flood_host.cpp,
 // flood_fuzz.cpp, held against a plain BFS in Python integers, tests/flood_reference.py).
 //
 // DEFINITION.  The BOUNDS are [lo, lo + size) in voxels; lo may be negative, every size in 1..2^30.  They are cut to the volume
@@ -59,7 +59,7 @@
 #define VRT_FLOOD_HD inline
 #endif
 
-// (include/vrt.h has the same values for the C-ABI; vrt_api_scene.hip asserts that they agree)
+// (include/vrt.h has the same values for the C-ABI; vrt_api_edit.hip asserts that they agree)
 #define VRT_FLOOD_MATCH_SAME 0
 #define VRT_FLOOD_MATCH_SOLID 1
 #define VRT_FLOOD_CONN_FACES 6

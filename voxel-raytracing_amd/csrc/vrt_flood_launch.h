@@ -1,4 +1,4 @@
-// vrt_flood_launch.h -- what vrt_flood.hip's kernels are handed and their launchers, for vrt_flood.hip and vrt_api_scene.hip
+// vrt_flood_launch.h -- what vrt_flood.hip's kernels are handed and their launchers, for vrt_flood.hip and vrt_api_edit.hip
 // (behind <hip/hip_runtime.h>).  vrt_flood.h has the definitions, the layout of the masks and the wake-up invariant.
 #pragma once
 

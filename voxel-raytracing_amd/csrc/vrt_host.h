@@ -52,6 +52,25 @@ private:
     size_t bytes_ = 0;
 };
 
+// Scratch memory a scene keeps from one call to the next and counts in its `bytes` (`total` below)
+struct Scratch {
+    DevBuf<uint8_t> buf;
+    size_t bytes = 0;
+    uint8_t* get() const { return buf.get(); }
+    void drop(uint64_t& total) { if (buf) { buf.reset(); total -= bytes; } bytes = 0; }
+    hipError_t room(size_t need, uint64_t& total)     // grown to `need` bytes (contents are not kept); a failure leaves it empty
+    {
+        if (need <= bytes) return hipSuccess;
+        drop(total);
+        const hipError_t e = buf.alloc(need);
+        if (e == hipSuccess) { bytes = need; total += need; }
+        return e;
+    }
+};
+
+const size_t kMaxCells = (size_t)4u << 20;        // above it a scene goes without a cell list
+inline size_t round256(size_t n) { return (n + 255u) & ~(size_t)255u; }
+
 } // namespace vrt
 
 // Development switches of a context: A/B experiments and the tests' "the same frame without X" runs.  Each changes speed only,
@@ -189,18 +208,18 @@ struct vrt_scene {
     // scene edits (vrt_scene_edit_box): which materials are metallic, and the passes' scratch memory (kept from edit to edit, counted
     // in `bytes`, dropped by vrt_scene_trim)
     bool metal[256] = {};
-    vrt::DevBuf<uint8_t> edit_scratch;
-    size_t edit_scratch_bytes = 0;
+    vrt::Scratch edit_scratch;
     // flood fills (vrt_scene_flood): the two masks, the activity flags, the rounds' counters and the record (vrt_flood_launch.h), kept
     // from flood to flood, counted in `bytes`, dropped by vrt_scene_trim; and how many rounds the latest flood ran
-    vrt::DevBuf<uint8_t> flood_scratch;
-    size_t flood_scratch_bytes = 0;
+    vrt::Scratch flood_scratch;
     uint32_t flood_rounds = 0;
     // mesh voxelization (vrt_scene_voxelize): the coverage and toggle masks and the record (vrt_voxelize_launch.h), kept, counted and
     // dropped as the flood's; rows per work item (0: VRT_VOXELIZE_ITEM_ROWS) and how many items the latest call launched
-    vrt::DevBuf<uint8_t> voxelize_scratch;
-    size_t voxelize_scratch_bytes = 0;
+    vrt::Scratch voxelize_scratch;
     uint32_t voxelize_item_rows = 0, voxelize_items = 0;
+    // the three together: what brick_scene_bytes counts and vrt_scene_trim drops
+    size_t scratch_bytes() const { return edit_scratch.bytes + flood_scratch.bytes + voxelize_scratch.bytes; }
+    void drop_scratch() { edit_scratch.drop(bytes); flood_scratch.drop(bytes); voxelize_scratch.drop(bytes); }
     uint64_t shade_gen = 0;           // changes whenever something a hit's colour depends on does (creation, vrt_scene_set_sky)
 };
 
@@ -212,6 +231,15 @@ int check_device_ptrs(vrt_ctx* c, int slot, const void* const* ptrs, int n, cons
 
 // vrt_api_scene.hip: the fields a launch that writes count planes marches through, built on first use
 int fields_for_counts(vrt_ctx* c, const vrt_scene* s, const uint8_t** out);
+// vrt_api_scene.hip, for the edits too (vrt_api_edit.hip): a dense scene's clearance fields built into dst from the voxels on the
+// device (open: with the open cells coded 0), its cell list made again, the count planes' fields dropped (the next launch that
+// asks builds them again), and a brick's entry in the cell list from its index pc in the padded grid.  Hidden: they were one
+// file's statics, and the library's dynamic symbols stay what they were
+#define VRT_HIDDEN __attribute__((visibility("hidden")))
+VRT_HIDDEN hipError_t build_fields(vrt_ctx* c, const vrt_scene* s, uint8_t* dst, bool open);
+VRT_HIDDEN hipError_t build_cell_list(vrt_ctx* c, vrt_scene* s);
+VRT_HIDDEN void drop_count_fields(vrt_scene* s);
+VRT_HIDDEN uint32_t brick_cell_code(uint32_t pc, int pbx, int pby);
 
 // vrt_api_scene.hip: what the read-back calls make of a box before any device work (vrt_scene_read.h: read_box_check; the message
 // names `name`; *count: the box's voxels), and the checked box as the kernels take it.  ReadBox is vrt_scene_read.h's, for the

@@ -1,5 +1,5 @@
 // vrt_voxelize.h -- which voxels a triangle mesh covers (vrt_scene_voxelize).  Plain integer arithmetic, no floating point
-// anywhere: coverage is a function of integers, so the device (vrt_voxelize.hip), the host (vrt_api_scene.hip) and the tests
+// anywhere: coverage is a function of integers, so the device (vrt_voxelize.hip), the host (vrt_api_edit.hip) and the tests
 // (tests/native/voxelize_host.cpp, held against Python integers) agree bit for bit by construction.
 //
 // UNITS.  Positions are in SIXTEENTHS of a voxel (VRT_VOXELIZE_UNIT).  Voxel (x, y, z) is the closed cube [16x, 16x+16]^3, its
@@ -64,7 +64,7 @@
 #define VRT_VOXELIZE_MAX_VERTICES (1u << 24)
 #define VRT_VOXELIZE_MAX_SIDE 512u
 #define VRT_VOXELIZE_MAX_SIZE (1u << 30)
-// (include/vrt.h has the same values for the C-ABI; vrt_api_scene.hip asserts that they agree)
+// (include/vrt.h has the same values for the C-ABI; vrt_api_edit.hip asserts that they agree)
 #define VRT_VOXELIZE_FILL_SURFACE 1u
 #define VRT_VOXELIZE_FILL_SOLID 2u
 #define VRT_VOXELIZE_MAX_CANDIDATES (1ull << 31)   // the most candidate voxels (and columns) one call may test

@@ -1,5 +1,5 @@
 // vrt_voxelize_launch.h -- what vrt_voxelize.hip's kernels are handed and their launchers, for vrt_voxelize.hip and
-// vrt_api_scene.hip (behind <hip/hip_runtime.h>).  vrt_voxelize.h has the definitions and the layout of the masks.
+// vrt_api_edit.hip (behind <hip/hip_runtime.h>).  vrt_voxelize.h has the definitions and the layout of the masks.
 #pragma once
 
 #include "vrt_voxelize.h"

@@ -180,9 +180,11 @@ def cases():
     for mode in (0, 1):
         c += _cross("literal", [(2, 2.0), (3, 2.0), (2, 1.0)], [(2, 16), (3, 16)], [(70, 35), (64, 130)], mode=mode, options={"denoise_verified": 0})
     c.append(Case("literal", 70, 35, 2, 16, 3, 2.0, options={"denoise_verified": 0, "denoise_packed": 0}))
+    c.append(Case("literal", 70, 35, 2, 16, 3, 2.0, mode=1, options={"denoise_verified": 0, "denoise_packed": 0}))
     # (48 rows = 3 whole strips over 2 ranks, an extended strip of 22 rows: the untiled launch's last block has rows to spare)
     c.append(Case("literal", 70, 48, 2, 16, 2, 2.0, options={"denoise_verified": 0}))
-    # non-integral steps: the bilinear k_denoise
+    # non-integral steps: the bilinear k_denoise (pass 0 is k_denoise_p0 all the same, and pass 2 of (3, 1.5) has the integral tap offset 4:
+    # k_denoise_ver)
     c += _cross("bilinear", [(2, 2.5), (2, 0.75), (3, 1.5)], [(2, 16), (3, 16)], [(70, 50)])
     c.append(Case("bilinear", 70, 48, 2, 16, 2, 1.5))
     # a guard too large to verify with: weighted passes fall to k_denoise_lds

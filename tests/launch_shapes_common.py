@@ -79,10 +79,12 @@ def halo_map(H, rank, nranks, strip_rows, halo, direction, distributed):
 
 
 # ---- C. segment lengths ------------------------------------------------------------------------------------------------------------
-# RESTATEMENT of the two rules of launch_denoise_pass (csrc/vrt_denoise.hip), in Python, for whole frames and for a rank's strips:
+# RESTATEMENT of the two rules launch_denoise_pass (csrc/vrt_denoise.hip) sizes its launches by, in Python, for whole frames and for a rank's strips:
 # strip_ext is the height of what one walk covers (the frame; sharded: strip_rows + 2 * extend), total all rows of the launch (the
-# frame; sharded: strip_ext * local strips).  If the rule changes there, change it here, and choose the cases below anew: they are
-# only worth their time while they produce the lengths their rows state.
+# frame; sharded: strip_ext * local strips).  The rules themselves are denoise_plan's (csrc/vrt_denoise_plan.h), and
+# tests/test_launch_shapes_cpu.py holds this restatement to that function, on every row below and over a sweep of frames.  If the rule
+# changes there, change it here, and choose the cases below anew: they are only worth their time while they produce the lengths
+# their rows state.
 
 def pair_segments(W, total, strip_ext, R, pair_wgs):
     """(seg_rows, segments per strip, rows of the last segment) of a k_denoise_pair launch."""
@@ -157,6 +159,7 @@ VER_CASES = [
     VerCase(16384, 65, 2, 0.0, 0, [(1, 12, 5), (1, 20, 5)]),                      # pass 0 in segments of 12; a weighted pass with R = 1
     VerCase(16384, 37, 3, 2.0, 1, [(1, 8, 5), (3, 12, 1), (5, 12, 1)]),           # the as-shipped taps
     VerCase(16384, 65, 3, 1.0, 1, [(1, 12, 5), (2, 20, 5), (3, 20, 5)]),
+    VerCase(16384, 37, 2, 0.0, 1, [(1, 8, 5), (1, 12, 1)]),                       # ... with the tap offset at run time (RT = 0)
 ]
 
 
@@ -173,6 +176,12 @@ class ShardPairCase:
 FAST_SIZES = ((200, 120), (70, 13))
 FAST_STEPS = (2.0, 1.0)
 FAST_ITERATIONS = (2, 3, 4)
+FAST_SHARD = (70, 50, 2, 16, 2, 2.0)                # W, H, ranks, strip rows, iterations, step: k_denoise_lds<.., FAST> (extended strips of 16 rows)
+# VRT_DENOISE_FAST through the verified pass' cheap half, k_denoise_ver<.., FLAG = false> ("denoise_pair" = 0; the as-shipped taps take it
+# anyway): three column strips, five segments of 8 rows.  (iterations, step) -> the tap offsets of the weighted passes, which are the
+# kernel's RT: 2, 3 and 5 at compile time, 4 at run time (RT = 0)
+FAST_VER_SIZE = (130, 37)
+FAST_VER_SETTINGS = {(3, 1.0): (2, 3), (3, 2.0): (3, 5), (2, 3.0): (4,)}
 
 
 # ---- E. "tags_async" --------------------------------------------------------------------------------------------------------------

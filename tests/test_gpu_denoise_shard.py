@@ -6,17 +6,19 @@ no more than enough).  Its own rows of the result must equal oracle.denoise of t
 and in both ping-pong targets every row farther than the halo from all of its strips must still hold the bytes it was pre-filled
 with: a sharded pass reads own rows +- halo and writes own rows +- (halo - 1) at most.
 
-What launch_denoise_pass selects (csrc/vrt_denoise.hip), with R the tap offset i * stepWidth + 1 of pass i, ext the sum of the
+What launch_denoise_pass selects (csrc/vrt_denoise_plan.h), with R the tap offset i * stepWidth + 1 of pass i, ext the sum of the
 reaches of the later passes and per = strip_rows + 2 ext the height of an extended strip -- the `path` of a case names what it is for:
 
   pass 0, canonical taps, verified, "denoise_p0" = 1                                   k_denoise_p0            p0-ver, pair, edges, ...
   R integral in 2 .. 5, canonical taps, verified, "denoise_pair" = 1, per >= 64        k_denoise_pair<.., R>   pair
   R integral in 1 .. 5, verified (guard <= the limit; pass 0 always)                   k_denoise_ver           p0-ver, pair-p0-off,
-      (as-shipped taps: <SHIPPED>, pass 0: <.., PASS0>; VRT_DENOISE_FAST: FLAG = false)                        shipped, halo-gt-strip
+      (as-shipped taps: <SHIPPED>, pass 0: <.., PASS0>; VRT_DENOISE_FAST: FLAG = false)                        shipped, halo-gt-strip, edges,
+                                                                                                               pair (per < 64), bilinear (4)
   R integral in 1 .. 5, not verified ("denoise_verified" = 0 or the guard too large),
       per a multiple of 4                                                              k_denoise_lds           literal, guard
-  anything else (R not integral, R > 5, per not a multiple of 4)                       k_denoise               literal, bilinear
+  anything else (R not integral, R > 5, per not a multiple of 4)                       k_denoise               literal, bilinear, halo-gt-strip
   k_denoise_fast is never taken with a shard.
+tests/test_launch_shapes_cpu.py asks the library's own routing (csrc/vrt_denoise_plan.h) which of these every pass of every case takes.
 """
 import numpy as np
 import pytest

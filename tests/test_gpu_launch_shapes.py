@@ -430,7 +430,7 @@ def test_fast_kernel_within_one_code_per_pass(vrt, oracle, engine, size, step, m
 def test_sharded_fast_lds_kernel_within_one_code(vrt, oracle, engine):
     """The same mode with a shard: the FAST form of k_denoise_lds (extended strips of 16 rows).  Poisoned planes; one weighted pass
     on an exact pass 0: own rows at most one code from the oracle, rows beyond the halo untouched."""
-    W, H, N, S, it, step = 70, 50, 2, 16, 2, 2.0
+    W, H, N, S, it, step = lsc.FAST_SHARD
     halo = dsc.halo_rows(it, step)
     rng = np.random.default_rng(23)
     with engine.options(denoise_verified=0):
@@ -445,6 +445,25 @@ def test_sharded_fast_lds_kernel_within_one_code(vrt, oracle, engine):
                         got = dsc.run_rank(vrt, engine, st, dsc.poisoned(truth, H, rank, N, S, halo, kind, rng), rank, N, S, halo, rng)
                         d = int(np.abs(got[own].astype(np.int32) - exp[own].astype(np.int32)).max())
                         assert d <= it - 1, (gkind, mode, rank, kind, d)
+
+
+@pytest.mark.parametrize("mode", [0, 1])
+def test_fast_ver_kernel_within_one_code_per_pass(vrt, oracle, engine, mode):
+    """VRT_DENOISE_FAST with "denoise_pair" = 0: the weighted passes take the cheap half of k_denoise_ver alone (FLAG = false), with the
+    tap offsets 2, 3 and 5 at compile time and 4 at run time (lsc.FAST_VER_SETTINGS).  The bound of include/vrt.h, non-finite
+    positions included: at most one code per channel and weighted pass, so iterations - 1 codes end to end against the oracle."""
+    W, H = lsc.FAST_VER_SIZE
+    for gkind in ("hostile", "smooth"):
+        truth = dsc.gbuffer(gkind, W, H)
+        planes = _dev_planes(engine, truth)
+        for iterations, step in lsc.FAST_VER_SETTINGS:
+            exp = oracle.denoise(*truth, iterations=iterations, step_width0=step, mode=mode)
+            st = _den_settings(vrt, W, H, iterations, step, mode | vrt.DENOISE_FAST)
+            with engine.options(denoise_pair=0):
+                got = vrt.DenoiserStage(engine, st).record(*planes).cpu().numpy()
+            d = int(np.abs(got.astype(np.int32) - exp.astype(np.int32)).max())
+            print(f"k_denoise_ver FAST {gkind} mode {mode} iterations {iterations} step {step}: {d} codes")
+            assert d <= iterations - 1, (gkind, mode, iterations, step, d)
 
 
 # ---- E. tags_async ----------------------------------------------------------------------------------------------------------------

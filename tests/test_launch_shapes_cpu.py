@@ -9,6 +9,7 @@ import re
 import numpy as np
 import pytest
 
+import denoise_plan_native as dpn
 import denoise_shard_common as dsc
 import launch_shapes_common as lsc
 
@@ -132,3 +133,217 @@ def test_sharded_pair_case_produces_the_stated_segments(vrt):
         assert (seg, last) == (c.seg_rows, c.last) and segs >= 2 and last < c.R
         assert seg != lsc.pair_segments(c.W, n_local * c.per, c.per, c.R, 0)[0]   # not what the launch would choose by itself
     assert _guard(vrt, c.iterations, c.step, 0, 1) <= GUARD_MAX
+
+
+# ---- the tables held to the code: denoise_plan (csrc/vrt_denoise_plan.h), the function launch_denoise_pass launches by, built for the host
+# (tests/native/denoise_plan_host.cpp) and given what vrt_denoise gives it (tests/denoise_plan_native.py: passes) ---------------------------
+
+def _segments(q, strip_ext):
+    return q.seg_rows, q.segs, strip_ext - (q.segs - 1) * q.seg_rows
+
+
+def test_restated_segment_rules_are_the_plans_on_every_table_row(vrt):
+    for c in lsc.PAIR_CASES:
+        for mode in (0, dpn.DENOISE_FAST):                                          # (the GPU test runs both)
+            p0, w = dpn.passes(vrt, c.W, c.H, c.iterations, c.step, mode, options={"denoise_pair_wgs": c.pair_wgs})
+            assert p0.name == "k_denoise_p0" and w.name == "k_denoise_pair" and w.pair_R == c.R and w.FLAG == (mode == 0)
+            assert _segments(w, c.H) == lsc.pair_segments(c.W, c.H, c.H, c.R, c.pair_wgs)
+            assert (w.seg_rows, _segments(w, c.H)[2]) == (c.seg_rows, c.last)
+    for c in lsc.VER_CASES:
+        ps = dpn.passes(vrt, c.W, c.H, c.iterations, c.step, c.mode, options={"denoise_pair": 0, "denoise_p0": 0})
+        assert len(ps) == len(c.passes)
+        for i, (q, (R, seg_rows, last)) in enumerate(zip(ps, c.passes)):
+            assert q.name == "k_denoise_ver" and (q.R, q.SHIPPED, q.PASS0, q.FLAG) == (R, c.mode & 1, int(i == 0), 1), (c.id, i)
+            assert _segments(q, c.H) == lsc.ver_segments(c.W, c.H, c.H, i == 0)
+            assert (q.seg_rows, _segments(q, c.H)[2]) == (seg_rows, last)
+    c = lsc.ShardPairCase
+    for rank in range(c.nranks):
+        w = dpn.passes(vrt, c.W, c.H, c.iterations, c.step, 0, options={"denoise_pair_wgs": c.pair_wgs}, shard=(rank, c.nranks, c.strip_rows))[-1]
+        assert w.name == "k_denoise_pair" and w.pair_R == c.R and w.grid_y == w.segs * c.local_strips[rank]
+        assert _segments(w, c.per) == lsc.pair_segments(c.W, c.local_strips[rank] * c.per, c.per, c.R, c.pair_wgs)
+        assert (w.seg_rows, _segments(w, c.per)[2]) == (c.seg_rows, c.last)
+
+
+def test_restated_segment_rules_are_the_plans_everywhere():
+    """pair_segments / ver_segments against the plan over frames the tables do not hold: W = 1, W one below, at and one above a multiple
+    of the strip width (64 - 2 R; 64 for k_denoise_ver), heights below 2 R, whole frames and a rank's extended strips, the knob off and forced."""
+    n = {"k_denoise_pair": 0, "k_denoise_ver": 0}
+    for R in range(1, 6):
+        ow = 64 - 2 * R
+        Ws = sorted({1, ow - 1, ow, ow + 1, 3 * ow - 1, 3 * ow, 3 * ow + 1, 63, 64, 65, 191, 192, 193, 4097, 16384})
+        Hs = sorted({1, 2, 3, 2 * R - 1, 2 * R, 2 * R + 1, 8, 9, 47, 48, 49, 117, 361, 925, 2160})
+        shapes = [(H, H, dict()) for H in Hs]                                      # (total rows, strip height, the shard)
+        shapes += [(local * (strip + 2 * ext), strip + 2 * ext, dict(nranks=2, strip_rows=strip, n_local_strips=local, extend=ext))
+                   for strip in (16, 64, 80) for ext in (0, 3, 8) for local in (1, 2, 3)]
+        for W in Ws:
+            for total, per, shard in shapes:
+                H = total if not shard else 2 * shard["strip_rows"] * shard["n_local_strips"] - 5
+                for pw in (0, 1, 3, 21, 60, 4096):
+                    q = dpn.plan(W, H, float(R), False, pair_wgs=pw, **shard)
+                    pair = R >= 2 and (not shard or per >= 64)
+                    assert q.name == ("k_denoise_pair" if pair else "k_denoise_ver"), (W, H, R, pw, shard)
+                    want = lsc.pair_segments(W, total, per, R, pw) if pair else lsc.ver_segments(W, total, per, False)
+                    assert _segments(q, per) == want, (W, H, R, pw, shard)
+                    n[q.name] += 1
+                for pass0 in (False, True):
+                    q = dpn.plan(W, H, float(R), pass0, no_pair=1, no_p0=1, **shard)
+                    assert q.name == "k_denoise_ver" and q.PASS0 == pass0 and _segments(q, per) == lsc.ver_segments(W, total, per, pass0), (W, H, R, pass0, shard)
+                    n[q.name] += 1
+    assert min(n.values()) > 5000, n
+
+
+# What the `path` label of a case in denoise_shard_common.cases() (and the comment above it there) claims: the kernel family of pass 0
+# and of a weighted pass.  f: the facts of the pass -- R its tap offset (integral: f.integral), per the height of an extended strip,
+# the case's options.  The conditions (per >= 64, per a multiple of 4, R <= 5) are the plan's own thresholds written once more, as the case
+# comments state them: a threshold changed in the plan fails here because this table copies the number, not because the table knows
+# better.  It is the cases' claim held to the code, not a second derivation of the rule; the same holds for `pair` in the sweep above.
+def _ver(f): return "k_denoise_ver"
+def _literal(f): return "k_denoise_lds" if f.per % 4 == 0 else "k_denoise"           # (R <= 5 in every such case)
+
+
+PATHS = {
+    # label:         (pass 0,                                                        a weighted pass)
+    "p0-ver":        ("k_denoise_p0",                                                _ver),
+    "pair":          ("k_denoise_p0",                                                lambda f: "k_denoise_pair" if f.per >= 64 else "k_denoise_ver"),
+    "pair-p0-off":   (lambda f: "k_denoise_p0" if f.p0 else "k_denoise_ver",         lambda f: "k_denoise_pair" if f.pair and f.per >= 64 else "k_denoise_ver"),
+    "shipped":       ("k_denoise_ver",                                               _ver),
+    "literal":       (_literal,                                                      _literal),
+    "bilinear":      ("k_denoise_p0",                                                lambda f: "k_denoise_ver" if f.integral else "k_denoise"),
+    "guard":         ("k_denoise_p0",                                                _literal),
+    "edges":         ("k_denoise_p0",                                                _ver),
+    "halo-gt-strip": ("k_denoise_p0",                                                lambda f: "k_denoise_ver" if f.R <= 5 else "k_denoise"),
+}
+
+
+class _Facts:
+    pass
+
+
+def test_case_labels_name_the_kernels_the_plan_takes(vrt):
+    taken = {}
+    for c in dsc.CASES:
+        assert set(c.options) <= {"denoise_verified", "denoise_pair", "denoise_p0", "denoise_packed"}
+        if c.guard_too_large:
+            assert dpn.guard(vrt, c.iterations, c.step, c.mode, c.phis, 1) > GUARD_MAX
+        ext = dsc.reaches(c.iterations, c.step)
+        for rank in range(c.nranks):
+            ps = dpn.passes(vrt, c.W, c.H, c.iterations, c.step, c.mode, c.phis, c.options, (rank, c.nranks, c.strip_rows))
+            assert len(ps) == (c.iterations if dsc.strips(c.H, rank, c.nranks, c.strip_rows) else 0)
+            for i, q in enumerate(ps):
+                f = _Facts()
+                sw = np.float32(i) * np.float32(c.step) + np.float32(1.0)
+                f.R, f.integral, f.per = int(sw), float(sw) == int(sw), c.strip_rows + 2 * sum(ext[i + 1:])
+                f.pair, f.p0 = c.options.get("denoise_pair", 1), c.options.get("denoise_p0", 1)
+                claim = PATHS[c.path][min(i, 1)]
+                want = claim if isinstance(claim, str) else claim(f)
+                assert q.name == want, (c.id, rank, i, q.instantiation, want)
+                assert q.SHIPPED == c.mode or q.name in ("k_denoise", "k_denoise_p0", "k_denoise_pair")
+                taken.setdefault(c.path, set()).add((min(i, 1), q.name) + ((q.pair_R,) if q.name == "k_denoise_pair" else ()))
+    assert set(taken) == set(PATHS)
+    # ... and each label reaches what it is for
+    assert {(1, "k_denoise_pair", R) for R in (2, 3, 4, 5)} <= taken["pair"] and (1, "k_denoise_ver") in taken["pair"]
+    assert {(0, "k_denoise_ver"), (0, "k_denoise_p0"), (1, "k_denoise_pair", 3), (1, "k_denoise_ver")} <= taken["pair-p0-off"]
+    assert taken["literal"] == {(i, k) for i in (0, 1) for k in ("k_denoise", "k_denoise_lds")}
+    assert (1, "k_denoise") in taken["bilinear"] and (1, "k_denoise_lds") in taken["guard"] and (1, "k_denoise") in taken["halo-gt-strip"]
+
+
+# The arms of launch_denoise_pass' switch: every instantiation of the denoiser kernels (profiles/denoise_plan_kernel_digest.txt lists
+# the same 43), as (family, template arguments).
+INSTANTIATIONS = (
+    [("k_denoise", inf) for inf in (0, 1)]
+    + [("k_denoise_lds", inf, sh, fast, packed) for sh in (0, 1) for inf, fast, packed in ((0, 0, 0), (0, 0, 1), (0, 1, 0), (1, 0, 0))]
+    + [("k_denoise_fast", sh, th) for sh in (0, 1) for th in (8, 16)]
+    + [("k_denoise_ver", sh, 1, rt, 1) for sh in (0, 1) for rt in (1, 0)]
+    + [("k_denoise_ver", sh, fl, rt, 0) for sh in (0, 1) for fl in (0, 1) for rt in (2, 3, 5, 0)]
+    + [("k_denoise_pair", fl, R) for fl in (0, 1) for R in (2, 3, 4, 5)]
+    + [("k_denoise_p0", 1)])
+
+# Instantiations that no case table of the GPU tests reaches, and why.  No development switch guards these two: vrt_denoise cannot launch
+# them at all.  PASS0 is the blur, all three phis +inf, and RT = 0 with it a tap offset other than 1.  Pass 0 has the offset 0 * stepWidth + 1 = 1;
+# a later pass has phis of +inf only if the caller passes +inf, and then its guard is +inf too and the pass is not verified
+# (test_a_blur_with_another_tap_offset_is_never_verified).  The parent has the same two arms; which instantiations exist is not this table's to change.
+NOT_REACHED = dict(
+    [(("k_denoise_ver", sh, 1, 0, 1), "a verified pass with phis of +inf and a tap offset above 1: vrt_denoise makes none") for sh in (0, 1)])
+
+
+def test_a_blur_with_another_tap_offset_is_never_verified(vrt):
+    inf = float("inf")
+    for mode in (0, 1, 2, 3):
+        for step in (0.0, 1.0, 2.0, 3.0, 4.0, 0.5):
+            for i in range(1, 10):
+                assert dpn.guard(vrt, 10, step, mode, (inf, inf, inf), i) > GUARD_MAX
+            for q in dpn.passes(vrt, 130, 37, 10, step, mode, phis=(inf, inf, inf))[1:]:
+                assert q.PHI_INF and q.name in ("k_denoise", "k_denoise_lds")
+
+
+def test_fast_ver_rows_take_the_cheap_half_of_the_verified_kernel(vrt):
+    W, H = lsc.FAST_VER_SIZE
+    seen = set()
+    for (iterations, step), offsets in lsc.FAST_VER_SETTINGS.items():
+        assert tuple(lsc.tap_offsets(iterations, step)[1:]) == offsets
+        for mode in (0, 1):
+            ps = dpn.passes(vrt, W, H, iterations, step, mode | dpn.DENOISE_FAST, options={"denoise_pair": 0})
+            assert ps[0].instantiation == (("k_denoise_lds", 1, 1, 0, 0) if mode else ("k_denoise_p0", 1))      # pass 0: exact kernels
+            for q, R in zip(ps[1:], offsets):
+                assert q.instantiation == ("k_denoise_ver", mode, 0, R if R in (2, 3, 5) else 0, 0) and q.R == R
+                assert _segments(q, H) == lsc.ver_segments(W, H, H, False) and q.grid_x > 1 and q.segs > 1
+                seen.add(q.instantiation)
+    assert len(seen) == 8
+
+
+def _table_plans(vrt):
+    """[(table, plans of one vrt_denoise call)] of every call the GPU tests make from the case tables"""
+    out = []
+    for c in dsc.CASES:
+        out += [("dsc.cases", dpn.passes(vrt, c.W, c.H, c.iterations, c.step, c.mode, c.phis, c.options, (rank, c.nranks, c.strip_rows))) for rank in range(c.nranks)]
+    for c in lsc.PAIR_CASES:
+        out += [("PAIR_CASES", dpn.passes(vrt, c.W, c.H, c.iterations, c.step, mode, options={"denoise_pair_wgs": c.pair_wgs})) for mode in (0, dpn.DENOISE_FAST)]
+    for c in lsc.VER_CASES:
+        out.append(("VER_CASES", dpn.passes(vrt, c.W, c.H, c.iterations, c.step, c.mode, options={"denoise_pair": 0, "denoise_p0": 0})))
+    c = lsc.ShardPairCase
+    out += [("ShardPairCase", dpn.passes(vrt, c.W, c.H, c.iterations, c.step, 0, options={"denoise_pair_wgs": c.pair_wgs}, shard=(rank, c.nranks, c.strip_rows)))
+            for rank in range(c.nranks)]
+    for W, H in lsc.FAST_SIZES:
+        for step in lsc.FAST_STEPS:
+            for mode in (0, 1):
+                for iterations in (1,) + tuple(lsc.FAST_ITERATIONS):
+                    out += [("FAST_*", dpn.passes(vrt, W, H, iterations, step, mode | dpn.DENOISE_FAST, options={"denoise_verified": 0, "denoise_th16": th16}))
+                            for th16 in (0, 1)]
+    W, H, N, S, iterations, step = lsc.FAST_SHARD
+    out += [("FAST_SHARD", dpn.passes(vrt, W, H, iterations, step, mode | dpn.DENOISE_FAST, options={"denoise_verified": 0}, shard=(rank, N, S)))
+            for mode in (0, 1) for rank in range(N)]
+    W, H = lsc.FAST_VER_SIZE
+    out += [("FAST_VER", dpn.passes(vrt, W, H, iterations, step, mode | dpn.DENOISE_FAST, options={"denoise_pair": 0}))
+            for mode in (0, 1) for iterations, step in lsc.FAST_VER_SETTINGS]
+    return out
+
+
+def test_every_instantiation_is_reached_by_a_case_table(vrt):
+    assert len(set(INSTANTIATIONS)) == len(INSTANTIATIONS) == 43
+    reached = {q.instantiation for _, ps in _table_plans(vrt) for q in ps}
+    assert reached <= set(INSTANTIATIONS)
+    assert set(INSTANTIATIONS) - reached == set(NOT_REACHED), sorted(set(INSTANTIATIONS) - reached)
+
+
+def test_the_switchs_arms_are_the_objects_kernels():
+    """INSTANTIATIONS against the two committed kernel listings (tools/kernel_digest.py over the objects of this commit and of its parent:
+    equal line for line) and against the arms of the switch in csrc/vrt_denoise.hip."""
+    here, parent = (open(os.path.join(ROOT, "profiles", n)).read() for n in ("denoise_plan_kernel_digest.txt", "denoise_plan_parent_kernel_digest.txt"))
+    assert here == parent
+    listed = set()
+    for m in re.finditer(r"^_ZN3vrt\d+(k_denoise\w*?)I((?:L[bi]\d+E)+)EEvNS_13DenoiseParamsE", here, re.M):
+        listed.add((m.group(1),) + tuple(int(a) for a in re.findall(r"L[bi](\d+)E", m.group(2))))
+    assert listed == set(INSTANTIATIONS)
+    arms = re.findall(r"case denoise_key\((\w+)((?:, \d+)+)\):\s+hipLaunchKernelGGL\(\((k_denoise\w*)<", open(os.path.join(CSRC, "vrt_denoise.hip")).read())
+    assert sorted((k,) + tuple(int(a) for a in args.split(", ")[1:]) for _, args, k in arms) == sorted(INSTANTIATIONS)
+
+
+def test_the_plan_under_the_sanitizers(tmp_path):
+    """The stand-alone program of tests/native/denoise_plan_host.cpp, built with -fsanitize=address,undefined: the sweep of small
+    frames, a rank's strips, and the largest frames (32768 a side; W * H up to 2^28 - 1, the verified form's bound).  Exit status 0, and
+    the checksums of the unsanitized shared-library build."""
+    lines = dpn.run_main_program(str(tmp_path / "denoise_plan_main_san"))
+    assert [l[0] for l in lines] == list(range(dpn.BLOCKS))
+    for block, plans, checksum in lines:
+        n = C.c_uint64()
+        assert dpn.lib().denoise_plan_block_c(block, C.byref(n)) == checksum and n.value == plans and plans > 10000

@@ -480,6 +480,49 @@ int  vrt_scene_voxelize(struct vrt_ctx* ctx, vrt_scene* scene, const int32_t* ve
  * latest one launched (surface + solid) */
 int  vrt_debug_voxelize_item_rows(vrt_scene* scene, uint32_t rows);
 int  vrt_debug_voxelize_items(const vrt_scene* scene, uint32_t* items);
+/* Morphology (no reference analogue): select voxels by their NEIGHBOURHOOD in the scene itself and grow, shrink, open, close or
+ * hollow the solid on the device -- hollow a voxelized solid to a shell, thicken a thin surface, remove specks (OPEN), close
+ * pinholes (CLOSE), erode or dilate by a margin.  csrc/vrt_morph.h is the definition; it uses integers only.  S is the set of
+ * solid cells (id != 0) of the infinite grid: the scene inside the volume, empty outside it (VRT_MORPH_BORDER_SOLID: solid outside
+ * it).  connectivity VRT_MORPH_FACES measures distance in L1, VRT_MORPH_CORNERS in L-infinity; radius r in 1..8.  dil_r(X) holds
+ * every cell within r of a cell of X, ero_r(X) every cell whose whole ball of radius r lies in X.  The result set R:
+ *   VRT_MORPH_DILATE dil_r(S) | VRT_MORPH_ERODE ero_r(S) | VRT_MORPH_OPEN dil_r(ero_r(S)) | VRT_MORPH_CLOSE ero_r(dil_r(S)) |
+ *   VRT_MORPH_HOLLOW S \ ero_r(S), a shell of thickness r.
+ * R is computed on the whole grid and written inside the bounds [lo, lo+size) only (voxels; lo may be negative, each size in
+ * 1..2^30; clipped to the volume, no clipped side above 512: VRT_ERR_INVALID, work in parts): an empty voxel in R becomes `id`, a
+ * solid voxel not in R becomes 0, every other voxel keeps its id -- morphology never recolours, and a grown voxel does not
+ * inherit a neighbour's id.  The volume outside the bounds is read as it is, r cells out (2r for OPEN and CLOSE), so parts
+ * computed from the same old scene agree with the whole; parts applied in place one after another see each other.  DILATE and
+ * CLOSE need id >= 1 (VRT_ERR_INVALID); ERODE, OPEN and HOLLOW never add a voxel and ignore it.  result (not NULL): how many
+ * voxels were added and removed (added + removed == edit.changed) and, as vrt_scene_brush's result, the edit.  Bounds wholly
+ * outside the volume: VRT_OK with a zero result.  When edit.changed == 0 nothing is written, no edit pass runs and the count
+ * planes' second set of fields is kept.  flags: VRT_MORPH_MEASURE writes nothing and reports added and removed only (edit stays
+ * zeros); it works on every scene, brick scenes that were never reserved included.  Otherwise brick scenes, slot exhaustion
+ * (VRT_ERR_UNSUPPORTED, nothing changed), stream rules and the metallic rule are vrt_scene_brush's.  A NULL argument, an unknown
+ * operation, connectivity or flag, a radius outside 1..8, a size of 0 or above 2^30: VRT_ERR_INVALID before any device work.  The
+ * masks (2 bits per cell of the clipped bounds grown by the halo) are kept with the scene between calls: vrt_scene_memory counts
+ * them, vrt_scene_trim drops them; VRT_ERR_UNSUPPORTED if they cannot be had. */
+#define VRT_MORPH_DILATE  0
+#define VRT_MORPH_ERODE   1
+#define VRT_MORPH_OPEN    2
+#define VRT_MORPH_CLOSE   3
+#define VRT_MORPH_HOLLOW  4
+#define VRT_MORPH_FACES   6
+#define VRT_MORPH_CORNERS 26
+#define VRT_MORPH_BORDER_SOLID 1u   /* flags: every cell outside the volume is solid */
+#define VRT_MORPH_MEASURE      2u   /* flags: write nothing, report added and removed only */
+typedef struct vrt_morph {
+    int32_t  op, connectivity, radius;
+    int32_t  lo[3];
+    uint32_t size[3];
+    uint32_t flags;
+    uint8_t  id;
+} vrt_morph;
+typedef struct vrt_morph_result {
+    uint64_t added, removed;
+    vrt_brush_result edit;     /* as vrt_scene_brush's; zeros under VRT_MORPH_MEASURE */
+} vrt_morph_result;
+int  vrt_scene_morph(struct vrt_ctx* ctx, vrt_scene* scene, const vrt_morph* morph, vrt_morph_result* result);
 void vrt_scene_free(vrt_ctx* ctx, vrt_scene* sc);            /* VoxelScene::destroy */
 
 /* ---- settings -------------------------------------------------------------------------------- */

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Register budget of the hand-scheduled kernels (csrc: the parts of vrt_device.hip, vrt_denoise.hip over its vrt_denoise_*.h, vrt_scene_edit.hip, vrt_scene_read.hip, vrt_brush.hip, vrt_flood.hip, vrt_voxelize.hip, vrt_query.hip, vrt_query_seg.hip, vrt_reproject.hip, vrt_reproject_cam.hip, vrt_upsample.hip, vrt_upsample_cam.hip, vrt_rays.hip, vrt_render_rays.hip), checked
+"""Register budget of the hand-scheduled kernels (csrc: the parts of vrt_device.hip, vrt_denoise.hip over its vrt_denoise_*.h, vrt_scene_edit.hip, vrt_scene_read.hip, vrt_brush.hip, vrt_flood.hip, vrt_voxelize.hip, vrt_morph.hip, vrt_query.hip, vrt_query_seg.hip, vrt_reproject.hip, vrt_reproject_cam.hip, vrt_upsample.hip, vrt_upsample_cam.hip, vrt_rays.hip, vrt_render_rays.hip), checked
 at build time.
 
 K1's look-up loop pins physical registers and the kernel sits at two occupancy cliffs that the compiler's own remark does
@@ -86,6 +86,13 @@ BUDGET = {
     "k_vox_scanENS_6VoxJobE": ("voxelize: the toggle mask's rows scanned into the coverage mask", 32, 64, 0),
     "k_vox_extentENS_6VoxJobE": ("voxelize: the covered count and what changes (counts, bounds)", 32, 64, 0),
     "k_vox_composeENS_6VoxJobE": ("voxelize: the tight box's new ids into the edit scratch", 32, 64, 0),
+    # morphology (vrt_morph.hip): gathers, ballots and a tile stepped r times in LDS (32 KiB a workgroup) -- no register cliff to
+    # guard, none may spill (16 .. 22 VGPRs, 36 .. 46 SGPRs)
+    "k_morph_passENS_8MorphJobE": ("morphology: the solid mask over the domain", 32, 64, 0),
+    "k_morph_stepILi6EE": ("morphology: one phase, r unit steps a tile, 6-connectivity", 32, 64, 0),
+    "k_morph_stepILi26EE": ("morphology: one phase, r unit steps a tile, 26-connectivity", 32, 64, 0),
+    "k_morph_extentENS_8MorphJobE": ("morphology: what changes (added, removed, bounds)", 32, 64, 0),
+    "k_morph_composeENS_8MorphJobE": ("morphology: the tight box's new ids into the edit scratch", 32, 64, 0),
     # ray queries (vrt_query.hip): k_query<TRAV, ANYHIT, PICK>; none may spill.  The closest-hit form over the look-up loop keeps the
     # ray's direction and first mapPos across the march for the hit record: seven waves per SIMD, the others eight
     "k_queryILi7ELb0ELb0EE": ("ray query, closest hit, look-up loop", 72, 80, 0),
@@ -137,7 +144,7 @@ BUDGET = {
 
 
 # the objects that hold budgeted kernels, as the Makefile builds them: (source, extra flags); slowest first
-OBJECTS = [("vrt_device.hip", ["-DVRT_K1_PART=%d" % n]) for n in (3, 0, 1, 2)] + [("vrt_denoise.hip", []), ("vrt_scene_edit.hip", []), ("vrt_scene_read.hip", []), ("vrt_brush.hip", []), ("vrt_flood.hip", []), ("vrt_voxelize.hip", []), ("vrt_query.hip", []), ("vrt_query_seg.hip", []),
+OBJECTS = [("vrt_device.hip", ["-DVRT_K1_PART=%d" % n]) for n in (3, 0, 1, 2)] + [("vrt_denoise.hip", []), ("vrt_scene_edit.hip", []), ("vrt_scene_read.hip", []), ("vrt_brush.hip", []), ("vrt_flood.hip", []), ("vrt_voxelize.hip", []), ("vrt_morph.hip", []), ("vrt_query.hip", []), ("vrt_query_seg.hip", []),
                                                                                      ("vrt_reproject.hip", []), ("vrt_reproject_cam.hip", []), ("vrt_upsample.hip", []), ("vrt_upsample_cam.hip", []), ("vrt_rays.hip", []),
                                                                                      ("vrt_render_rays.hip", [])]
 

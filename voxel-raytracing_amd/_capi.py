@@ -128,7 +128,23 @@ class VoxelizeResult(C.Structure):
     _fields_ = [("covered", C.c_uint64), ("edit", BrushResult)]
 
 
-MAX_QUERY_RAYS = 1 << 28       # rays per vrt_trace_rays / vrt_occluded_rays / vrt_pick_pixels / vrt_trace_segments / vrt_occluded_segments call
+MORPH_DILATE, MORPH_ERODE, MORPH_OPEN, MORPH_CLOSE, MORPH_HOLLOW = 0, 1, 2, 3, 4   # vrt_morph.op
+MORPH_FACES, MORPH_CORNERS = 6, 26                                      # vrt_morph.connectivity
+MORPH_BORDER_SOLID, MORPH_MEASURE = 1, 2                                # vrt_morph.flags
+
+
+class Morph(C.Structure):
+    """vrt_morph: an operation, a connectivity, a radius, the bounds that may change, flags and the id of added voxels (csrc/vrt_morph.h)."""
+    _fields_ = [("op", C.c_int32), ("connectivity", C.c_int32), ("radius", C.c_int32), ("lo", C.c_int32 * 3), ("size", C.c_uint32 * 3),
+                ("flags", C.c_uint32), ("id", C.c_uint8)]
+
+
+class MorphResult(C.Structure):
+    """vrt_morph_result: the voxels added and removed, and the edit as vrt_scene_brush reports one."""
+    _fields_ = [("added", C.c_uint64), ("removed", C.c_uint64), ("edit", BrushResult)]
+
+
+MAX_QUERY_RAYS = 1 << 28      # rays per vrt_trace_rays / vrt_occluded_rays / vrt_pick_pixels / vrt_trace_segments / vrt_occluded_segments call
 
 assert C.sizeof(Push) == 96 and C.sizeof(Material) == 32
 
@@ -195,6 +211,7 @@ SYMBOLS = {
     "vrt_scene_voxelize": (C.c_int, [_P, _P, _P, C.c_uint32, _P, C.c_uint32, C.POINTER(Voxelize), C.POINTER(VoxelizeResult)]),
     "vrt_debug_voxelize_item_rows": (C.c_int, [_P, C.c_uint32]),
     "vrt_debug_voxelize_items": (C.c_int, [_P, C.POINTER(C.c_uint32)]),
+    "vrt_scene_morph": (C.c_int, [_P, _P, C.POINTER(Morph), C.POINTER(MorphResult)]),
     "vrt_scene_free": (None, [_P, _P]),
     "vrt_settings_default": (None, [C.POINTER(Settings)]),
     "vrt_render_geometry": (C.c_int, [_P, _P, C.POINTER(Push), C.POINTER(Settings), C.POINTER(Frame), C.POINTER(Shard)]),

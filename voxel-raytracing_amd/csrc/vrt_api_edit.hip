@@ -1,7 +1,8 @@
 // vrt_api_edit.hip -- what rewrites a scene through the C-ABI: edits of dense scenes and of reserved brick scenes
 // (vrt_scene_reserve_bricks, vrt_scene_edit_box, vrt_scene_fill_box), and the edits whose ids a kernel composes: brushes and stamps,
-// flood fills (whose loop over rounds lives here) and mesh voxelization (whose cut of the triangles into work items lives here).
-// Host code only; the kernels are vrt_scene_edit.hip, vrt_scene_build.hip, vrt_brush.hip, vrt_flood.hip and vrt_voxelize.hip.
+// flood fills (whose loop over rounds lives here), mesh voxelization (whose cut of the triangles into work items lives here)
+// and morphology (whose phases are launched here).
+// Host code only; the kernels are vrt_scene_edit.hip, vrt_scene_build.hip, vrt_brush.hip, vrt_flood.hip, vrt_voxelize.hip and vrt_morph.hip.
 // vrt_api_scene.hip makes, describes and reads the scenes.
 #include <cstring>
 
@@ -9,6 +10,7 @@
 #include "vrt_brush_launch.h"          // (brings vrt_scene_read.h and its launchers)
 #include "vrt_flood_launch.h"
 #include "vrt_voxelize_launch.h"
+#include "vrt_morph_launch.h"
 
 using namespace vrt;
 
@@ -21,6 +23,10 @@ static_assert(VRT_FLOOD_SAME == VRT_FLOOD_MATCH_SAME && VRT_FLOOD_SOLID == VRT_F
               "include/vrt.h and csrc/vrt_flood.h number the predicates, connectivities or flags differently");
 static_assert(VRT_VOXELIZE_SURFACE == VRT_VOXELIZE_FILL_SURFACE && VRT_VOXELIZE_SOLID == VRT_VOXELIZE_FILL_SOLID,
               "include/vrt.h and csrc/vrt_voxelize.h number the fills differently");
+static_assert(VRT_MORPH_DILATE == VRT_MORPH_OP_DILATE && VRT_MORPH_ERODE == VRT_MORPH_OP_ERODE && VRT_MORPH_OPEN == VRT_MORPH_OP_OPEN &&
+              VRT_MORPH_CLOSE == VRT_MORPH_OP_CLOSE && VRT_MORPH_HOLLOW == VRT_MORPH_OP_HOLLOW && VRT_MORPH_FACES == VRT_MORPH_CONN_FACES &&
+              VRT_MORPH_CORNERS == VRT_MORPH_CONN_CORNERS && VRT_MORPH_BORDER_SOLID == VRT_MORPH_FLAG_BORDER_SOLID && VRT_MORPH_MEASURE == VRT_MORPH_FLAG_MEASURE,
+              "include/vrt.h and csrc/vrt_morph.h number the operations, connectivities or flags differently");
 static_assert(VRT_BRUSH_SET == 0 && VRT_BRUSH_PAINT == 1 && VRT_BRUSH_ADD == 2 && VRT_BRUSH_REPLACE == 3, "vox_job_ok spells the modes as numbers");
 
 namespace {
@@ -716,6 +722,76 @@ int vrt_debug_voxelize_items(const vrt_scene* s, uint32_t* items)
 {
     if (!s || !items) return fail(VRT_ERR_INVALID, "vrt_debug_voxelize_items: NULL argument");
     *items = s->voxelize_items;
+    return VRT_OK;
+}
+
+} // extern "C"
+
+// ---- morphology (vrt_scene_morph; csrc/vrt_morph.h) -------------------------------------------------------------------------------
+
+namespace {
+
+hipError_t morph_compose(const void* job, uint8_t* ids, hipStream_t st) { return launch_morph_compose(*(const MorphJob*)job, ids, st); }
+
+} // namespace
+
+extern "C" {
+
+int vrt_scene_morph(struct vrt_ctx* c, vrt_scene* s, const vrt_morph* morph, vrt_morph_result* result)
+{
+    const std::string name("vrt_scene_morph");
+    if (!c || !s || !morph || !result) return fail(VRT_ERR_INVALID, name + ": NULL argument");
+    if (morph->op < VRT_MORPH_DILATE || morph->op > VRT_MORPH_HOLLOW) return fail(VRT_ERR_INVALID, name + ": unknown operation (VRT_MORPH_DILATE .. VRT_MORPH_HOLLOW)");
+    if (morph->connectivity != VRT_MORPH_FACES && morph->connectivity != VRT_MORPH_CORNERS)
+        return fail(VRT_ERR_INVALID, name + ": connectivity is VRT_MORPH_FACES (6) or VRT_MORPH_CORNERS (26)");
+    if (morph->radius < 1 || morph->radius > VRT_MORPH_MAX_RADIUS) return fail(VRT_ERR_INVALID, name + ": the radius is in 1.." + std::to_string(VRT_MORPH_MAX_RADIUS));
+    if (morph->flags & ~(uint32_t)(VRT_MORPH_BORDER_SOLID | VRT_MORPH_MEASURE)) return fail(VRT_ERR_INVALID, name + ": unknown flag");
+    if (morph_adds(morph->op) && morph->id == 0) return fail(VRT_ERR_INVALID, name + ": DILATE and CLOSE need id != 0 (the id of the voxels they add)");
+    if (!morph_args_ok(morph->op, morph->connectivity, morph->radius, morph->flags, morph->id, morph->size)) return fail(VRT_ERR_INVALID, name + ": each size of the bounds is in 1..2^30");
+    const bool measure = (morph->flags & VRT_MORPH_MEASURE) != 0u;
+    int32_t clo[3];
+    uint32_t csize[3];
+    const bool any = clip_box(s, morph->lo, morph->size, clo, csize);
+    if (any && !morph_sides_ok(csize))
+        return fail(VRT_ERR_INVALID, name + ": the bounds inside the volume have no side above " + std::to_string(VRT_MORPH_MAX_SIDE) + "; work in parts");
+    memset(result, 0, sizeof *result);
+    if (const int rc = measure ? VRT_OK : editable(s, name)) return rc;
+    if (!any) return VRT_OK;                                     // bounds wholly outside the volume: nothing to do
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    std::lock_guard<std::mutex> lock(s->lazy);
+    MorphJob j{};
+    j.box = read_box_of(s, clo, csize);
+    j.dim[0] = s->d.vol.W; j.dim[1] = s->d.vol.H; j.dim[2] = s->d.vol.D;
+    morph_domain(clo, csize, morph_halo(morph->op, morph->radius), j.mlo, j.msize);
+    j.op = morph->op; j.connectivity = morph->connectivity; j.radius = (uint32_t)morph->radius;
+    j.border_solid = (morph->flags & VRT_MORPH_BORDER_SOLID) ? 1u : 0u; j.id = morph->id;
+    // scratch: mask A | mask B | the record
+    const size_t mask = round256(morph_mask_words(j.msize) * 4u);
+    if (s->morph_scratch.room(2 * mask + round256(sizeof(MorphRecord)), s->bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(VRT_ERR_UNSUPPORTED, name + ": no device memory for two masks of " + std::to_string(mask) + " bytes; work in parts");
+    }
+    j.mask[0] = (uint32_t*)s->morph_scratch.get(); j.mask[1] = (uint32_t*)(s->morph_scratch.get() + mask);
+    MorphRecord* const rec_dev = (MorphRecord*)(s->morph_scratch.get() + 2 * mask);
+    const MorphRecord init = morph_record_init();
+    MorphRecord rec = init;
+    HIPCHK(hipMemcpyAsync(rec_dev, &init, sizeof init, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(launch_morph_pass(j, c->stream));
+    const uint32_t phases = morph_phases(morph->op);
+    for (uint32_t p = 0; p < phases; p++) HIPCHK(launch_morph_step(j, j.mask[p & 1u], j.mask[(p + 1u) & 1u], morph_phase_erodes(morph->op, p), c->stream));
+    j.result = j.mask[phases & 1u];
+    HIPCHK(launch_morph_extent(j, rec_dev, c->stream));
+    HIPCHK(hipMemcpyAsync(&rec, rec_dev, sizeof rec, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    vrt_morph_result out{};
+    out.added = rec.added; out.removed = rec.removed;
+    if (rec.added + rec.removed != rec.edit.changed) return fail(VRT_ERR_HIP, name + ": internal error (added + removed != changed)");
+    if (!measure) {
+        const int rc = composed_edit(c, s, rec.edit, clo, csize, j.box, morph_compose, &j, "the bounds", name, &out.edit);
+        if (rc != VRT_OK) return rc;
+    }
+    *result = out;
     return VRT_OK;
 }
 

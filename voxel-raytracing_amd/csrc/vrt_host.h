@@ -217,9 +217,12 @@ struct vrt_scene {
     // dropped as the flood's; rows per work item (0: VRT_VOXELIZE_ITEM_ROWS) and how many items the latest call launched
     vrt::Scratch voxelize_scratch;
     uint32_t voxelize_item_rows = 0, voxelize_items = 0;
-    // the three together: what brick_scene_bytes counts and vrt_scene_trim drops
-    size_t scratch_bytes() const { return edit_scratch.bytes + flood_scratch.bytes + voxelize_scratch.bytes; }
-    void drop_scratch() { edit_scratch.drop(bytes); flood_scratch.drop(bytes); voxelize_scratch.drop(bytes); }
+    // morphology (vrt_scene_morph): the two masks over the domain and the record (vrt_morph_launch.h), kept, counted and dropped as
+    // the flood's
+    vrt::Scratch morph_scratch;
+    // the four together: what brick_scene_bytes counts and vrt_scene_trim drops
+    size_t scratch_bytes() const { return edit_scratch.bytes + flood_scratch.bytes + voxelize_scratch.bytes + morph_scratch.bytes; }
+    void drop_scratch() { edit_scratch.drop(bytes); flood_scratch.drop(bytes); voxelize_scratch.drop(bytes); morph_scratch.drop(bytes); }
     uint64_t shade_gen = 0;           // changes whenever something a hit's colour depends on does (creation, vrt_scene_set_sky)
 };
 

@@ -576,6 +576,48 @@ class VoxelScene:
         check(lib().vrt_debug_voxelize_items(self.handle, C.byref(n)))
         return int(n.value)
 
+    # ---- morphology (vrt_scene_morph; csrc/vrt_morph.h) ----------------------------------------------------------------------
+    MORPH_OPS = {"dilate": _capi.MORPH_DILATE, "erode": _capi.MORPH_ERODE, "open": _capi.MORPH_OPEN, "close": _capi.MORPH_CLOSE,
+                 "hollow": _capi.MORPH_HOLLOW}
+
+    def morph(self, op, radius: int, connectivity: int = 6, id: int = 0, bounds=None, border_solid: bool = False, measure: bool = False):
+        """Grow, shrink, open, close or hollow the scene's solid (vrt_scene_morph).  op: "dilate" | "erode" | "open" | "close" |
+        "hollow" (or its number); radius 1..8; connectivity 6 (distance in L1) | 26 (L-infinity); id: what an added voxel becomes
+        (dilate and close need one; no voxel is ever recoloured); bounds: (lo, size) that may change, None = the whole volume (no
+        side of them inside the volume above 512); border_solid: the cells outside the volume count as solid; measure: write
+        nothing.  Returns a dict: added, removed, and changed, lo, size as brush returns them (zeros under measure)."""
+        o = self.MORPH_OPS[op] if isinstance(op, str) else int(op)
+        lo, size = ((0, 0, 0), (self.width, self.height, self.depth)) if bounds is None else bounds
+        if any(int(t) < 0 for t in size) or not 0 <= int(id) <= 255:
+            raise ValueError("VoxelScene.morph: negative size or id outside 0..255")
+        m = _capi.Morph(op=o, connectivity=int(connectivity), radius=int(radius), id=int(id),
+                        flags=(_capi.MORPH_BORDER_SOLID if border_solid else 0) | (_capi.MORPH_MEASURE if measure else 0))
+        m.lo[:], m.size[:] = [int(t) for t in lo], [int(t) for t in size]
+        res = _capi.MorphResult()
+        self._raise(lib().vrt_scene_morph(self.engine.ctx, self.handle, C.byref(m), C.byref(res)))
+        return {"added": int(res.added), "removed": int(res.removed), "changed": int(res.edit.changed), "lo": tuple(int(t) for t in res.edit.lo),
+                "size": tuple(int(t) for t in res.edit.size)}
+
+    def dilate(self, radius: int, id: int, connectivity: int = 6, **kw):
+        """Every empty voxel within `radius` of a solid one becomes `id`."""
+        return self.morph("dilate", radius, connectivity, id, **kw)
+
+    def erode(self, radius: int, connectivity: int = 6, **kw):
+        """Every solid voxel within `radius` of an empty one becomes empty."""
+        return self.morph("erode", radius, connectivity, 0, **kw)
+
+    def open(self, radius: int, connectivity: int = 6, **kw):
+        """Erode, then dilate what is left back: specks and spurs thinner than the ball go, nothing is added."""
+        return self.morph("open", radius, connectivity, 0, **kw)
+
+    def close(self, radius: int, id: int, connectivity: int = 6, **kw):
+        """Dilate, then erode back: pinholes and gaps narrower than the ball become `id`, nothing is removed."""
+        return self.morph("close", radius, connectivity, id, **kw)
+
+    def hollow(self, radius: int = 1, connectivity: int = 6, **kw):
+        """Keep a shell of thickness `radius` of every solid; the interior becomes empty."""
+        return self.morph("hollow", radius, connectivity, 0, **kw)
+
     # ---- read-back (vrt_scene_read_box, vrt_scene_list_box, vrt_scene_save_vox_*) ---------------------------------------
     @staticmethod
     def _box(lo, size):

@@ -20,6 +20,10 @@
 // becomes ID -- FILL surface (default) | solid | both, MODE set (default) | paint | add -- inside the mesh's own bounds
 // (VoxelScene::voxelize).  The reader is minimal: `v` and `f` lines, polygons as fans, negative indices, everything after a `/`
 // ignored; coordinates are voxels.
+// --morph OP:CONN:R[:ID[:solid][:LOX,LOY,LOZ:SX,SY,SZ]] (repeatable, in command-line order with the others): OP dilate | erode | open |
+// close | hollow of the scene's solid by the ball of radius R (1..8) of CONN 6 | 26; added voxels become ID (dilate and close need
+// one); `solid`: the cells outside the volume count as solid; inside the bounds if given, else in the whole volume
+// (VoxelScene::morph); e.g. --morph hollow:6:1 leaves a shell one voxel thick of a voxelized solid.
 // --save-obj OUT.obj: the surface of the scene as it stands after the edits as a Wavefront OBJ of quads in voxel coordinates, grouped
 // by id, with its .mtl beside it (VoxelScene::saveObj).
 // --read-box X Y Z SX SY SZ OUT: the ids of the box, x fastest, raw bytes (VoxelScene::read).  With any of these and no image output
@@ -135,6 +139,43 @@ vrt_flood parseFlood(const std::string& spec)
     return fl;
 }
 
+// --morph OP:CONN:R[:ID[:solid][:LOX,LOY,LOZ:SX,SY,SZ]]; without bounds size[0] stays 0 and the scene's dimensions are taken
+vrt_morph parseMorph(const std::string& spec)
+{
+    auto split = [](const std::string& t, char sep) {
+        std::vector<std::string> out; size_t at = 0;
+        for (;;) { const size_t e = t.find(sep, at); out.push_back(t.substr(at, e == std::string::npos ? e : e - at)); if (e == std::string::npos) break; at = e + 1; }
+        return out;
+    };
+    const std::vector<std::string> f = split(spec, ':');
+    const std::string want = "--morph wants OP:CONN:R[:ID[:solid][:LOX,LOY,LOZ:SX,SY,SZ]], got " + spec;
+    if (f.size() < 3) throw std::runtime_error(want);
+    vrt_morph m{};
+    if (f[0] == "dilate") m.op = VRT_MORPH_DILATE; else if (f[0] == "erode") m.op = VRT_MORPH_ERODE; else if (f[0] == "open") m.op = VRT_MORPH_OPEN;
+    else if (f[0] == "close") m.op = VRT_MORPH_CLOSE; else if (f[0] == "hollow") m.op = VRT_MORPH_HOLLOW; else throw std::runtime_error("--morph: unknown operation " + f[0]);
+    m.connectivity = std::stoi(f[1]);
+    m.radius = std::stoi(f[2]);
+    size_t at = 3;
+    if (at < f.size() && f[at] != "solid" && f[at].find(',') == std::string::npos) {
+        const unsigned long id = std::stoul(f[at++]);
+        if (id > 255) throw std::runtime_error("--morph: ids are 0..255");
+        m.id = (uint8_t)id;
+    }
+    if (at < f.size() && f[at] == "solid") { m.flags |= VRT_MORPH_BORDER_SOLID; at++; }
+    if (at == f.size()) return m;
+    if (at + 2 != f.size()) throw std::runtime_error(want);
+    for (size_t k = 0; k < 2; k++) {
+        const std::vector<std::string> v = split(f[at + k], ',');
+        if (v.size() != 3) throw std::runtime_error("--morph: three comma-separated whole voxels, got " + f[at + k]);
+        for (size_t a = 0; a < 3; a++) {
+            const long long t = std::stoll(v[a]);
+            if (k == 1 && (t < 1 || t > 0xFFFFFFFFll)) throw std::runtime_error("--morph: a size of the bounds is outside 1..2^32-1");
+            if (k == 0) m.lo[a] = (int32_t)t; else m.size[a] = (uint32_t)t;
+        }
+    }
+    return m;
+}
+
 // --voxelize FILE.obj:ID[:FILL[:MODE]]
 struct VoxelizeOp { std::vector<int32_t> vertices; std::vector<uint32_t> triangles; uint8_t id = 0; uint32_t fill = VRT_VOXELIZE_SURFACE; int32_t mode = VRT_BRUSH_SET; };
 
@@ -185,7 +226,7 @@ int run(int argc, char** argv)
         int frames = 1; uint32_t windowW = 0, windowH = 0; float flyForward = 0, flyStrafe = 0, flyMouseX = 0; bool temporal = false, reproject = false, upsample = false;
         std::string dumpPushes, projection; std::vector<vrt_push> allPushes;
         struct Box { std::array<int32_t, 3> lo; std::array<uint32_t, 3> size; uint8_t id; };
-        struct SceneOp { bool isBrush; Box box; vrt_brush brush; bool isFlood = false; vrt_flood flood{}; bool isVoxelize = false; VoxelizeOp voxelize{}; };   // --fill, --brush, --flood and --voxelize, in the order given
+        struct SceneOp { bool isBrush; Box box; vrt_brush brush; bool isFlood = false; vrt_flood flood{}; bool isVoxelize = false; VoxelizeOp voxelize{}; bool isMorph = false; vrt_morph morph{}; };   // --fill, --brush, --flood, --voxelize and --morph, in the order given
         std::vector<SceneOp> sceneOps; Box readBox{}; std::string saveVox, saveObj, readBoxOut;
         for (int i = 1; i < argc; i++) {
             std::string a = argv[i];
@@ -204,6 +245,7 @@ int run(int argc, char** argv)
             else if (a == "--brush") sceneOps.push_back(SceneOp{true, Box{}, parseBrush(next())});
             else if (a == "--flood") { SceneOp op{false, Box{}, vrt_brush{}}; op.isFlood = true; op.flood = parseFlood(next()); sceneOps.push_back(op); }
             else if (a == "--voxelize") { SceneOp op{false, Box{}, vrt_brush{}}; op.isVoxelize = true; op.voxelize = parseVoxelize(next()); sceneOps.push_back(op); }
+            else if (a == "--morph") { SceneOp op{false, Box{}, vrt_brush{}}; op.isMorph = true; op.morph = parseMorph(next()); sceneOps.push_back(op); }
             else if (a == "--save-vox") saveVox = next();
             else if (a == "--save-obj") saveObj = next();
             else if (a == "--width") settings->targetResolution[0] = (uint32_t)std::stoul(next());
@@ -264,6 +306,14 @@ int run(int argc, char** argv)
             if (op.isVoxelize) {
                 const vrt_voxelize_result r = scene->voxelize(op.voxelize.vertices, op.voxelize.triangles, op.voxelize.id, op.voxelize.fill, op.voxelize.mode);
                 std::printf("voxelize: %llu voxels covered, %llu changed, box %d %d %d + %u %u %u\n", (unsigned long long)r.covered, (unsigned long long)r.edit.changed,
+                            r.edit.lo[0], r.edit.lo[1], r.edit.lo[2], r.edit.size[0], r.edit.size[1], r.edit.size[2]);
+                continue;
+            }
+            if (op.isMorph) {
+                vrt_morph m = op.morph;
+                if (m.size[0] == 0u) { m.size[0] = scene->width; m.size[1] = scene->height; m.size[2] = scene->depth; }
+                const vrt_morph_result r = scene->morph(m);
+                std::printf("morph: %llu voxels added, %llu removed, box %d %d %d + %u %u %u\n", (unsigned long long)r.added, (unsigned long long)r.removed,
                             r.edit.lo[0], r.edit.lo[1], r.edit.lo[2], r.edit.size[0], r.edit.size[1], r.edit.size[2]);
                 continue;
             }

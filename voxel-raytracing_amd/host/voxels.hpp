@@ -256,6 +256,24 @@ public:
         }
         return voxelize(vertices, triangles, job);
     }
+    // Morphology (no reference analogue; vrt_scene_morph): grow, shrink, open, close or hollow the scene's solid by the ball of `radius`
+    // (1..8) of connectivity VRT_MORPH_FACES | VRT_MORPH_CORNERS; an added voxel becomes `id` (DILATE and CLOSE need one), none is
+    // recoloured; flags VRT_MORPH_BORDER_SOLID | VRT_MORPH_MEASURE; without bounds the whole volume.
+    vrt_morph_result morph(const vrt_morph& m) { vrt_morph_result r{}; check(vrt_scene_morph(engine->ctx, handle, &m, &r)); return r; }
+    vrt_morph_result morph(int32_t op, int32_t radius, int32_t connectivity = VRT_MORPH_FACES, uint8_t id = 0, uint32_t flags = 0u)
+    {
+        vrt_morph m{};
+        m.op = op; m.connectivity = connectivity; m.radius = radius; m.flags = flags; m.id = id;
+        m.size[0] = width; m.size[1] = height; m.size[2] = depth;
+        return morph(m);
+    }
+    vrt_morph_result morph(int32_t op, int32_t radius, int32_t connectivity, uint8_t id, uint32_t flags, const std::array<int32_t, 3>& lo, const std::array<uint32_t, 3>& size)
+    {
+        vrt_morph m{};
+        m.op = op; m.connectivity = connectivity; m.radius = radius; m.flags = flags; m.id = id;
+        for (size_t a = 0; a < 3; a++) { m.lo[a] = lo[a]; m.size[a] = size[a]; }
+        return morph(m);
+    }
     // A brick scene becomes editable, with room for `capacity` bricks in its pool (vrt_scene_reserve_bricks); edit / fill then work on it
     // Read-back (no reference analogue; vrt_scene_read_box / vrt_scene_list_box / vrt_scene_save_vox_file).  read: the ids of the
     // box [lo, lo + size), x fastest -- what edit takes.  voxels: the box's non-empty voxels (no side above 256), one word each,

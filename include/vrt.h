@@ -523,6 +523,72 @@ typedef struct vrt_morph_result {
     vrt_brush_result edit;     /* as vrt_scene_brush's; zeros under VRT_MORPH_MEASURE */
 } vrt_morph_result;
 int  vrt_scene_morph(struct vrt_ctx* ctx, vrt_scene* scene, const vrt_morph* morph, vrt_morph_result* result);
+/* Connected components: label, measure and filter all the regions of the bounds at once on the device -- delete every speck below N
+ * voxels, fill every closed cavity, keep only the largest object, count the islands and list their sizes and boxes.
+ * csrc/vrt_components.h is the definition; it uses integers only.  The bounds [lo, lo+size) are in voxels (lo may be negative, each
+ * size in 1..2^30; clipped to the volume, no clipped side above 512: VRT_ERR_INVALID, work in parts; wholly outside the volume:
+ * VRT_OK with a zero result).  A voxel PASSES under VRT_COMP_SOLID and VRT_COMP_SAME iff its id != 0, under VRT_COMP_EMPTY iff its
+ * id == 0; two adjacent passing voxels are JOINED always (SOLID, EMPTY) or iff their ids are equal (SAME); adjacent means a shared
+ * face (VRT_COMP_FACES) or a face, edge or corner (VRT_COMP_CORNERS), among the voxels of the clipped bounds only.  The ROOT of a
+ * component is its voxel of lowest rx + csize[0] * (ry + csize[1] * rz), (rx, ry, rz) its offset from the clipped lo; components
+ * are numbered 0..n-1 in ascending root order, so every output is a function of the scene's content alone.
+ * vrt_scene_components lists one vrt_component per component in that order (records may be NULL with capacity 0: count only; a
+ * capacity below the count with records != NULL: VRT_ERR_INVALID after *result is written, as vrt_scene_list_box).  It works on
+ * every scene, brick scenes never reserved included, and writes nothing to the scene.  result->largest: the number of the component
+ * with the most voxels, the lowest number among equals (0 when there is none).
+ * vrt_scene_component_labels copies the labels (a voxel's component number, 0xFFFFFFFF if it does not pass; read-box order) of a
+ * box inside the clipped bounds of the scene's latest labelling (by vrt_scene_components or vrt_scene_filter_components).  Every call
+ * that rewrites the scene after it -- edit, fill, brush, stamp, flood, voxelize, morph, filter -- and vrt_scene_trim make that
+ * labelling stale: VRT_ERR_INVALID.
+ * vrt_scene_filter_components labels the bounds, SELECTS the components with min_voxels <= voxels <= max_voxels,
+ * (faces & faces_all) == faces_all, (faces & faces_none) == 0 and, under VRT_COMP_KEEP_LARGEST, all but the largest, and makes every
+ * voxel of a selected component `id`, with vrt_scene_flood's rules for the edit: no-op (changed == 0 writes nothing), tight box,
+ * brick slots (VRT_ERR_UNSUPPORTED, nothing changed), the metallic rule, the stream rules.  VRT_COMP_MEASURE writes nothing and
+ * reports the selection only; it works on every scene.  A NULL argument, an unknown match, connectivity or flag, a face bit above
+ * 5, min_voxels > max_voxels, a size of 0 or above 2^30: VRT_ERR_INVALID before any device work.  The label volume (4 bytes per
+ * voxel of the clipped bounds: 512 MiB at 512^3) and the table are kept with the scene: vrt_scene_memory counts them,
+ * vrt_scene_trim drops them; VRT_ERR_UNSUPPORTED if they cannot be had. */
+#define VRT_COMP_SOLID   0
+#define VRT_COMP_SAME    1
+#define VRT_COMP_EMPTY   2
+#define VRT_COMP_FACES   6
+#define VRT_COMP_CORNERS 26
+#define VRT_COMP_KEEP_LARGEST 1u   /* vrt_component_filter.flags: the largest component is never selected */
+#define VRT_COMP_MEASURE      2u   /* vrt_component_filter.flags: write nothing, report the selection only */
+typedef struct vrt_components {
+    int32_t  lo[3];
+    uint32_t size[3];
+    int32_t  match, connectivity;
+    uint32_t flags;            /* 0: none is defined */
+} vrt_components;
+typedef struct vrt_component {
+    int32_t  root[3];          /* volume coordinates */
+    uint32_t id;               /* of the root voxel */
+    uint64_t voxels;
+    int32_t  lo[3];            /* the tight box */
+    uint32_t size[3];
+    uint32_t faces;            /* bit d: a voxel on face d of the clipped bounds; 0 = -x, 1 = +x, 2 = -y, 3 = +y, 4 = -z, 5 = +z */
+    uint32_t reserved;         /* 0 */
+} vrt_component;
+typedef struct vrt_components_result {
+    uint64_t components, voxels;
+    uint64_t largest;          /* number of the largest; lowest number wins ties */
+} vrt_components_result;
+typedef struct vrt_component_filter {
+    uint64_t min_voxels, max_voxels;
+    uint32_t faces_all, faces_none;
+    uint32_t flags;
+    uint8_t  id;               /* what every voxel of a selected component becomes */
+} vrt_component_filter;
+typedef struct vrt_filter_result {
+    uint64_t components, voxels;   /* selected */
+    vrt_brush_result edit;     /* as vrt_scene_brush's; zeros under VRT_COMP_MEASURE */
+} vrt_filter_result;
+int  vrt_scene_components(struct vrt_ctx* ctx, const vrt_scene* scene, const vrt_components* components, vrt_component* records, uint64_t capacity,
+                          vrt_components_result* result);
+int  vrt_scene_component_labels(struct vrt_ctx* ctx, const vrt_scene* scene, const int32_t lo[3], const uint32_t size[3], uint32_t* labels /* host */);
+int  vrt_scene_filter_components(struct vrt_ctx* ctx, vrt_scene* scene, const vrt_components* components, const vrt_component_filter* filter,
+                                 vrt_filter_result* result);
 void vrt_scene_free(vrt_ctx* ctx, vrt_scene* sc);            /* VoxelScene::destroy */
 
 /* ---- settings -------------------------------------------------------------------------------- */

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Register budget of the hand-scheduled kernels (csrc: the parts of vrt_device.hip, vrt_denoise.hip over its vrt_denoise_*.h, vrt_scene_edit.hip, vrt_scene_read.hip, vrt_brush.hip, vrt_flood.hip, vrt_voxelize.hip, vrt_morph.hip, vrt_query.hip, vrt_query_seg.hip, vrt_reproject.hip, vrt_reproject_cam.hip, vrt_upsample.hip, vrt_upsample_cam.hip, vrt_rays.hip, vrt_render_rays.hip), checked
+"""Register budget of the hand-scheduled kernels (csrc: the parts of vrt_device.hip, vrt_denoise.hip over its vrt_denoise_*.h, vrt_scene_edit.hip, vrt_scene_read.hip, vrt_brush.hip, vrt_flood.hip, vrt_voxelize.hip, vrt_morph.hip, vrt_components.hip, vrt_query.hip, vrt_query_seg.hip, vrt_reproject.hip, vrt_reproject_cam.hip, vrt_upsample.hip, vrt_upsample_cam.hip, vrt_rays.hip, vrt_render_rays.hip), checked
 at build time.
 
 K1's look-up loop pins physical registers and the kernel sits at two occupancy cliffs that the compiler's own remark does
@@ -93,6 +93,22 @@ BUDGET = {
     "k_morph_stepILi26EE": ("morphology: one phase, r unit steps a tile, 26-connectivity", 32, 64, 0),
     "k_morph_extentENS_8MorphJobE": ("morphology: what changes (added, removed, bounds)", 32, 64, 0),
     "k_morph_composeENS_8MorphJobE": ("morphology: the tight box's new ids into the edit scratch", 32, 64, 0),
+    # connected components (vrt_components.hip): a union-find over the label volume, ballots, 5 KB of LDS in the tile pass -- no register
+    # cliff to guard, none may spill (8 .. 44 VGPRs, 16 .. 72 SGPRs)
+    "k_comp_tileILi6ELb0EE": ("components: labels inside a tile, 6-connectivity", 64, 80, 0),
+    "k_comp_tileILi6ELb1EE": ("components: labels inside a tile, 6-connectivity, equal ids", 64, 80, 0),
+    "k_comp_tileILi26ELb0EE": ("components: labels inside a tile, 26-connectivity", 64, 80, 0),
+    "k_comp_tileILi26ELb1EE": ("components: labels inside a tile, 26-connectivity, equal ids", 64, 80, 0),
+    "k_comp_seamILi6EE": ("components: unions across tile faces", 32, 64, 0),
+    "k_comp_seamILi26EE": ("components: unions across tile faces, edges and corners", 32, 64, 0),
+    "k_comp_flattenENS_7CompJobE": ("components: labels to roots, roots counted per segment", 32, 64, 0),
+    "k_comp_numberENS_7CompJobE": ("components: roots numbered in order, table entries written", 32, 64, 0),
+    "k_comp_measureENS_7CompJobE": ("components: numbers into the labels, counts and boxes per tile", 32, 64, 0),
+    "k_comp_summaryENS_7CompJobE": ("components: the largest and the voxel total", 32, 64, 0),
+    "k_comp_selectENS_7CompJobE": ("components: the filter's verdict per component", 32, 64, 0),
+    "k_comp_extentENS_7CompJobE": ("components: what the filter changes (count, bounds)", 32, 64, 0),
+    "k_comp_composeENS_7CompJobE": ("components: the tight box's new ids into the edit scratch", 32, 64, 0),
+    "k_comp_labelsENS_7CompJobE": ("components: a box of labels for the host", 32, 64, 0),
     # ray queries (vrt_query.hip): k_query<TRAV, ANYHIT, PICK>; none may spill.  The closest-hit form over the look-up loop keeps the
     # ray's direction and first mapPos across the march for the hit record: seven waves per SIMD, the others eight
     "k_queryILi7ELb0ELb0EE": ("ray query, closest hit, look-up loop", 72, 80, 0),
@@ -144,7 +160,7 @@ BUDGET = {
 
 
 # the objects that hold budgeted kernels, as the Makefile builds them: (source, extra flags); slowest first
-OBJECTS = [("vrt_device.hip", ["-DVRT_K1_PART=%d" % n]) for n in (3, 0, 1, 2)] + [("vrt_denoise.hip", []), ("vrt_scene_edit.hip", []), ("vrt_scene_read.hip", []), ("vrt_brush.hip", []), ("vrt_flood.hip", []), ("vrt_voxelize.hip", []), ("vrt_morph.hip", []), ("vrt_query.hip", []), ("vrt_query_seg.hip", []),
+OBJECTS = [("vrt_device.hip", ["-DVRT_K1_PART=%d" % n]) for n in (3, 0, 1, 2)] + [("vrt_denoise.hip", []), ("vrt_scene_edit.hip", []), ("vrt_scene_read.hip", []), ("vrt_brush.hip", []), ("vrt_flood.hip", []), ("vrt_voxelize.hip", []), ("vrt_morph.hip", []), ("vrt_components.hip", []), ("vrt_query.hip", []), ("vrt_query_seg.hip", []),
                                                                                      ("vrt_reproject.hip", []), ("vrt_reproject_cam.hip", []), ("vrt_upsample.hip", []), ("vrt_upsample_cam.hip", []), ("vrt_rays.hip", []),
                                                                                      ("vrt_render_rays.hip", [])]
 

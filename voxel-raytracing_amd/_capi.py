@@ -144,7 +144,39 @@ class MorphResult(C.Structure):
     _fields_ = [("added", C.c_uint64), ("removed", C.c_uint64), ("edit", BrushResult)]
 
 
-MAX_QUERY_RAYS = 1 << 28      # rays per vrt_trace_rays / vrt_occluded_rays / vrt_pick_pixels / vrt_trace_segments / vrt_occluded_segments call
+COMP_SOLID, COMP_SAME, COMP_EMPTY = 0, 1, 2                             # vrt_components.match
+COMP_FACES, COMP_CORNERS = 6, 26                                        # vrt_components.connectivity
+COMP_KEEP_LARGEST, COMP_MEASURE = 1, 2                                  # vrt_component_filter.flags
+COMP_NONE = 0xFFFFFFFF                                                  # the label of a voxel that does not pass
+
+
+class Components(C.Structure):
+    """vrt_components: the bounds, a predicate and a connectivity (csrc/vrt_components.h)."""
+    _fields_ = [("lo", C.c_int32 * 3), ("size", C.c_uint32 * 3), ("match", C.c_int32), ("connectivity", C.c_int32), ("flags", C.c_uint32)]
+
+
+class Component(C.Structure):
+    """vrt_component: one component's record."""
+    _fields_ = [("root", C.c_int32 * 3), ("id", C.c_uint32), ("voxels", C.c_uint64), ("lo", C.c_int32 * 3), ("size", C.c_uint32 * 3),
+                ("faces", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class ComponentsResult(C.Structure):
+    _fields_ = [("components", C.c_uint64), ("voxels", C.c_uint64), ("largest", C.c_uint64)]
+
+
+class ComponentFilter(C.Structure):
+    """vrt_component_filter: which components are selected, and the id their voxels become."""
+    _fields_ = [("min_voxels", C.c_uint64), ("max_voxels", C.c_uint64), ("faces_all", C.c_uint32), ("faces_none", C.c_uint32),
+                ("flags", C.c_uint32), ("id", C.c_uint8)]
+
+
+class FilterResult(C.Structure):
+    """vrt_filter_result: the components and voxels selected, and the edit as vrt_scene_brush reports one."""
+    _fields_ = [("components", C.c_uint64), ("voxels", C.c_uint64), ("edit", BrushResult)]
+
+
+MAX_QUERY_RAYS = 1 << 28     # rays per vrt_trace_rays / vrt_occluded_rays / vrt_pick_pixels / vrt_trace_segments / vrt_occluded_segments call
 
 assert C.sizeof(Push) == 96 and C.sizeof(Material) == 32
 
@@ -212,6 +244,9 @@ SYMBOLS = {
     "vrt_debug_voxelize_item_rows": (C.c_int, [_P, C.c_uint32]),
     "vrt_debug_voxelize_items": (C.c_int, [_P, C.POINTER(C.c_uint32)]),
     "vrt_scene_morph": (C.c_int, [_P, _P, C.POINTER(Morph), C.POINTER(MorphResult)]),
+    "vrt_scene_components": (C.c_int, [_P, _P, C.POINTER(Components), _P, C.c_uint64, C.POINTER(ComponentsResult)]),
+    "vrt_scene_component_labels": (C.c_int, [_P, _P, C.POINTER(C.c_int32), C.POINTER(C.c_uint32), _P]),
+    "vrt_scene_filter_components": (C.c_int, [_P, _P, C.POINTER(Components), C.POINTER(ComponentFilter), C.POINTER(FilterResult)]),
     "vrt_scene_free": (None, [_P, _P]),
     "vrt_settings_default": (None, [C.POINTER(Settings)]),
     "vrt_render_geometry": (C.c_int, [_P, _P, C.POINTER(Push), C.POINTER(Settings), C.POINTER(Frame), C.POINTER(Shard)]),

@@ -1,9 +1,10 @@
 // vrt_api_edit.hip -- what rewrites a scene through the C-ABI: edits of dense scenes and of reserved brick scenes
 // (vrt_scene_reserve_bricks, vrt_scene_edit_box, vrt_scene_fill_box), and the edits whose ids a kernel composes: brushes and stamps,
 // flood fills (whose loop over rounds lives here), mesh voxelization (whose cut of the triangles into work items lives here)
-// and morphology (whose phases are launched here).
-// Host code only; the kernels are vrt_scene_edit.hip, vrt_scene_build.hip, vrt_brush.hip, vrt_flood.hip, vrt_voxelize.hip and vrt_morph.hip.
+// and morphology (whose phases are launched here), and the connected components (whose passes are launched here; listing them writes nothing).
+// Host code only; the kernels are vrt_scene_edit.hip, vrt_scene_build.hip, vrt_brush.hip, vrt_flood.hip, vrt_voxelize.hip, vrt_morph.hip and vrt_components.hip.
 // vrt_api_scene.hip makes, describes and reads the scenes.
+#include <cstddef>
 #include <cstring>
 
 #include "vrt_host.h"
@@ -11,6 +12,7 @@
 #include "vrt_flood_launch.h"
 #include "vrt_voxelize_launch.h"
 #include "vrt_morph_launch.h"
+#include "vrt_components_launch.h"
 
 using namespace vrt;
 
@@ -27,6 +29,13 @@ static_assert(VRT_MORPH_DILATE == VRT_MORPH_OP_DILATE && VRT_MORPH_ERODE == VRT_
               VRT_MORPH_CLOSE == VRT_MORPH_OP_CLOSE && VRT_MORPH_HOLLOW == VRT_MORPH_OP_HOLLOW && VRT_MORPH_FACES == VRT_MORPH_CONN_FACES &&
               VRT_MORPH_CORNERS == VRT_MORPH_CONN_CORNERS && VRT_MORPH_BORDER_SOLID == VRT_MORPH_FLAG_BORDER_SOLID && VRT_MORPH_MEASURE == VRT_MORPH_FLAG_MEASURE,
               "include/vrt.h and csrc/vrt_morph.h number the operations, connectivities or flags differently");
+static_assert(VRT_COMP_SOLID == VRT_COMP_MATCH_SOLID && VRT_COMP_SAME == VRT_COMP_MATCH_SAME && VRT_COMP_EMPTY == VRT_COMP_MATCH_EMPTY &&
+              VRT_COMP_FACES == VRT_COMP_CONN_FACES && VRT_COMP_CORNERS == VRT_COMP_CONN_CORNERS && VRT_COMP_KEEP_LARGEST == VRT_COMP_FLAG_KEEP_LARGEST &&
+              VRT_COMP_MEASURE == VRT_COMP_FLAG_MEASURE, "include/vrt.h and csrc/vrt_components.h number the predicates, connectivities or flags differently");
+static_assert(sizeof(vrt_component) == sizeof(CompRecord) && offsetof(vrt_component, root) == offsetof(CompRecord, root) && offsetof(vrt_component, id) == offsetof(CompRecord, id) &&
+              offsetof(vrt_component, voxels) == offsetof(CompRecord, voxels) && offsetof(vrt_component, lo) == offsetof(CompRecord, lo) &&
+              offsetof(vrt_component, size) == offsetof(CompRecord, size) && offsetof(vrt_component, faces) == offsetof(CompRecord, faces) &&
+              offsetof(vrt_component, reserved) == offsetof(CompRecord, reserved), "include/vrt.h and csrc/vrt_components.h lay the record out differently");
 static_assert(VRT_BRUSH_SET == 0 && VRT_BRUSH_PAINT == 1 && VRT_BRUSH_ADD == 2 && VRT_BRUSH_REPLACE == 3, "vox_job_ok spells the modes as numbers");
 
 namespace {
@@ -240,6 +249,7 @@ int brick_scene_edit(vrt_ctx* c, vrt_scene* s, const EditBox& box, const EditIds
 // waited for the stream and holds the lock
 int scene_edit_locked(vrt_ctx* c, vrt_scene* s, const EditBox& b, const EditIds& src, const std::string& name)
 {
+    s->edit_gen++;                                               // whatever was labelled before is stale (vrt_scene_component_labels), even if the edit is refused
     if (s->bricks) return brick_scene_edit(c, s, b, src, name);
     const VolumeView& d = s->d.vol;
     const size_t nbox = (size_t)(b.hi[0] - b.lo[0]) * (size_t)(b.hi[1] - b.lo[1]) * (size_t)(b.hi[2] - b.lo[2]);
@@ -789,6 +799,197 @@ int vrt_scene_morph(struct vrt_ctx* c, vrt_scene* s, const vrt_morph* morph, vrt
     if (rec.added + rec.removed != rec.edit.changed) return fail(VRT_ERR_HIP, name + ": internal error (added + removed != changed)");
     if (!measure) {
         const int rc = composed_edit(c, s, rec.edit, clo, csize, j.box, morph_compose, &j, "the bounds", name, &out.edit);
+        if (rc != VRT_OK) return rc;
+    }
+    *result = out;
+    return VRT_OK;
+}
+
+} // extern "C"
+
+// ---- connected components (vrt_scene_components, vrt_scene_component_labels, vrt_scene_filter_components; csrc/vrt_components.h) --
+
+namespace {
+
+hipError_t comp_compose(const void* job, uint8_t* ids, hipStream_t st) { return launch_comp_compose(*(const CompJob*)job, ids, st); }
+
+// One labelling and where its results lie: comp_scratch is label volume | the segments' counts | the summary | the filter's record
+struct CompRun { CompJob j; CompSummary sum; CompSummary* sum_dev; BrushRecord* rec_dev; };
+
+void comp_scratch_layout(const vrt_scene* s, const uint32_t csize[3], size_t* labels, size_t* work)
+{
+    *labels = round256((size_t)csize[0] * csize[1] * csize[2] * 4u);
+    *work = round256(((size_t)list_segments_per_row(csize[0]) * csize[1] * csize[2] + 2u) * 4u);
+}
+
+// what the checks every entry point makes of a vrt_components leave: VRT_OK and *any (false: the bounds lie outside the volume)
+int comp_bounds(const vrt_scene* s, const vrt_components* q, const std::string& name, int32_t clo[3], uint32_t csize[3], bool* any)
+{
+    if (!comp_match_ok(q->match)) return fail(VRT_ERR_INVALID, name + ": unknown match (VRT_COMP_SOLID, VRT_COMP_SAME or VRT_COMP_EMPTY)");
+    if (!comp_conn_ok(q->connectivity)) return fail(VRT_ERR_INVALID, name + ": connectivity is VRT_COMP_FACES (6) or VRT_COMP_CORNERS (26)");
+    if (q->flags != 0u) return fail(VRT_ERR_INVALID, name + ": unknown flag");
+    if (!comp_args_ok(q->match, q->connectivity, q->flags, q->size)) return fail(VRT_ERR_INVALID, name + ": each size of the bounds is in 1..2^30");
+    *any = clip_box(s, q->lo, q->size, clo, csize);
+    if (*any && !comp_sides_ok(csize))
+        return fail(VRT_ERR_INVALID, name + ": the bounds inside the volume have no side above " + std::to_string(VRT_COMP_MAX_SIDE) + "; work in parts");
+    return VRT_OK;
+}
+
+// The passes of vrt_components.h over the clipped bounds [clo, clo + csize).  The caller checked the arguments, waited for the stream
+// and holds the scene's lock.  Returns when the stream is done: the label volume, the table and run->sum are complete.
+int comp_label(vrt_ctx* c, vrt_scene* s, const vrt_components* q, const int32_t clo[3], const uint32_t csize[3], const std::string& name, CompRun* run)
+{
+    CompJob& j = run->j;
+    j = CompJob{};
+    j.box = read_box_of(s, clo, csize);
+    for (int a = 0; a < 3; a++) { j.clo[a] = clo[a]; j.csize[a] = csize[a]; }
+    comp_tiles(csize, j.nt);
+    j.match = q->match; j.connectivity = q->connectivity;
+    size_t labels, work;
+    comp_scratch_layout(s, csize, &labels, &work);
+    s->comp_valid = false;
+    if (s->comp_scratch.room(labels + work + round256(sizeof(CompSummary)) + round256(sizeof(BrushRecord)), s->bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(VRT_ERR_UNSUPPORTED, name + ": no device memory for a label volume of " + std::to_string(labels) + " bytes; work in parts");
+    }
+    uint8_t* const p = s->comp_scratch.get();
+    j.labels = (uint32_t*)p;
+    uint32_t* const work_dev = (uint32_t*)(p + labels);
+    run->sum_dev = (CompSummary*)(p + labels + work);
+    run->rec_dev = (BrushRecord*)(p + labels + work + round256(sizeof(CompSummary)));
+    const uint32_t nseg = list_segments_per_row(csize[0]) * csize[1] * csize[2];
+    uint32_t total = 0;
+    HIPCHK(hipMemsetAsync(run->sum_dev, 0, sizeof(CompSummary), c->stream));
+    HIPCHK(launch_comp_tile(j, c->stream));
+    HIPCHK(launch_comp_seam(j, c->stream));
+    HIPCHK(launch_comp_flatten(j, work_dev, c->stream));
+    HIPCHK(launch_list_scan(work_dev, nseg, c->stream));
+    HIPCHK(hipMemcpyAsync(&total, work_dev + nseg, 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    j.ncomp = total;
+    run->sum = CompSummary{};
+    if (total != 0u) {
+        if (s->comp_table.room((size_t)total * sizeof(CompStat), s->bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(VRT_ERR_UNSUPPORTED, name + ": no device memory for a table of " + std::to_string(total) + " components; work in parts");
+        }
+        j.table = (CompStat*)s->comp_table.get();
+        HIPCHK(launch_comp_number(j, work_dev, c->stream));
+        HIPCHK(launch_comp_measure(j, c->stream));
+        HIPCHK(launch_comp_summary(j, run->sum_dev, c->stream));
+        HIPCHK(hipMemcpyAsync(&run->sum, run->sum_dev, sizeof(CompSummary), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+    }
+    s->comp_valid = true; s->comp_gen = s->edit_gen;
+    for (int a = 0; a < 3; a++) { s->comp_clo[a] = clo[a]; s->comp_csize[a] = csize[a]; }
+    return VRT_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int vrt_scene_components(struct vrt_ctx* c, const vrt_scene* scene, const vrt_components* q, vrt_component* records, uint64_t capacity, vrt_components_result* result)
+{
+    const std::string name("vrt_scene_components");
+    if (!c || !scene || !q || !result) return fail(VRT_ERR_INVALID, name + ": NULL argument");
+    vrt_scene* const s = const_cast<vrt_scene*>(scene);          // the scene's content is not written: its scratch memory and its lock are
+    int32_t clo[3];
+    uint32_t csize[3];
+    bool any = false;
+    if (const int rc = comp_bounds(s, q, name, clo, csize, &any)) return rc;
+    memset(result, 0, sizeof *result);
+    if (!any) return VRT_OK;                                     // bounds wholly outside the volume: no components
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    std::lock_guard<std::mutex> lock(s->lazy);
+    CompRun run;
+    if (const int rc = comp_label(c, s, q, clo, csize, name, &run)) return rc;
+    const uint64_t n = run.j.ncomp;
+    result->components = n; result->voxels = run.sum.voxels;
+    result->largest = n ? (uint64_t)comp_largest_number(run.sum.largest) : 0ull;
+    if (!records || !n) return VRT_OK;
+    if (capacity < n) return fail(VRT_ERR_INVALID, name + ": the bounds have " + std::to_string(n) + " components and `records` room for " + std::to_string(capacity));
+    std::vector<CompStat> table(n);
+    HIPCHK(hipMemcpyAsync(table.data(), run.j.table, n * sizeof(CompStat), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    for (uint64_t k = 0; k < n; k++) {
+        const CompRecord r = comp_record_of(table[k], clo, csize);
+        memcpy(records + k, &r, sizeof r);
+    }
+    return VRT_OK;
+}
+
+int vrt_scene_component_labels(struct vrt_ctx* c, const vrt_scene* scene, const int32_t lo[3], const uint32_t size[3], uint32_t* labels)
+{
+    const std::string name("vrt_scene_component_labels");
+    if (!c || !scene || !lo || !size || !labels) return fail(VRT_ERR_INVALID, name + ": NULL argument");
+    vrt_scene* const s = const_cast<vrt_scene*>(scene);
+    for (int a = 0; a < 3; a++)
+        if (size[a] == 0u) return fail(VRT_ERR_INVALID, name + ": the box is empty");
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    std::lock_guard<std::mutex> lock(s->lazy);
+    if (!s->comp_valid) return fail(VRT_ERR_INVALID, name + ": the scene has no labelling (vrt_scene_components makes one; vrt_scene_trim drops it)");
+    if (s->comp_gen != s->edit_gen) return fail(VRT_ERR_INVALID, name + ": the scene was edited after its latest labelling; label it again");
+    for (int a = 0; a < 3; a++)
+        if (lo[a] < s->comp_clo[a] || (int64_t)lo[a] + (int64_t)size[a] > (int64_t)s->comp_clo[a] + (int64_t)s->comp_csize[a])
+            return fail(VRT_ERR_INVALID, name + ": the box leaves the bounds of the latest labelling");
+    const size_t n = (size_t)size[0] * size[1] * size[2];
+    DevBuf<uint32_t> stage;
+    if (stage.alloc(n * 4u) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(VRT_ERR_UNSUPPORTED, name + ": no device memory for a staging buffer of " + std::to_string(n * 4u) + " bytes; read the labels in parts");
+    }
+    CompJob j{};
+    for (int a = 0; a < 3; a++) { j.clo[a] = s->comp_clo[a]; j.csize[a] = s->comp_csize[a]; }
+    j.labels = (uint32_t*)s->comp_scratch.get();
+    HIPCHK(launch_comp_labels(j, lo, size, stage.get(), c->stream));
+    HIPCHK(hipMemcpyAsync(labels, stage.get(), n * 4u, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return VRT_OK;
+}
+
+int vrt_scene_filter_components(struct vrt_ctx* c, vrt_scene* s, const vrt_components* q, const vrt_component_filter* f, vrt_filter_result* result)
+{
+    const std::string name("vrt_scene_filter_components");
+    if (!c || !s || !q || !f || !result) return fail(VRT_ERR_INVALID, name + ": NULL argument");
+    if (f->flags & ~(uint32_t)(VRT_COMP_KEEP_LARGEST | VRT_COMP_MEASURE)) return fail(VRT_ERR_INVALID, name + ": unknown filter flag");
+    if (f->min_voxels > f->max_voxels) return fail(VRT_ERR_INVALID, name + ": min_voxels > max_voxels");
+    if (!comp_filter_ok(f->min_voxels, f->max_voxels, f->faces_all, f->faces_none, f->flags)) return fail(VRT_ERR_INVALID, name + ": a face mask has the bits 0..5");
+    int32_t clo[3];
+    uint32_t csize[3];
+    bool any = false;
+    if (const int rc = comp_bounds(s, q, name, clo, csize, &any)) return rc;
+    const bool measure = (f->flags & VRT_COMP_MEASURE) != 0u;
+    memset(result, 0, sizeof *result);
+    if (const int rc = measure ? VRT_OK : editable(s, name)) return rc;
+    if (!any) return VRT_OK;                                     // bounds wholly outside the volume: nothing to do
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    std::lock_guard<std::mutex> lock(s->lazy);
+    CompRun run;
+    if (const int rc = comp_label(c, s, q, clo, csize, name, &run)) return rc;
+    if (run.j.ncomp == 0u) return VRT_OK;
+    CompJob& j = run.j;
+    j.id = f->id;
+    CompFilter F{};
+    F.min_voxels = f->min_voxels; F.max_voxels = f->max_voxels; F.faces_all = f->faces_all; F.faces_none = f->faces_none; F.flags = f->flags;
+    F.largest = comp_largest_number(run.sum.largest);
+    const BrushRecord init = brush_record_init();
+    BrushRecord rec = init;
+    HIPCHK(launch_comp_select(j, F, run.sum_dev, c->stream));
+    if (!measure) {
+        HIPCHK(hipMemcpyAsync(run.rec_dev, &init, sizeof init, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(launch_comp_extent(j, run.rec_dev, c->stream));
+        HIPCHK(hipMemcpyAsync(&rec, run.rec_dev, sizeof rec, hipMemcpyDeviceToHost, c->stream));
+    }
+    HIPCHK(hipMemcpyAsync(&run.sum, run.sum_dev, sizeof(CompSummary), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    vrt_filter_result out{};
+    out.components = run.sum.sel_components; out.voxels = run.sum.sel_voxels;
+    if (!measure) {
+        const int rc = composed_edit(c, s, rec, clo, csize, j.box, comp_compose, &j, "the bounds", name, &out.edit);
         if (rc != VRT_OK) return rc;
     }
     *result = out;

@@ -220,9 +220,25 @@ struct vrt_scene {
     // morphology (vrt_scene_morph): the two masks over the domain and the record (vrt_morph_launch.h), kept, counted and dropped as
     // the flood's
     vrt::Scratch morph_scratch;
-    // the four together: what brick_scene_bytes counts and vrt_scene_trim drops
-    size_t scratch_bytes() const { return edit_scratch.bytes + flood_scratch.bytes + voxelize_scratch.bytes + morph_scratch.bytes; }
-    void drop_scratch() { edit_scratch.drop(bytes); flood_scratch.drop(bytes); voxelize_scratch.drop(bytes); morph_scratch.drop(bytes); }
+    // connected components (vrt_scene_components, vrt_scene_filter_components): the label volume, the segments' counts, the summary
+    // and the filter's record in one allocation, the table in another (its size follows from the component count), kept, counted
+    // and dropped as the flood's.  edit_gen counts the rewrites of the scene (scene_edit_locked); the latest labelling is valid
+    // for vrt_scene_component_labels while comp_valid and comp_gen == edit_gen, over the clipped bounds comp_clo, comp_csize
+    vrt::Scratch comp_scratch, comp_table;
+    uint64_t edit_gen = 0, comp_gen = 0;
+    bool comp_valid = false;
+    int32_t comp_clo[3] = {0, 0, 0};
+    uint32_t comp_csize[3] = {0, 0, 0};
+    // the six together: what brick_scene_bytes counts and vrt_scene_trim drops
+    size_t scratch_bytes() const
+    {
+        return edit_scratch.bytes + flood_scratch.bytes + voxelize_scratch.bytes + morph_scratch.bytes + comp_scratch.bytes + comp_table.bytes;
+    }
+    void drop_scratch()
+    {
+        edit_scratch.drop(bytes); flood_scratch.drop(bytes); voxelize_scratch.drop(bytes); morph_scratch.drop(bytes);
+        comp_scratch.drop(bytes); comp_table.drop(bytes); comp_valid = false;
+    }
     uint64_t shade_gen = 0;           // changes whenever something a hit's colour depends on does (creation, vrt_scene_set_sky)
 };
 

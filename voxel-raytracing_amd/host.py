@@ -618,6 +618,76 @@ class VoxelScene:
         """Keep a shell of thickness `radius` of every solid; the interior becomes empty."""
         return self.morph("hollow", radius, connectivity, 0, **kw)
 
+    # ---- connected components (vrt_scene_components, vrt_scene_filter_components; csrc/vrt_components.h) ------------------
+    COMP_MATCHES = {"solid": _capi.COMP_SOLID, "same": _capi.COMP_SAME, "empty": _capi.COMP_EMPTY}
+    COMPONENT_DTYPE = np.dtype([("root", np.int32, 3), ("id", np.uint32), ("voxels", np.uint64), ("lo", np.int32, 3), ("size", np.uint32, 3),
+                                ("faces", np.uint32), ("reserved", np.uint32)])
+
+    def _components(self, match, connectivity, bounds):
+        mt = self.COMP_MATCHES[match] if isinstance(match, str) else int(match)
+        lo, size = ((0, 0, 0), (self.width, self.height, self.depth)) if bounds is None else bounds
+        if any(int(t) < 0 for t in size):
+            raise ValueError("VoxelScene.components: negative size")
+        q = _capi.Components(match=mt, connectivity=int(connectivity), flags=0)
+        q.lo[:], q.size[:] = [int(t) for t in lo], [int(t) for t in size]
+        return q
+
+    def components(self, match="solid", connectivity: int = 6, bounds=None):
+        """Every connected component of the bounds at once (vrt_scene_components).  match: "solid" (non-empty voxels, whatever their
+        ids) | "same" (non-empty voxels of one id) | "empty" (the cavities and the outer air); connectivity: 6 | 26; bounds: (lo,
+        size), None = the whole volume (no side of them inside the volume above 512).  Returns (records, result): a structured
+        array (COMPONENT_DTYPE: root, id, voxels, lo, size, faces) in component order -- ascending root -- and a dict: components,
+        voxels, largest.  Nothing is written; works on every scene."""
+        q = self._components(match, connectivity, bounds)
+        res = _capi.ComponentsResult()
+        self._raise(lib().vrt_scene_components(self.engine.ctx, self.handle, C.byref(q), None, 0, C.byref(res)))
+        rec = np.zeros(int(res.components), dtype=self.COMPONENT_DTYPE)
+        if rec.size:
+            self._raise(lib().vrt_scene_components(self.engine.ctx, self.handle, C.byref(q), rec.ctypes.data_as(C.c_void_p), rec.size, C.byref(res)))
+            assert int(res.components) == rec.size
+        return rec, {"components": int(res.components), "voxels": int(res.voxels), "largest": int(res.largest)}
+
+    def labels(self, box=None) -> np.ndarray:
+        """The labels of the scene's latest labelling (vrt_scene_component_labels): a uint32 array indexed [z, y, x], a voxel's
+        component number, 0xFFFFFFFF where it does not pass.  box: (lo, size) inside that labelling's clipped bounds; None = the
+        whole volume.  VrtError once anything has rewritten the scene since."""
+        lo, size = ((0, 0, 0), (self.width, self.height, self.depth)) if box is None else box
+        clo, csz = self._box(lo, size)
+        out = np.empty((int(size[2]), int(size[1]), int(size[0])), dtype=np.uint32)
+        self._raise(lib().vrt_scene_component_labels(self.engine.ctx, self.handle, clo, csz, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def filter_components(self, id: int, match="solid", connectivity: int = 6, bounds=None, min_voxels: int = 0, max_voxels: int = 2 ** 64 - 1,
+                          faces_all: int = 0, faces_none: int = 0, keep_largest: bool = False, measure: bool = False):
+        """Every voxel of every selected component becomes `id` (vrt_scene_filter_components).  Selected: min_voxels <= voxels <=
+        max_voxels, touching all the faces of the bounds in faces_all and none of those in faces_none (bit d: 0 = -x .. 5 = +z),
+        and under keep_largest not the largest.  measure: write nothing.  Returns a dict: components and voxels selected, and
+        changed, lo, size as brush returns them."""
+        q = self._components(match, connectivity, bounds)
+        if not 0 <= int(id) <= 255 or not 0 <= int(min_voxels) < 2 ** 64 or not 0 <= int(max_voxels) < 2 ** 64 or not 0 <= int(faces_all) < 2 ** 32 \
+                or not 0 <= int(faces_none) < 2 ** 32:
+            raise ValueError("VoxelScene.filter_components: id in 0..255, counts in 0..2^64-1, face masks in 0..2^32-1")
+        f = _capi.ComponentFilter(min_voxels=int(min_voxels), max_voxels=int(max_voxels), faces_all=int(faces_all), faces_none=int(faces_none),
+                                  flags=(_capi.COMP_KEEP_LARGEST if keep_largest else 0) | (_capi.COMP_MEASURE if measure else 0), id=int(id))
+        res = _capi.FilterResult()
+        self._raise(lib().vrt_scene_filter_components(self.engine.ctx, self.handle, C.byref(q), C.byref(f), C.byref(res)))
+        return {"components": int(res.components), "voxels": int(res.voxels), "changed": int(res.edit.changed),
+                "lo": tuple(int(t) for t in res.edit.lo), "size": tuple(int(t) for t in res.edit.size)}
+
+    def despeckle(self, min_voxels: int, connectivity: int = 6, **kw):
+        """Delete every solid component of fewer than min_voxels voxels."""
+        if int(min_voxels) < 1:
+            raise ValueError("VoxelScene.despeckle: min_voxels >= 1")
+        return self.filter_components(0, "solid", connectivity, max_voxels=int(min_voxels) - 1, **kw)
+
+    def fill_cavities(self, id: int, connectivity: int = 6, **kw):
+        """Every region of air that touches no face of the bounds becomes `id`."""
+        return self.filter_components(id, "empty", connectivity, faces_none=63, **kw)
+
+    def keep_largest(self, connectivity: int = 6, **kw):
+        """Delete every solid component but the largest."""
+        return self.filter_components(0, "solid", connectivity, keep_largest=True, **kw)
+
     # ---- read-back (vrt_scene_read_box, vrt_scene_list_box, vrt_scene_save_vox_*) ---------------------------------------
     @staticmethod
     def _box(lo, size):

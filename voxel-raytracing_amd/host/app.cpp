@@ -24,6 +24,11 @@
 // close | hollow of the scene's solid by the ball of radius R (1..8) of CONN 6 | 26; added voxels become ID (dilate and close need
 // one); `solid`: the cells outside the volume count as solid; inside the bounds if given, else in the whole volume
 // (VoxelScene::morph); e.g. --morph hollow:6:1 leaves a shell one voxel thick of a voxelized solid.
+// --components MATCH:CONN[:LOX,LOY,LOZ:SX,SY,SZ] (repeatable, in command-line order with the others): one line per connected component
+// of the bounds (else the whole volume) -- MATCH solid | same | empty, CONN 6 | 26 -- in ascending order of its root
+// (VoxelScene::components).  --despeckle N deletes every solid component below N voxels, --fill-cavities ID makes every region of air
+// that touches no face of the volume ID, --keep-largest deletes every solid component but the largest (6-connectivity, the whole
+// volume; VoxelScene::despeckle, fillCavities, keepLargest); they compose with --save-vox like the other edits.
 // --save-obj OUT.obj: the surface of the scene as it stands after the edits as a Wavefront OBJ of quads in voxel coordinates, grouped
 // by id, with its .mtl beside it (VoxelScene::saveObj).
 // --read-box X Y Z SX SY SZ OUT: the ids of the box, x fastest, raw bytes (VoxelScene::read).  With any of these and no image output
@@ -176,6 +181,32 @@ vrt_morph parseMorph(const std::string& spec)
     return m;
 }
 
+// --components MATCH:CONN[:LOX,LOY,LOZ:SX,SY,SZ]; without bounds size[0] stays 0 and the scene's dimensions are taken
+vrt_components parseComponents(const std::string& spec)
+{
+    auto split = [](const std::string& t, char sep) {
+        std::vector<std::string> out; size_t at = 0;
+        for (;;) { const size_t e = t.find(sep, at); out.push_back(t.substr(at, e == std::string::npos ? e : e - at)); if (e == std::string::npos) break; at = e + 1; }
+        return out;
+    };
+    const std::vector<std::string> f = split(spec, ':');
+    if (f.size() != 2 && f.size() != 4) throw std::runtime_error("--components wants MATCH:CONN[:LOX,LOY,LOZ:SX,SY,SZ], got " + spec);
+    vrt_components q{};
+    if (f[0] == "solid") q.match = VRT_COMP_SOLID; else if (f[0] == "same") q.match = VRT_COMP_SAME; else if (f[0] == "empty") q.match = VRT_COMP_EMPTY;
+    else throw std::runtime_error("--components: unknown match " + f[0]);
+    q.connectivity = std::stoi(f[1]);
+    for (size_t k = 0; k + 2 < f.size(); k++) {
+        const std::vector<std::string> v = split(f[2 + k], ',');
+        if (v.size() != 3) throw std::runtime_error("--components: three comma-separated whole voxels, got " + f[2 + k]);
+        for (size_t a = 0; a < 3; a++) {
+            const long long t = std::stoll(v[a]);
+            if (k == 1 && (t < 1 || t > 0xFFFFFFFFll)) throw std::runtime_error("--components: a size of the bounds is outside 1..2^32-1");
+            if (k == 0) q.lo[a] = (int32_t)t; else q.size[a] = (uint32_t)t;
+        }
+    }
+    return q;
+}
+
 // --voxelize FILE.obj:ID[:FILL[:MODE]]
 struct VoxelizeOp { std::vector<int32_t> vertices; std::vector<uint32_t> triangles; uint8_t id = 0; uint32_t fill = VRT_VOXELIZE_SURFACE; int32_t mode = VRT_BRUSH_SET; };
 
@@ -226,7 +257,8 @@ int run(int argc, char** argv)
         int frames = 1; uint32_t windowW = 0, windowH = 0; float flyForward = 0, flyStrafe = 0, flyMouseX = 0; bool temporal = false, reproject = false, upsample = false;
         std::string dumpPushes, projection; std::vector<vrt_push> allPushes;
         struct Box { std::array<int32_t, 3> lo; std::array<uint32_t, 3> size; uint8_t id; };
-        struct SceneOp { bool isBrush; Box box; vrt_brush brush; bool isFlood = false; vrt_flood flood{}; bool isVoxelize = false; VoxelizeOp voxelize{}; bool isMorph = false; vrt_morph morph{}; };   // --fill, --brush, --flood, --voxelize and --morph, in the order given
+        struct SceneOp { bool isBrush; Box box; vrt_brush brush; bool isFlood = false; vrt_flood flood{}; bool isVoxelize = false; VoxelizeOp voxelize{}; bool isMorph = false; vrt_morph morph{};
+                         int comp = 0; vrt_components components{}; unsigned long compValue = 0; };   // --fill, --brush, --flood, --voxelize, --morph, --components, --despeckle, --fill-cavities and --keep-largest, in the order given (comp: 1 list, 2 despeckle, 3 fill cavities, 4 keep largest)
         std::vector<SceneOp> sceneOps; Box readBox{}; std::string saveVox, saveObj, readBoxOut;
         for (int i = 1; i < argc; i++) {
             std::string a = argv[i];
@@ -246,6 +278,15 @@ int run(int argc, char** argv)
             else if (a == "--flood") { SceneOp op{false, Box{}, vrt_brush{}}; op.isFlood = true; op.flood = parseFlood(next()); sceneOps.push_back(op); }
             else if (a == "--voxelize") { SceneOp op{false, Box{}, vrt_brush{}}; op.isVoxelize = true; op.voxelize = parseVoxelize(next()); sceneOps.push_back(op); }
             else if (a == "--morph") { SceneOp op{false, Box{}, vrt_brush{}}; op.isMorph = true; op.morph = parseMorph(next()); sceneOps.push_back(op); }
+            else if (a == "--components") { SceneOp op{false, Box{}, vrt_brush{}}; op.comp = 1; op.components = parseComponents(next()); sceneOps.push_back(op); }
+            else if (a == "--despeckle" || a == "--fill-cavities" || a == "--keep-largest") {
+                SceneOp op{false, Box{}, vrt_brush{}};
+                op.comp = a == "--despeckle" ? 2 : a == "--fill-cavities" ? 3 : 4;
+                if (op.comp != 4) op.compValue = std::stoul(next());
+                if (op.comp == 2 && op.compValue < 1) throw std::runtime_error("--despeckle wants N >= 1");
+                if (op.comp == 3 && op.compValue > 255) throw std::runtime_error("--fill-cavities: ids are 0..255");
+                sceneOps.push_back(op);
+            }
             else if (a == "--save-vox") saveVox = next();
             else if (a == "--save-obj") saveObj = next();
             else if (a == "--width") settings->targetResolution[0] = (uint32_t)std::stoul(next());
@@ -307,6 +348,24 @@ int run(int argc, char** argv)
                 const vrt_voxelize_result r = scene->voxelize(op.voxelize.vertices, op.voxelize.triangles, op.voxelize.id, op.voxelize.fill, op.voxelize.mode);
                 std::printf("voxelize: %llu voxels covered, %llu changed, box %d %d %d + %u %u %u\n", (unsigned long long)r.covered, (unsigned long long)r.edit.changed,
                             r.edit.lo[0], r.edit.lo[1], r.edit.lo[2], r.edit.size[0], r.edit.size[1], r.edit.size[2]);
+                continue;
+            }
+            if (op.comp == 1) {
+                vrt_components q = op.components;
+                if (q.size[0] == 0u) { q.size[0] = scene->width; q.size[1] = scene->height; q.size[2] = scene->depth; }
+                vrt_components_result r{};
+                const std::vector<vrt_component> rec = scene->components(q, &r);
+                std::printf("components: %llu, %llu voxels, largest %llu\n", (unsigned long long)r.components, (unsigned long long)r.voxels, (unsigned long long)r.largest);
+                for (size_t k = 0; k < rec.size(); k++)
+                    std::printf("component %zu: root %d %d %d id %u voxels %llu box %d %d %d + %u %u %u faces %u\n", k, rec[k].root[0], rec[k].root[1], rec[k].root[2], rec[k].id,
+                                (unsigned long long)rec[k].voxels, rec[k].lo[0], rec[k].lo[1], rec[k].lo[2], rec[k].size[0], rec[k].size[1], rec[k].size[2], rec[k].faces);
+                continue;
+            }
+            if (op.comp != 0) {
+                const vrt_filter_result r = op.comp == 2 ? scene->despeckle(op.compValue) : op.comp == 3 ? scene->fillCavities((uint8_t)op.compValue) : scene->keepLargest();
+                std::printf("%s: %llu components of %llu voxels selected, %llu changed, box %d %d %d + %u %u %u\n",
+                            op.comp == 2 ? "despeckle" : op.comp == 3 ? "fill-cavities" : "keep-largest", (unsigned long long)r.components, (unsigned long long)r.voxels,
+                            (unsigned long long)r.edit.changed, r.edit.lo[0], r.edit.lo[1], r.edit.lo[2], r.edit.size[0], r.edit.size[1], r.edit.size[2]);
                 continue;
             }
             if (op.isMorph) {

@@ -274,6 +274,62 @@ public:
         for (size_t a = 0; a < 3; a++) { m.lo[a] = lo[a]; m.size[a] = size[a]; }
         return morph(m);
     }
+    // Connected components (no reference analogue; vrt_scene_components, vrt_scene_component_labels, vrt_scene_filter_components): every
+    // component of the bounds at once -- match VRT_COMP_SOLID | VRT_COMP_SAME | VRT_COMP_EMPTY, connectivity VRT_COMP_FACES |
+    // VRT_COMP_CORNERS -- as records in ascending order of their roots; labels: the component number of every voxel of a box inside the
+    // latest labelling's bounds (0xFFFFFFFF: does not pass), x fastest; filter: every voxel of a selected component becomes f.id.
+    std::vector<vrt_component> components(const vrt_components& q, vrt_components_result* result = nullptr)
+    {
+        vrt_components_result r{};
+        check(vrt_scene_components(engine->ctx, handle, &q, nullptr, 0, &r));
+        std::vector<vrt_component> rec((size_t)r.components);
+        if (!rec.empty()) check(vrt_scene_components(engine->ctx, handle, &q, rec.data(), rec.size(), &r));
+        if (result) *result = r;
+        return rec;
+    }
+    std::vector<vrt_component> components(int32_t match = VRT_COMP_SOLID, int32_t connectivity = VRT_COMP_FACES, vrt_components_result* result = nullptr)
+    {
+        return components(wholeVolume(match, connectivity), result);
+    }
+    std::vector<uint32_t> labels(const std::array<int32_t, 3>& lo, const std::array<uint32_t, 3>& size)
+    {
+        std::vector<uint32_t> out((size_t)size[0] * size[1] * size[2]);
+        check(vrt_scene_component_labels(engine->ctx, handle, lo.data(), size.data(), out.data()));
+        return out;
+    }
+    vrt_filter_result filterComponents(const vrt_components& q, const vrt_component_filter& f)
+    {
+        vrt_filter_result r{};
+        check(vrt_scene_filter_components(engine->ctx, handle, &q, &f, &r));
+        return r;
+    }
+    // delete every solid component below minVoxels voxels | every region of air that touches no face of the volume becomes id | delete
+    // every solid component but the largest
+    vrt_filter_result despeckle(uint64_t minVoxels, int32_t connectivity = VRT_COMP_FACES)
+    {
+        vrt_component_filter f{};
+        f.max_voxels = minVoxels ? minVoxels - 1u : 0u;
+        return filterComponents(wholeVolume(VRT_COMP_SOLID, connectivity), f);
+    }
+    vrt_filter_result fillCavities(uint8_t id, int32_t connectivity = VRT_COMP_FACES)
+    {
+        vrt_component_filter f{};
+        f.max_voxels = ~0ull; f.faces_none = 63u; f.id = id;
+        return filterComponents(wholeVolume(VRT_COMP_EMPTY, connectivity), f);
+    }
+    vrt_filter_result keepLargest(int32_t connectivity = VRT_COMP_FACES)
+    {
+        vrt_component_filter f{};
+        f.max_voxels = ~0ull; f.flags = VRT_COMP_KEEP_LARGEST;
+        return filterComponents(wholeVolume(VRT_COMP_SOLID, connectivity), f);
+    }
+    vrt_components wholeVolume(int32_t match, int32_t connectivity) const
+    {
+        vrt_components q{};
+        q.match = match; q.connectivity = connectivity;
+        q.size[0] = width; q.size[1] = height; q.size[2] = depth;
+        return q;
+    }
     // A brick scene becomes editable, with room for `capacity` bricks in its pool (vrt_scene_reserve_bricks); edit / fill then work on it
     // Read-back (no reference analogue; vrt_scene_read_box / vrt_scene_list_box / vrt_scene_save_vox_file).  read: the ids of the
     // box [lo, lo + size), x fastest -- what edit takes.  voxels: the box's non-empty voxels (no side above 256), one word each,

@@ -1035,6 +1035,34 @@ int  vrt_last_timings(vrt_ctx* ctx, float* primary_ms, float* geometry_ms, float
  * out[4i+2] = 1 if the fast path is sure of its texel (only then may the two be compared), out[4i+3] = float bits of the
  * fast coordinate u * sky_w.  tests/test_gpu_sky.py sweeps it over 10^8 directions. */
 int  vrt_debug_sky_texels(vrt_ctx* ctx, const vrt_scene* scene, const float* dirs_dev, size_t n, uint32_t* out_dev);
+/* Diagnostic of the numeric spec on the device (csrc/vrt_spec.h): evaluates ONE primitive per element, bit patterns
+ * in and bit patterns out, so that nothing is rounded on the way.  a_dev, b_dev, c_dev: n device words each (a float's bits; for
+ * VRT_SPEC_WRAP_TEXEL b holds the texture size n as a uint32); out_dev: n device words, 3 n for VRT_SPEC_NORMALIZE3 (x, y, z per
+ * element).  Element i is evaluated by lane i of the launch (256 lanes a workgroup): elements 64 k .. 64 k + 63 share a wave.
+ *   fn  evaluates              reads      writes per element
+ *   0   sqrt_spec(a)           a          the result's bits
+ *   1   div_spec(a, b)         a, b       the result's bits
+ *   2   atan2_spec(a, b)       a = y, b = x   the result's bits
+ *   3   asin_spec(a)           a          the result's bits
+ *   4   exp_spec(a)            a          the result's bits
+ *   5   unorm8(a)              a          0 .. 255
+ *   6   snorm8(a)              a          -127 .. 127, sign-extended to 32 bits
+ *   7   wrap_texel(a, b)       a, b       the texel index
+ *   8   normalize3(a, b, c)    a, b, c    three words
+ * An array fn does not read may be NULL.  VRT_ERR_INVALID: an unknown fn, a NULL ctx, out_dev or array that fn reads; n == 0 with
+ * valid pointers does nothing and succeeds; VRT_ERR_UNSUPPORTED: n > 2^31.  The kernel pins the header under the library's compiler
+ * flags in a unit of its own; the copies inlined into the render and denoise kernels stay pinned by the frame tests.
+ * tests/test_gpu_spec.py holds it to the oracle on every bit pattern of the one-argument primitives. */
+#define VRT_SPEC_SQRT        0u
+#define VRT_SPEC_DIV         1u
+#define VRT_SPEC_ATAN2       2u
+#define VRT_SPEC_ASIN        3u
+#define VRT_SPEC_EXP         4u
+#define VRT_SPEC_UNORM8      5u
+#define VRT_SPEC_SNORM8      6u
+#define VRT_SPEC_WRAP_TEXEL  7u
+#define VRT_SPEC_NORMALIZE3  8u
+int  vrt_debug_spec(vrt_ctx* ctx, uint32_t fn, const uint32_t* a_dev, const uint32_t* b_dev, const uint32_t* c_dev, size_t n, uint32_t* out_dev);
 /* Development builds only (make variant EXTRA=-DVRT_TRACE_COUNTERS; the product library answers zeros): look-ups of the brick
  * march since the last call, summed over the lanes of all rays -- all, those inside an occupied brick (the second, dependent
  * load), those that found a solid voxel, those that ended in the border or an open brick.  Waits for the stream; resets. */

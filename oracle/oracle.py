@@ -74,6 +74,8 @@ def lib():
         l.vo_expf.restype = C.c_float; l.vo_expf.argtypes = [C.c_float]
         l.vo_unorm8.restype = C.c_uint8; l.vo_unorm8.argtypes = [C.c_float]
         l.vo_snorm8.restype = C.c_int8; l.vo_snorm8.argtypes = [C.c_float]
+        l.vo_spec_batch.restype = C.c_int
+        l.vo_spec_batch.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int]
         l.vo_render_rows.restype = None
         l.vo_render_rows.argtypes = [C.POINTER(Scene), C.POINTER(Push), C.POINTER(Params), C.POINTER(Frame), C.c_int, C.c_int]
         l.vo_render_mt.restype = None
@@ -147,6 +149,23 @@ def snorm8(x):
     x = np.asarray(x, np.float32)
     c = np.fmin(np.fmax(x, np.float32(-1)), np.float32(1))
     return np.floor(c * np.float32(127) + np.float32(0.5)).astype(np.int8)
+
+
+SPEC_FNS = ("sqrt", "div", "atan2", "asin", "exp", "unorm8", "snorm8", "wrap_texel", "normalize3")      # fn numbers of vrt_debug_spec
+
+
+def spec_batch(fn, a, b=None, c=None, nthreads=8):
+    """vo_spec_batch: primitive `fn` over arrays of 32-bit patterns (uint32, equal lengths) -> uint32 [n], or [n, 3] for fn 8."""
+    a = np.ascontiguousarray(a, np.uint32).ravel()
+    b = None if b is None else np.ascontiguousarray(b, np.uint32).ravel()
+    c = None if c is None else np.ascontiguousarray(c, np.uint32).ravel()
+    assert all(x is None or x.size == a.size for x in (b, c))
+    out = np.empty((a.size, 3) if fn == 8 else (a.size,), np.uint32)
+    rc = lib().vo_spec_batch(int(fn), a.ctypes.data, None if b is None else b.ctypes.data, None if c is None else c.ctypes.data,
+                             a.size, out.ctypes.data, int(nthreads))
+    if rc != 0:
+        raise ValueError(f"vo_spec_batch({fn}): unknown fn or a missing array")
+    return out
 
 
 def jitter(index, render_width, display_width):

@@ -109,14 +109,18 @@ float vo_expf(float x)
     return p * s.f;
 }
 
-/* Vulkan float -> UNORM8 / SNORM8 conversion, canonical round-half-up of the scaled value. */
+/* Vulkan float -> UNORM8 / SNORM8 conversion, canonical round-half-up of the scaled value.  The clamp's fmaxf ignores a NaN
+ * (DESIGN.md 3), so a NaN ends at the lower bound; said outright, because a libm may answer NaN for a SIGNALLING NaN (glibc since
+ * 2.25), after which the clamp would end at the upper bound: 255 and 127, on that libm only. */
 uint8_t vo_unorm8(float c)
 {
+    if (c != c) return 0;
     c = fminf(fmaxf(c, 0.0f), 1.0f);
     return (uint8_t)floorf(c * 255.0f + 0.5f);
 }
 int8_t vo_snorm8(float c)
 {
+    if (c != c) return -127;
     c = fminf(fmaxf(c, -1.0f), 1.0f);
     return (int8_t)floorf(c * 127.0f + 0.5f);
 }
@@ -129,6 +133,63 @@ static inline uint32_t wrap_texel(float u, uint32_t n)
     int32_t i = (int32_t)floorf(fr * (float)n);
     if (i >= (int32_t)n) i = (int32_t)n - 1;
     return (uint32_t)i;
+}
+
+/* The primitives above over arrays of bit patterns (vrt_oracle.h: vo_spec_batch): wrappers only, no formula of their own. */
+static inline float f_of(uint32_t u) { float f; memcpy(&f, &u, 4); return f; }
+static inline uint32_t u_of(float f) { uint32_t u; memcpy(&u, &f, 4); return u; }
+
+typedef struct spec_job {
+    int fn; const uint32_t *a, *b, *c; uint32_t* out; size_t i0, i1;
+} spec_job;
+
+static void* spec_main(void* p)
+{
+    const spec_job* j = (const spec_job*)p;
+    const uint32_t *a = j->a, *b = j->b, *c = j->c;
+    uint32_t* out = j->out;
+    for (size_t i = j->i0; i < j->i1; i++) {
+        switch (j->fn) {
+        case 0: out[i] = u_of(sqrtf(f_of(a[i]))); break;
+        case 1: out[i] = u_of(f_of(a[i]) / f_of(b[i])); break;
+        case 2: out[i] = u_of(vo_atan2f(f_of(a[i]), f_of(b[i]))); break;
+        case 3: out[i] = u_of(vo_asinf(f_of(a[i]))); break;
+        case 4: out[i] = u_of(vo_expf(f_of(a[i]))); break;
+        case 5: out[i] = (uint32_t)vo_unorm8(f_of(a[i])); break;
+        case 6: out[i] = (uint32_t)(int32_t)vo_snorm8(f_of(a[i])); break;
+        case 7: out[i] = wrap_texel(f_of(a[i]), b[i]); break;
+        case 8: {
+            float v[3] = { f_of(a[i]), f_of(b[i]), f_of(c[i]) }, d[3];
+            normalize3(v, d);
+            out[3 * i] = u_of(d[0]); out[3 * i + 1] = u_of(d[1]); out[3 * i + 2] = u_of(d[2]);
+            break;
+        }
+        default: break;
+        }
+    }
+    return NULL;
+}
+
+int vo_spec_batch(int fn, const uint32_t* a, const uint32_t* b, const uint32_t* c, size_t n, uint32_t* out, int nthreads)
+{
+    const int two = fn == 1 || fn == 2 || fn == 7 || fn == 8;
+    if (fn < 0 || fn > 8 || !a || !out || (two && !b) || (fn == 8 && !c)) return -1;
+    if (nthreads < 1) nthreads = 1;
+    if (nthreads > 64) nthreads = 64;
+    pthread_t th[64];
+    spec_job jobs[64];
+    const size_t per = (n + (size_t)nthreads - 1) / (size_t)nthreads;
+    for (int t = 0; t < nthreads; t++) {
+        size_t i0 = per * (size_t)t, i1 = i0 + per;
+        if (i0 > n) i0 = n;
+        if (i1 > n) i1 = n;
+        spec_job j = { fn, a, b, c, out, i0, i1 };
+        jobs[t] = j;
+        if (t > 0) pthread_create(&th[t], NULL, spec_main, &jobs[t]);
+    }
+    spec_main(&jobs[0]);
+    for (int t = 1; t < nthreads; t++) pthread_join(th[t], NULL);
+    return 0;
 }
 
 /* ------------------------------------------------------------------------------------------ */

@@ -172,6 +172,13 @@ float vo_expf(float x);
 uint8_t vo_unorm8(float c);
 int8_t  vo_snorm8(float c);
 
+/* The primitives over arrays of 32-bit patterns, with the fn numbers of vrt_debug_spec (include/vrt.h): 0 sqrtf(a), 1 a / b,
+ * 2 vo_atan2f(a = y, b = x), 3 vo_asinf(a), 4 vo_expf(a), 5 vo_unorm8(a), 6 vo_snorm8(a) sign-extended, 7 the nearest / repeat
+ * texel of coordinate a in a texture of b texels (b: a uint32), 8 normalize(a, b, c) -> three words per element.  Wrappers over
+ * the functions of this file and C's sqrtf and /; n elements dealt to nthreads (1 .. 64) threads in contiguous ranges.
+ * Returns 0, or -1 for an unknown fn or a NULL array that fn reads. */
+int vo_spec_batch(int fn, const uint32_t* a, const uint32_t* b, const uint32_t* c, size_t n, uint32_t* out, int nthreads);
+
 #ifdef __cplusplus
 }
 #endif

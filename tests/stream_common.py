@@ -173,6 +173,7 @@ A = Case("A", "scene lifecycle",
           S("vrt_scene_set_sky", scene="s", sky=SKY75),
           S("vrt_scene_set_blue_noise", scene="s", noise=16),
           S("vrt_debug_sky_texels", scene="s", dirs=("panorama", (64, 32)), out="texels"),
+          S("vrt_debug_spec", fn=2, pairs=("edges", 4099), out="atan2"),        # spec_common.FN_ATAN2; a last wave of three lanes
           _render("a1", frame=2, jitter=(0.25, -0.25)),
           S("vrt_scene_set_sky", scene="s", sky=SKY11),
           _render("a2", "primary_only", res=RAGGED, frame=3),

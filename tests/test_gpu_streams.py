@@ -458,6 +458,26 @@ class Run:
             assert len(np.unique(g[:, 0])) == sky.shape[0] * sky.shape[1], "a panorama of 64 x 32 directions sees every texel of the 7 x 5 sky"
         return launch, verify
 
+    def h_vrt_debug_spec(self, a):
+        """One primitive of the numeric spec over n pairs of spec_common's edge set, against the oracle's vo_spec_batch."""
+        import spec_common as sp
+        kind, n = a["pairs"]
+        assert kind == "edges"
+        e = sp.edge_set()
+        y, x = np.resize(e, n), np.resize(e[::-1][5:], n)
+        yd, xd = self.upload(a["out"] + ".y", y.view(np.int32)), self.upload(a["out"] + ".x", x.view(np.int32))
+        out = self.buf(a["out"], (n + 64,), np.int32)
+        exp = _once((self.group, a["out"], _args(a)), lambda: self.oracle.spec_batch(a["fn"], y, x, nthreads=8))
+
+        def launch():
+            self.check(self.lib.vrt_debug_spec(self.engine.ctx, a["fn"], P(yd.data_ptr()), P(xd.data_ptr()), None, n, P(out.data_ptr())))
+
+        def verify():
+            g = out.cpu().numpy().view(np.uint32)
+            assert (g[n:] == np.uint32(sc.POISON * 0x01010101)).all(), (self.case.id, self.kind, a["out"], "wrote past its n elements")
+            sp.hold(g[:n], exp, a["fn"], (y, x), f"case {self.case.id} on {self.kind}: vrt_debug_spec")
+        return launch, verify
+
     # ---- strip and halo copies (the numpy row maps of voxel-raytracing_amd/distributed.py) ---------------------------------------
     GUARD = 2
 

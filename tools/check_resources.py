@@ -42,6 +42,8 @@ BUDGET = {
     "k_denoise_pairILb1ELi5EE": ("K3 verified weighted pass, every weight once, tap offset 5 (the reference's pass 2)", 96, 96, 0),
     "k_denoise_pairILb0ELi3EE": ("K3 VRT_DENOISE_FAST weighted pass, every weight once, tap offset 3", 96, 96, 0),
     "k_denoise_p0ILb1EE": ("K3 verified pass 0, a wave to itself (no LDS ring, no barrier)", 64, 96, 0),
+    # the numeric spec's primitives one per element (vrt_debug_spec, vrt_device.hip part 0): a diagnostic, no cliff to guard; no spill
+    "k_debug_specEjPKjS1_S1_mPj": ("diagnostic: one primitive of vrt_spec.h per element", 32, 48, 0),
     # scene edits (vrt_scene_edit_box): no register cliff to guard, but none of them may spill
     "k_edit_writeEPhS0_": ("scene edit: the box's ids into the volume and field 8", 64, 96, 0),
     "k_edit_occ1EPKh": ("scene edit: occ1 words under the box", 64, 96, 0),

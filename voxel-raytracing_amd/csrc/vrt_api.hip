@@ -860,6 +860,18 @@ int vrt_debug_sky_texels(vrt_ctx* c, const vrt_scene* s, const float* dirs_dev, 
     return VRT_OK;
 }
 
+int vrt_debug_spec(vrt_ctx* c, uint32_t fn, const uint32_t* a_dev, const uint32_t* b_dev, const uint32_t* c_dev, size_t n, uint32_t* out_dev)
+{
+    if (!c || !a_dev || !out_dev) return fail(VRT_ERR_INVALID, "vrt_debug_spec: NULL argument");
+    if (fn > VRT_SPEC_NORMALIZE3) return fail(VRT_ERR_INVALID, "vrt_debug_spec: unknown fn");
+    const bool two = fn == VRT_SPEC_DIV || fn == VRT_SPEC_ATAN2 || fn == VRT_SPEC_WRAP_TEXEL || fn == VRT_SPEC_NORMALIZE3;
+    if ((two && !b_dev) || (fn == VRT_SPEC_NORMALIZE3 && !c_dev)) return fail(VRT_ERR_INVALID, "vrt_debug_spec: NULL argument");
+    if (n > ((size_t)1 << 31)) return fail(VRT_ERR_UNSUPPORTED, "vrt_debug_spec: more than 2^31 elements");
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(launch_debug_spec(fn, a_dev, b_dev, c_dev, n, out_dev, c->stream));
+    return VRT_OK;
+}
+
 int vrt_debug_brick_counts(vrt_ctx* c, uint64_t out[4])
 {
     if (!c || !out) return fail(VRT_ERR_INVALID, "vrt_debug_brick_counts: NULL argument");

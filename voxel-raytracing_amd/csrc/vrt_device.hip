@@ -527,6 +527,41 @@ __global__ __launch_bounds__(256) void k_debug_sky(const DevScene s, const float
     out[4 * i] = sx | (sy << 16); out[4 * i + 1] = tx | (ty << 16); out[4 * i + 2] = sure ? 1u : 0u; out[4 * i + 3] = __float_as_uint(un);
 }
 
+// Diagnostic (vrt_debug_spec): one primitive of vrt_spec.h per element, bit patterns in, bit patterns out -- lane i of the launch
+// evaluates element i (no reordering: which elements share a wave is part of what tests/test_gpu_spec.py varies).  fn as in
+// include/vrt.h; out holds one word per element, three (x, y, z) for normalize3.  Nothing is restated here: the calls below are
+// the header's functions under this object's flags.
+__global__ __launch_bounds__(256) void k_debug_spec(uint32_t fn, const uint32_t* __restrict__ a, const uint32_t* __restrict__ b,
+                                                    const uint32_t* __restrict__ c, size_t n, uint32_t* __restrict__ out)
+{
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float x = __uint_as_float(a[i]);
+    switch (fn) {
+    case 0: out[i] = __float_as_uint(sqrt_spec(x)); break;
+    case 1: out[i] = __float_as_uint(div_spec(x, __uint_as_float(b[i]))); break;
+    case 2: out[i] = __float_as_uint(atan2_spec(x, __uint_as_float(b[i]))); break;
+    case 3: out[i] = __float_as_uint(asin_spec(x)); break;
+    case 4: out[i] = __float_as_uint(exp_spec(x)); break;
+    case 5: out[i] = (uint32_t)unorm8(x); break;
+    case 6: out[i] = (uint32_t)(int32_t)snorm8(x); break;
+    case 7: out[i] = wrap_texel(x, b[i]); break;
+    case 8: {
+        const f3 d = normalize3(mk3(x, __uint_as_float(b[i]), __uint_as_float(c[i])));
+        out[3 * i] = __float_as_uint(d.x); out[3 * i + 1] = __float_as_uint(d.y); out[3 * i + 2] = __float_as_uint(d.z);
+        break;
+    }
+    default: break;
+    }
+}
+
+hipError_t launch_debug_spec(uint32_t fn, const uint32_t* a, const uint32_t* b, const uint32_t* c, size_t n, uint32_t* out, hipStream_t s)
+{
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_debug_spec, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, fn, a, b, c, n, out);
+    return hipGetLastError();
+}
+
 // development build (-DVRT_TRACE_COUNTERS): the brick march's look-up counters, read and reset
 hipError_t debug_brick_counts(unsigned long long out[4])
 {

@@ -68,8 +68,12 @@ VRT_HD float atan_unit(float t)
     float y0 = 0.0f;
     const bool red = t > 0.4142135623730950f;
 #if defined(__HIP_DEVICE_COMPILE__)
-    // the reduced argument for the lanes that need it: numerator in [-0.586, 0], denominator in (1.41, 2] -- always operands
-    // the short division is exact for (NaN lanes, atan(0, 0), take the plain operator with the whole wave)
+    // The host's `if (red) t = (t - 1) / (t + 1)` as a select: the quotient is computed by div_spec -- the plain, correctly
+    // rounded operator -- for every active lane and kept only where `red` holds, so a lane's value is the host's whatever the
+    // other lanes of its wave hold (a lane that is not `red`, a NaN lane and atan(0, 0) included, divides and drops the
+    // quotient).  The ballot only lets a wave with no `red` lane skip the division's instructions: a uniform branch, cheaper
+    // than the divergent one.  tests/test_gpu_spec.py submits the same pairs in waves that are all `red`, mixed, and `red` in
+    // one lane, and holds each to the oracle.
     if (__ballot(red) != 0ull) {
         const float n = t - 1.0f, d = t + 1.0f;
         const float q = div_spec(n, d);
@@ -134,13 +138,22 @@ VRT_HD float exp_spec(float x)
 }
 
 // float -> UNORM8 / SNORM8 (render-target conversion of RGBA8_UNORM / RGBA8_SNORM, geometry_stage.cpp:22,32).
+// The clamp's fmaxf ignores a NaN, so a NaN ends at the lower bound: unorm8(NaN) = 0, snorm8(NaN) = -127.  The device's max does so for
+// every NaN; a host libm may answer NaN for a SIGNALLING one (glibc since 2.25 does, and the clamp then ends at the UPPER bound), so
+// the host path says it outright.  tests/test_spec_cpu.py and tests/test_gpu_spec.py hold both to the oracle on all 2^32 patterns.
 VRT_HD uint8_t unorm8(float c)
 {
+#if !defined(__HIP_DEVICE_COMPILE__)
+    if (c != c) return 0;
+#endif
     c = fminf(fmaxf(c, 0.0f), 1.0f);
     return (uint8_t)floorf(c * 255.0f + 0.5f);
 }
 VRT_HD int8_t snorm8(float c)
 {
+#if !defined(__HIP_DEVICE_COMPILE__)
+    if (c != c) return -127;
+#endif
     c = fminf(fmaxf(c, -1.0f), 1.0f);
     return (int8_t)floorf(c * 127.0f + 0.5f);
 }

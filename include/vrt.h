@@ -151,6 +151,11 @@ int  vrt_ctx_synchronize(vrt_ctx* ctx);                     /* device.waitIdle()
  * speed only, never a result -- the tests render "the same frame without X" with them.  Name (default), who looks at it:
  *   every vrt_render_geometry* call:  "tile_tags" (1), "box_rect" (1), "fast_loop" (1), "thresh_runs" (1), "hit_table" (1), "sky_fast" (1),
  *                                     "sky_span" (1: the sky waves of an all-sky 32x8 span store whole rows; needs sky_fast),
+ *                                     "sky_plane" (1: in primary-only launches of more than 8 frames the sky waves of frames that share a view
+ *                                     -- ray-generation constants, screen size and sky equal bit for bit -- load the miss colour from a plane
+ *                                     computed once per view, csrc/vrt_miss_plane.h; needs sky_fast; 0: every sky wave decides its texel),
+ *                                     (read-only through vrt_ctx_get_option, for the tests: "sky_planes_built", "sky_planes_held",
+ *                                     "sky_plane_min_group" and "sky_plane_of_<f>" -- the plane frame f of the latest launch loaded from, 0: none),
  *                                     "no_bounce_kernel" (1), "ao_batch" (1: the AO rays of a wave from a pool in LDS every lane draws on),
  *                                     "packed_bounces" (1: the bounce chain as one word per hit on dense scenes; 2: on brick scenes too,
  *                                     where it measured slower; 0: the stack of hits), "tags_async" (0: the tile tags of a launch on a

@@ -24,7 +24,7 @@ static const OptName kOptNames[] = {
     {"tile_tags", "VRT_TILE_TAGS", &DevOptions::tile_tags}, {"box_rect", "VRT_BOX_RECT", &DevOptions::box_rect},
     {"xcd_regions", "VRT_XCD_REGIONS", &DevOptions::xcd_regions}, {"fast_loop", "VRT_FAST_LOOP", &DevOptions::fast_loop},
     {"no_bounce_kernel", "VRT_NO_BOUNCE_KERNEL", &DevOptions::no_bounce_kernel}, {"sky_fast", "VRT_SKY_FAST", &DevOptions::sky_fast},
-    {"sky_span", "VRT_SKY_SPAN", &DevOptions::sky_span},
+    {"sky_span", "VRT_SKY_SPAN", &DevOptions::sky_span}, {"sky_plane", "VRT_SKY_PLANE", &DevOptions::sky_plane},
     {"packed_bounces", "VRT_PACKED_BOUNCES", &DevOptions::packed_bounces}, {"ao_batch", "VRT_AO_BATCH", &DevOptions::ao_batch}, {"tags_async", "VRT_TAGS_ASYNC", &DevOptions::tags_async},
     {"hit_table", "VRT_HIT_TABLE", &DevOptions::hit_table},
     {"thresh_runs", "VRT_THRESH_RUNS", &DevOptions::thresh_runs}, {"segment_budget", "VRT_SEGMENT_BUDGET", &DevOptions::segment_budget}, {"denoise_th16", "VRT_DENOISE_TH", &DevOptions::denoise_th16}, {"denoise_packed", "VRT_DENOISE_PACKED", &DevOptions::denoise_packed},
@@ -120,6 +120,15 @@ int vrt_ctx_get_option(vrt_ctx* c, const char* name, int32_t* value)
     if (!c || !name || !value) return fail(VRT_ERR_INVALID, "vrt_ctx_get_option: NULL argument");
     for (const OptName& o : kOptNames)
         if (strcmp(o.name, name) == 0) { *value = c->opt.*(o.field); return VRT_OK; }
+    // read-only state of the miss-colour planes (vrt_miss_plane.h), for the tests: planes computed so far, planes held, the rule's
+    // minimum group, and "sky_plane_of_<f>": the plane frame f of the latest launch loaded from (1 .. 4; 0: none)
+    if (strcmp(name, "sky_planes_built") == 0) { *value = (int32_t)c->sky_planes_built; return VRT_OK; }
+    if (strcmp(name, "sky_planes_held") == 0) { *value = 0; for (int q = 0; q < VRT_SKY_PLANES; q++) *value += c->sky_planes.valid[q] ? 1 : 0; return VRT_OK; }
+    if (strcmp(name, "sky_plane_min_group") == 0) { *value = VRT_SKY_PLANE_MIN_GROUP; return VRT_OK; }
+    if (strncmp(name, "sky_plane_of_", 13) == 0 && name[13] >= '0' && name[13] <= '9') {
+        const int f = atoi(name + 13);
+        if (f < VRT_MAX_TABLE) { *value = c->sky_plane_last[f]; return VRT_OK; }
+    }
     return fail(VRT_ERR_INVALID, std::string("vrt_ctx_get_option: unknown option '") + name + "'");
 }
 
@@ -537,7 +546,8 @@ static int launch_records(vrt_ctx* c, size_t px, GeomParams& p)
 // Tile tags: dense scenes, frames with a box rectangle, launches that do not report the reference's iteration counts.  Takes the
 // next of the context's two tag buffers (*tag_buf), grows it, and fills it: by k_tile_tags, or with the one word per frame that
 // says "trace every block".  tab: the launch's slot table, or -1.
-static int launch_tags(vrt_ctx* c, const vrt_scene* s, const Launch& l, const FrameSlot* slots, int tab, bool counts, GeomParams& p, int* tag_buf)
+static int launch_tags(vrt_ctx* c, const vrt_scene* s, const Launch& l, const FrameSlot* slots, int tab, bool counts, const VerdictPlanes& vp,
+                       GeomParams& p, int* tag_buf)
 {
     const int n = l.n;
     bool want = c->opt.tile_tags != 0 && s->cells_ok && !counts && l.W <= 8128 && l.H <= 8128;
@@ -582,16 +592,17 @@ static int launch_tags(vrt_ctx* c, const vrt_scene* s, const Launch& l, const Fr
             HIPCHK(hipStreamSynchronize(c->stream));
             if (c->tag_stream) HIPCHK(hipStreamSynchronize(c->tag_stream));
             c->verdicts[b].reset(); c->verdict_bytes[b] = 0;
-            HIPCHK(c->verdicts[b].alloc(bytes));
+            // (VRT_VERDICT_HEAD bytes in front of the verdicts: the addresses of the launch's miss-colour planes, k_block_verdicts)
+            HIPCHK(c->verdicts[b].alloc(VRT_VERDICT_HEAD + bytes));
             c->verdict_bytes[b] = bytes;
         }
-        p.verdicts = c->verdicts[b].get();
+        p.verdicts = c->verdicts[b].get() + VRT_VERDICT_HEAD;
     }
     if (!tags) {
         // every frame's one word = tile_gen
         std::vector<uint32_t> ones((size_t)n, c->tile_gen);
         HIPCHK(hipMemcpyAsync(c->tile_tags[b].get(), ones.data(), (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(launch_block_verdicts(p, c->stream));
+        HIPCHK(launch_block_verdicts(p, vp, c->stream));
         return VRT_OK;
     }
     p.cells = s->cells.get(); p.n_cells = s->n_cells; p.cell_size = s->bricks ? 8u : 4u;
@@ -603,7 +614,7 @@ static int launch_tags(vrt_ctx* c, const vrt_scene* s, const Launch& l, const Fr
     const bool async = c->opt.tags_async >= 2 || (c->opt.tags_async != 0 && hipStreamQuery(c->stream) == hipErrorNotReady);
     if (!async) {
         HIPCHK(launch_tile_tags(p, c->stream));
-        HIPCHK(launch_block_verdicts(p, c->stream));
+        HIPCHK(launch_block_verdicts(p, vp, c->stream));
         return VRT_OK;
     }
     if (!c->tag_stream) {
@@ -620,9 +631,48 @@ static int launch_tags(vrt_ctx* c, const vrt_scene* s, const Launch& l, const Fr
     if (c->tag_read_valid[b]) HIPCHK(hipStreamWaitEvent(c->tag_stream, c->tag_read[b], 0));     // the launch that last read this buffer
     if (tab >= 0) HIPCHK(hipStreamWaitEvent(c->tag_stream, c->tab_uploaded[tab], 0));            // the slots the tag kernel reads
     HIPCHK(launch_tile_tags(p, c->tag_stream));
-    HIPCHK(launch_block_verdicts(p, c->tag_stream));
+    HIPCHK(launch_block_verdicts(p, vp, c->tag_stream));
     HIPCHK(hipEventRecord(c->tag_done[b], c->tag_stream));
     HIPCHK(hipStreamWaitEvent(c->stream, c->tag_done[b], 0));
+    return VRT_OK;
+}
+
+// Miss-colour planes (vrt_miss_plane.h: the rule is sky_plane_select's, this is its plumbing): the frames' keys, the rule, and
+// k_miss_plane on the context's stream for every slot the rule wants filled.  vp: what k_block_verdicts hands on to K1.
+static int launch_sky_planes(vrt_ctx* c, const vrt_scene* s, const Launch& l, const FrameSlot* slots, const GeomParams& p, VerdictPlanes& vp)
+{
+    memset(&vp, 0, sizeof vp);
+    memset(c->sky_plane_last, 0, sizeof c->sky_plane_last);
+    const bool eligible = p.table != nullptr && p.fused_shade == 1 && p.sky_fast != 0;
+    if (!eligible || c->opt.sky_plane == 0) return VRT_OK;       // (sky_plane_select says the same; this spares the keys)
+    static_assert(sizeof(RayGenConsts) == 40 && offsetof(RayGenConsts, cd) == 0, "sky_plane_key takes RayGenConsts as ten floats");
+    std::vector<SkyPlaneKey> keys((size_t)l.n);
+    for (int f = 0; f < l.n; f++)
+        keys[(size_t)f] = sky_plane_key(reinterpret_cast<const float*>(&slots[f].rg), slots[f].pc.cam_right, l.W, l.H, p.fast_screen_div, s->shade_gen);
+    SkyPlaneChoice ch;
+    sky_plane_select(c->sky_planes, true, true, l.n, keys.data(), VRT_SKY_PLANE_MIN_GROUP, ch);
+    const size_t px = (size_t)l.W * (size_t)l.H;
+    for (int q = 0; q < VRT_SKY_PLANES; q++) {
+        const int f = ch.build_from[q];
+        if (f < 0) continue;
+        c->sky_planes.valid[q] = false;                          // (until the kernel is in the stream: a failure below leaves no plane behind)
+        if (c->sky_plane_px[q] < px) {
+            HIPCHK(hipStreamSynchronize(c->stream));            // (a launch still in the stream may read the slot's old memory)
+            c->sky_plane_buf[q].reset(); c->sky_plane_px[q] = 0;
+            HIPCHK(c->sky_plane_buf[q].alloc(px * sizeof(uint32_t)));
+            c->sky_plane_px[q] = px;
+        }
+        MissPlaneParams mp;
+        mp.sc = p.sc; mp.rg = slots[f].rg;
+        for (int a = 0; a < 3; a++) mp.cam_right[a] = slots[f].pc.cam_right[a];
+        mp.rcp_w = p.rcp_w; mp.rcp_h = p.rcp_h; mp.fast_screen_div = p.fast_screen_div; mp.W = l.W; mp.H = l.H;
+        mp.plane = c->sky_plane_buf[q].get();
+        HIPCHK(launch_miss_plane(mp, c->stream));
+        c->sky_planes.valid[q] = true;
+        c->sky_planes_built++;
+    }
+    for (int q = 0; q < VRT_SKY_PLANES; q++) vp.plane[q] = c->sky_planes.valid[q] ? c->sky_plane_buf[q].get() : nullptr;
+    for (int f = 0; f < l.n; f++) vp.which[f] = c->sky_plane_last[f] = ch.plane_of[f];
     return VRT_OK;
 }
 
@@ -678,8 +728,11 @@ static int render_frames(vrt_ctx* c, const vrt_scene* s, int n, const vrt_push* 
         }
         p.hit_colors = c->hit_colors.get();
     }
+    VerdictPlanes vp;
+    rc = launch_sky_planes(c, s, l, slots, p, vp);
+    if (rc != VRT_OK) return rc;
     int tag_buf = -1;
-    rc = launch_tags(c, s, l, slots, tab, counts, p, &tag_buf);
+    rc = launch_tags(c, s, l, slots, tab, counts, vp, p, &tag_buf);
     if (rc != VRT_OK) return rc;
     HIPCHK(launch_primary(p, c->stream));
     if (tag_buf >= 0 && c->tag_stream) { HIPCHK(hipEventRecord(c->tag_read[tag_buf], c->stream)); c->tag_read_valid[tag_buf] = true; }

@@ -364,6 +364,9 @@ int vrt_scene_trim(vrt_ctx* c, vrt_scene* s)
     std::lock_guard<std::mutex> lock(s->lazy);
     drop_count_fields(s);
     s->drop_scratch();                                           // (an edit, a flood, a voxelization takes its own again)
+    // the calling context's miss-colour planes (vrt_miss_plane.h): the next launch that wants one builds it again
+    c->sky_planes.clear();
+    for (int q = 0; q < VRT_SKY_PLANES; q++) { c->sky_plane_buf[q].reset(); c->sky_plane_px[q] = 0; }
     return VRT_OK;
 }
 

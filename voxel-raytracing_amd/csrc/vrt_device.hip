@@ -27,6 +27,40 @@ namespace vrt {
 // K1: primary rays
 // ---------------------------------------------------------------------------------------------
 
+// What a sky wave with a miss-colour plane stores for its pixel: zeros in every plane but the colour's, c8 there -- the stores of
+// k_primary's short path, statement for statement (kept there as they are: moved into this function, every kernel's machine code
+// changes).  flags: the tile map's; span_nt: the wave holds two whole rows of an all-sky span (vrt_span.h), whose planes of zeros go
+// out as non-temporal stores; strip_off: the pixel's byte offset in the rank's packed strips.
+__device__ __forceinline__ void store_miss_pixel(const MissPlanes& f, uint32_t flags, bool span_nt, uint32_t i32, uint32_t c8, uint32_t strip_off)
+{
+    if (span_nt && (flags & VRT_MAPFLAG_SIX)) {
+        __builtin_nontemporal_store((vrt_f4){0.0f, 0.0f, 0.0f, 0.0f}, gptr<vrt_f4>(f.position, i32 << 4));
+        __builtin_nontemporal_store((vrt_f2){0.0f, 0.0f}, gptr<vrt_f2>(f.motion, i32 << 3));
+        __builtin_nontemporal_store(0.0f, gptr<float>(f.depth, i32 << 2));
+        __builtin_nontemporal_store(0u, gptr<uint32_t>(f.normal8, i32 << 2));
+        __builtin_nontemporal_store((uint8_t)0, gptr<uint8_t>(f.mask8, i32));
+        *gptr<uint32_t>(f.color8, i32 << 2) = c8;
+        return;
+    }
+    if (flags & VRT_MAPFLAG_SIX) {                       // the reference's six targets and nothing else: six stores, no pointer tested
+        *gptr<vrt_f4>(f.position, i32 << 4) = (vrt_f4){0.0f, 0.0f, 0.0f, 0.0f};
+        *gptr<vrt_f2>(f.motion, i32 << 3) = (vrt_f2){0.0f, 0.0f};
+        *gptr<float>(f.depth, i32 << 2) = 0.0f;
+        *gptr<uint32_t>(f.normal8, i32 << 2) = 0u;
+        *gptr<uint8_t>(f.mask8, i32) = (uint8_t)0;
+        *gptr<uint32_t>(f.color8, i32 << 2) = c8;
+        return;
+    }
+    if (f.position) *gptr<vrt_f4>(f.position, i32 << 4) = (vrt_f4){0.0f, 0.0f, 0.0f, 0.0f};
+    if (f.motion) *gptr<vrt_f2>(f.motion, i32 << 3) = (vrt_f2){0.0f, 0.0f};
+    if (f.depth) *gptr<float>(f.depth, i32 << 2) = 0.0f;
+    if (f.normal8) *gptr<uint32_t>(f.normal8, i32 << 2) = 0u;
+    if (f.mask8) *gptr<uint8_t>(f.mask8, i32) = (uint8_t)0;
+    if (f.hit_id) *gptr<uint8_t>(f.hit_id, i32) = (uint8_t)0;
+    if (f.color8) *gptr<uint32_t>(f.color8, i32 << 2) = c8;
+    if (f.color8_strips) *gptr<uint32_t>(f.color8_strips, strip_off) = c8;
+}
+
 // MODE 0: write hit records for K2 (split);  1: no secondary rays enabled, shade inline;  4: the megakernel without its bounce loop;
 // MODE 5, 6, 7: the megakernel with the bounce chain as one word per hit (color_main_ray_packed: no stack of hits; what the product
 //         traversals launch) for at most 2 / 5 / VRT_MAX_BOUNCES bounces;
@@ -143,6 +177,26 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 8))) voi
     // (two vector registers from here on, whatever they were made from: without this the megakernels' register allocation
     // changes with the choice above and the bounce chain spills one register more)
     asm volatile("" : "+v"(px), "+v"(py));
+    // A skip block of a frame that has a miss-colour plane (vrt_miss_plane.h; bits 2 - 4 of the verdict byte: which of the launch's
+    // planes, 0 = none): the pixel's colour word is in the plane -- no ray is generated, no texel decided.  The plane's address is
+    // one of the four in front of the verdicts (k_block_verdicts put them there), requested in one batch with the planes a miss is
+    // stored to.  Ahead of ray generation, which these waves have no use for.
+    if constexpr (kVerdict) {
+        const uint32_t which = (verdict >> 2) & 7u;
+        if ((verdict & 1u) != 0u && which != 0u) {
+            const_u32_ptr hp = (const_u32_ptr)((const __attribute__((address_space(4))) char*)P.verdicts - VRT_VERDICT_HEAD + 8u * (which - 1u));
+            asm volatile("" : "+s"(hp));
+            const MissPlanes f = SlotOf<true>::miss_planes(P, frame);
+            uint32_t pw[2] = {hp[0], hp[1]};
+            asm volatile("" :: "s"(f.color8), "s"(f.position), "s"(pw[0]), "s"(pw[1]));      // (one batch, one wait)
+            const uint32_t* plane;
+            __builtin_memcpy(&plane, pw, 8);
+            const uint32_t i32 = (uint32_t)py * (uint32_t)W + (uint32_t)px;
+            const uint32_t c8 = *gptr<const uint32_t>(plane, i32 << 2);
+            store_miss_pixel(f, M.flags, span, i32, c8, ((uint32_t)(yp0 + (py - y0)) * (uint32_t)W + (uint32_t)px) << 2);
+            return;
+        }
+    }
     size_t i = (size_t)py * (size_t)W + (size_t)px;
 
     const DevScene& s = P.sc;
@@ -608,6 +662,26 @@ hipError_t launch_hit_colors(const GeomParams& p, uint32_t* table, hipStream_t s
     return hipGetLastError();
 }
 
+// The miss-colour plane of a view (vrt_miss_plane.h): the word K1 stores in the colour target of a pixel that misses, for every pixel
+// of a W x H frame, by K1's own long miss path -- primary_v, primary_normalize, sky_color, unorm8: the same functions, so the plane
+// holds bit for bit what a sky wave of K1 would store (the short path's texel is the long path's wherever it is sure: vrt_sky.h).
+// One lane per pixel, a workgroup per 256 pixels of a row; plain stores: the plane is read by every frame of its group.
+__global__ __launch_bounds__(256) void k_miss_plane(const MissPlaneParams P)
+{
+    const int px = (int)(blockIdx.x * 256u + threadIdx.x), py = (int)blockIdx.y;
+    if (px >= P.W) return;
+    const f3 v = primary_v(P.rg, P.cam_right[0], P.cam_right[1], P.cam_right[2], P.rcp_w, P.rcp_h, P.fast_screen_div, px, py);
+    const f3 col = sky_color(P.sc, primary_normalize(v));
+    P.plane[(size_t)py * (size_t)P.W + (size_t)px] = (uint32_t)unorm8(col.x) | ((uint32_t)unorm8(col.y) << 8) | ((uint32_t)unorm8(col.z) << 16);
+}
+
+hipError_t launch_miss_plane(const MissPlaneParams& p, hipStream_t s)
+{
+    if (p.W <= 0 || p.H <= 0 || !p.plane) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_miss_plane, dim3((unsigned)((p.W + 255) / 256), (unsigned)p.H), dim3(256), 0, s, p);
+    return hipGetLastError();
+}
+
 // ---------------------------------------------------------------------------------------------
 // Tile tags: which 8x8-pixel blocks of a frame can a primary ray meet anything in?  One lane per occupied 4^3-voxel cell of
 // the volume (the scene's list of them); the cell, grown by one voxel on every side, is projected through the frame's
@@ -708,8 +782,13 @@ hipError_t launch_tile_tags(const GeomParams& p, hipStream_t s)
 // a 64 x 4 workgroup are 64 neighbouring blocks of four rows: their byte stores are whole 64-byte pieces of a row.
 // ---------------------------------------------------------------------------------------------
 // (table launches only: the slots are read from the table)
-__global__ __launch_bounds__(256) void k_block_verdicts(const GeomParams P)
+// vp: the launch's miss-colour planes (vrt_miss_plane.h) -- which of them each frame loads from goes into bits 2 - 4 of the bytes of
+// the frame's blocks, and the planes' addresses into the VRT_VERDICT_HEAD bytes in front of the verdicts, where K1's sky waves find both
+// without a kernel argument of their own.
+__global__ __launch_bounds__(256) void k_block_verdicts(const GeomParams P, const VerdictPlanes vp)
 {
+    if (blockIdx.x == 0u && blockIdx.y == 0u && blockIdx.z == 0u && threadIdx.y == 0u && threadIdx.x < (uint32_t)VRT_SKY_PLANES)
+        reinterpret_cast<const uint32_t**>(P.verdicts - VRT_VERDICT_HEAD)[threadIdx.x] = vp.plane[threadIdx.x];
     const uint32_t frame = blockIdx.z, col8 = blockIdx.x * 64u + threadIdx.x, row8 = blockIdx.y * 4u + threadIdx.y;
     const uint32_t k = (uint32_t)P.tile_h >> 3;                   // block rows per workgroup tile of K1 (1 or 2)
     const uint32_t blocks_x = (uint32_t)P.tiles_x * ((uint32_t)P.tile_w >> 3), blocks_y = (uint32_t)P.tiles_y_local * k;
@@ -730,16 +809,16 @@ __global__ __launch_bounds__(256) void k_block_verdicts(const GeomParams P)
     for (uint32_t j = 0; j < 4u; j++) tag[j] = verdict_tag(tg + row8 * tags_x, (col8 & ~3u) + j, tags_x, tag_all, gen);
     const bool span_path = (P.map.flags & VRT_MAPFLAG_SKY_SPAN) != 0u;
     P.verdicts[verdict_offset(row8, col8, frame, (uint32_t)P.n_frames, verdict_pitch(blocks_x))] =
-        (uint8_t)block_verdict_byte(tag[0], tag[1], tag[2], tag[3], col8, span_path, (uint32_t)P.W, tag_all, gen, box, py0);
+        (uint8_t)(block_verdict_byte(tag[0], tag[1], tag[2], tag[3], col8, span_path, (uint32_t)P.W, tag_all, gen, box, py0) | ((uint32_t)vp.which[frame] << 2));
 }
 
-hipError_t launch_block_verdicts(const GeomParams& p, hipStream_t s)
+hipError_t launch_block_verdicts(const GeomParams& p, const VerdictPlanes& vp, hipStream_t s)
 {
     const unsigned blocks_x = (unsigned)(p.tiles_x * (p.tile_w / 8)), blocks_y = (unsigned)(p.tiles_y_local * (p.tile_h / 8));
     if (!p.verdicts || blocks_x == 0u || blocks_y == 0u) return hipSuccess;
     if (!p.table) return hipErrorInvalidValue;
     dim3 grid((blocks_x + 63u) / 64u, (blocks_y + 3u) / 4u, (unsigned)p.n_frames), block(64, 4);
-    hipLaunchKernelGGL(k_block_verdicts, grid, block, 0, s, p);
+    hipLaunchKernelGGL(k_block_verdicts, grid, block, 0, s, p, vp);
     return hipGetLastError();
 }
 

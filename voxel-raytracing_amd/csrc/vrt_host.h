@@ -90,6 +90,7 @@ struct DevOptions {
     int ao_batch = 1;          // the AO rays of a wave from a pool in LDS that every lane draws on (df_ao_pool_loop, brick_ao_pool)
     int sky_fast = 1;          // sky texel of waves that cannot hit anything by vrt_sky.h
     int sky_span = 1;          // the sky waves of an all-sky 32x8 span store whole rows (vrt_span.h); 0: every wave its own 8x8 block
+    int sky_plane = 1;         // the sky waves of primary-only table launches load the miss colour from their view's plane (vrt_miss_plane.h); 0: every wave decides its texel
     int thresh_runs = 1;       // primary rays through df_prim_loop (long runs by threshold)
     int segment_budget = 1;    // segment queries march a wave with min(max_steps, what its 64 segments can need) (vrt_query_seg.hip)
     int hit_table = 1;         // launches without secondary rays take a hit's colour from the table of colorHit() over materials x normals
@@ -139,6 +140,14 @@ struct vrt_ctx {
     // buffer b, grown (behind a synchronise of both streams) when a launch needs more, never shrunk, released with the context
     vrt::DevBuf<uint8_t> verdicts[2];
     size_t verdict_bytes[2] = {0, 0};
+    // miss-colour planes (k_miss_plane; vrt_miss_plane.h says when a launch uses one): W x H words per slot, built on `stream` ahead
+    // of the launch that first uses them and read by K1 on `stream` only -- a slot is rewritten behind every launch that read it.
+    // Each slot allocated when first built, grown when a larger frame takes it, released with the context and by vrt_scene_trim
+    vrt::SkyPlaneCache sky_planes;
+    vrt::DevBuf<uint32_t> sky_plane_buf[VRT_SKY_PLANES];
+    size_t sky_plane_px[VRT_SKY_PLANES] = {0, 0, 0, 0};
+    uint64_t sky_planes_built = 0;     // k_miss_plane launches so far (vrt_ctx_get_option)
+    uint8_t sky_plane_last[VRT_MAX_TABLE] = {};   // which plane each frame of the latest launch loaded from (0: none; vrt_ctx_get_option)
     uint32_t tile_gen = 0;
     int tag_flip = 0;
     hipStream_t tag_stream = nullptr;

@@ -15,6 +15,7 @@
 #include "vrt_reproject.h"
 #include "vrt_upsample.h"
 #include "vrt_raygen.h"
+#include "vrt_miss_plane.h"
 
 namespace vrt {
 
@@ -217,6 +218,25 @@ struct GeomParams {
 };
 static_assert(sizeof(GeomParams) == 2688, "GeomParams grew: every kernel that takes it changes (tools/kernel_digest.py)");
 
+// Miss-colour planes (vrt_miss_plane.h: when a launch uses one).  k_block_verdicts' second argument: the planes of the launch and
+// which of them each frame's sky waves load from (0: none, q + 1: plane[q]); it stores the addresses in the VRT_VERDICT_HEAD bytes
+// in front of GeomParams::verdicts (the last 8 * VRT_SKY_PLANES of them) and the choice in bits 2 - 4 of the frame's verdict bytes.
+#define VRT_VERDICT_HEAD 64u
+struct VerdictPlanes {
+    const uint32_t* plane[VRT_SKY_PLANES];
+    uint8_t         which[VRT_MAX_TABLE];
+};
+static_assert(8u * VRT_SKY_PLANES <= VRT_VERDICT_HEAD && VRT_SKY_PLANES < 8 && VRT_SKY_PLANE_MAX_FRAMES == VRT_MAX_TABLE, "the planes' addresses fit the head, their numbers three bits");
+// k_miss_plane: everything a pixel's miss colour depends on, and where the W x H words go
+struct MissPlaneParams {
+    DevScene     sc;
+    RayGenConsts rg;
+    float        cam_right[3];
+    float        rcp_w, rcp_h;
+    int32_t      fast_screen_div, W, H;
+    uint32_t*    plane;
+};
+
 #define VRT_DENOISE_SEGS 64    // counters of redone pixels (diagnostics): a workgroup adds to counter (its index % 64)
 struct DenoiseParams {
     const uint8_t* color_in;
@@ -360,7 +380,8 @@ hipError_t launch_debug_sky(const DevScene& sc, const float* v, size_t n, uint32
 hipError_t launch_debug_spec(uint32_t fn, const uint32_t* a, const uint32_t* b, const uint32_t* c, size_t n, uint32_t* out, hipStream_t s);
 hipError_t launch_open_cells(const uint8_t* vox, int W, int H, int D, uint8_t* df, size_t stride, uint8_t* tmp0, uint8_t* tmp1, hipStream_t s, int mark = 0);
 hipError_t launch_tile_tags(const GeomParams& p, hipStream_t s);
-hipError_t launch_block_verdicts(const GeomParams& p, hipStream_t s);   // (nothing where p.verdicts is NULL)
+hipError_t launch_block_verdicts(const GeomParams& p, const VerdictPlanes& vp, hipStream_t s);   // (nothing where p.verdicts is NULL)
+hipError_t launch_miss_plane(const MissPlaneParams& p, hipStream_t s);
 hipError_t launch_hit_colors(const GeomParams& p, uint32_t* table, hipStream_t s);
 hipError_t launch_pad_vox(const uint8_t* vox, int W, int H, int D, uint8_t* dst, hipStream_t s);
 // scene edits: the volume and the box [lo, hi) of it that is rewritten

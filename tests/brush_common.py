@@ -173,14 +173,19 @@ def brush_sequence(dims, seed):
     return seq
 
 
+def needs_more_slots(vol, out, free_slots):
+    """the brick edits' own rule, for whichever tool rewrote vol into out, from the numpy volumes: the bricks that appear are more
+    than the free slots and the slots of the bricks that vanish"""
+    before, after = brick_occupancy(vol), brick_occupancy(out)
+    appear, vanish = int((after & ~before).sum()), int((before & ~after).sum())
+    return appear > free_slots + vanish
+
+
 def expected(vol, o, bricks, free_slots):
     """-> (the volume after, (changed, lo, size), refused): refused is the brick edits' own rule, from the numpy volumes"""
     out, res = R.brush(vol, o["shape"], o["mode"], o["p"], o["id"], o["match"])
-    if bricks and res[0]:
-        before, after = brick_occupancy(vol), brick_occupancy(out)
-        appear, vanish = int((after & ~before).sum()), int((before & ~after).sum())
-        if appear > free_slots + vanish:
-            return vol, (0, [0, 0, 0], [0, 0, 0]), True
+    if bricks and res[0] and needs_more_slots(vol, out, free_slots):
+        return vol, (0, [0, 0, 0], [0, 0, 0]), True
     return out, res, False
 
 
